@@ -2,7 +2,7 @@
 """bench.py — Mcells/s per RK3 step of the headline equation (BASELINE.json):
 WENO5 advection by the vortex-deformation field + Eikonal reinitialisation, fp64, RK3, NeumannBC.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1: 512³ on one MI355X (the configuration the metric is quoted on).
 N > 1 (launched by torch.distributed.run, one rank per GPU): the grid is 1024 × 1024 × 128·N,
@@ -17,6 +17,10 @@ self-check of the two stage orders, the timed loop, the JSON line.  It measures 
 A "step" is one pass of the reference's step loop body (src/timestepping.jl:104-116):
 compute_cfl + the 3 fused RK3 stage kernels + ghost fills (hooks = identity).  Inputs are resident
 in HBM when the timed region starts.  One JSON line is printed by rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (with its roofline block, read from HIP events of the
+same timed steps).  `--full` adds what the headline figure does not need: the CPU baseline of the oracle (`cpu_baseline`; `--cpu-full` for
+SURVEY.md §8d's longer sample).  `--dump-outputs DIR` writes what the last timed step left for a caller (see dump_outputs).
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ os.environ.setdefault("LSM_COMM_TIMEOUT_MS", "30000")     # a rank that waits fo
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_BYTES = 32 << 20   # --dump-outputs: the seeded sample of ϕ, over all ranks (the plane and the times come on top)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec (≈6.3 TB/s achievable)
 FP64_PEAK_TFLOPS = 78.6
 
@@ -51,6 +56,25 @@ def one_step(eq, tc):
     dt = eq.integrator.cfl * eq.compute_cfl(tc)
     eq._advance(tc, dt)
     return tc + dt
+
+
+def dump_outputs(out_dir, eq, tc, rank, world):
+    """What a caller of the timed path receives after its last step, as DIR/<name>.npy (float64): the level set ϕ —
+    the state's interior as current_state().values() hands it over, Fortran order — and the time it has reached.
+    ϕ is 1 GiB at 512³, so `phi_sample` holds the nodes at a fixed, seeded set of flat (Fortran-order) indices, sorted,
+    and `phi_plane_z` (one GPU) the whole plane through the initial sphere's centre (z = 0.35); `t` = [the time reached].
+    Ranks of a slab run write their own slab's sample with a `_rank<r>` suffix."""
+    phi = np.asarray(eq.current_state().values(), dtype=np.float64)
+    flat = phi.reshape(-1, order="F")
+    k = DUMP_BYTES // 8 // world
+    idx = np.arange(flat.size) if flat.size <= k else np.unique(np.random.default_rng(20240611).integers(0, flat.size, size=k))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"phi_sample": flat[idx], "t": np.array([tc])}
+    if world == 1:
+        arrays["phi_plane_z"] = np.ascontiguousarray(phi[:, :, int(round(0.35 * (phi.shape[2] - 1)))])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(n_sample, threads, steps=1):
@@ -152,15 +176,21 @@ def main():
     ap.add_argument("--prewarm", type=int, default=10, help="untimed steps before the warm-up steps: the device's ramp out of idle (set-up)")
     ap.add_argument("--n", type=int, default=512, help="cells per side of the per-GPU 512³-equivalent workload")
     ap.add_argument("--mode", default="fast", choices=["fast", "strict"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=256, help="side of the single-thread oracle sample")
-    ap.add_argument("--cpu-full", action="store_true", help="SURVEY.md §8d's full CPU sample: 10 steps at 256^3 on one core, 2 at 512^3 on all (minutes)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline of the oracle (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, a seeded sample of ϕ: see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--cpu-sample", type=int, default=256, help="side of the single-thread oracle sample (--full)")
+    ap.add_argument("--cpu-full", action="store_true", help="SURVEY.md §8d's full CPU sample: 10 steps at 256^3 on one core, 2 at 512^3 on all (minutes; implies --full)")
     ap.add_argument("--profile-every", type=int, default=4, help="HIP-event pairs around every N-th stage launch of the timed region (1 = all)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "local"],
                     help="rccl: one process per GPU (torch.distributed.run); local: --gpus N rank THREADS on device 0 over the in-process transport (rehearsal)")
     ap.add_argument("--config", default="headline", choices=["headline", "2", "3", "5", "5r"],
                     help="headline = BASELINE config 4's equation at 512^3 on one GPU (the metric); 2, 3, 5: the other single-GPU BASELINE configs; 5r: config 5 with reinitialize! every 10 steps (tools/configs.py)")
     args = ap.parse_args()
+    args.full = args.full or args.cpu_full
+    if args.dump_outputs and args.config != "headline":
+        ap.error("--dump-outputs writes the headline workload's outputs; it does not apply to --config " + args.config)
     if args.config != "headline":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import configs
@@ -295,6 +325,8 @@ def run(args, lsm, torch, ctx):
     n_launch, stage_ms = eq.backend.profile_read()
     eq.backend.profile_enable(False)
     el = max(ctx.gather(el))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eq, tc, rank, world)
 
     ms_per_step = el / args.steps * 1e3
     mcells = cells * args.steps / el / 1e6
@@ -371,7 +403,7 @@ def run(args, lsm, torch, ctx):
     out["fp64_vector"] = {"achieved_tflops": round(local_cells * 3 * args.steps * flop_per_node_stage / (stage_ms * 1e-3) / 1e12, 2)
                           if n_launch else 0.0, "peak_tflops": FP64_PEAK_TFLOPS,
                           "note": "algorithmic flop estimate from the ISA of the fused stage kernel (DESIGN.md §3.1)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the oracle on ONE core (the reference's hot path is single-threaded, src/timestepping.jl:101-202)
         # and OpenMP over all host cores.  Default: 2 RK3 steps at 256^3 on one core, 2 at 512^3 on all cores (≈25 s each);
         # --cpu-full: 10 steps at 256^3 on one core as SURVEY asks (≈2 min; the rate is the same: profiles/r3/cpu_full.json).

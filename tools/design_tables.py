@@ -43,7 +43,7 @@ def configs_table():
     rows = ["| what | figure | file |", "|---|---|---|"]
     b = json.load(open(os.path.join(P, "bench_default_run.json")))
     r = b["roofline"]
-    rows.append("| headline, 512³ WENO5 advect + Eikonal RK3 (`bench.py --steps 20 --warmup 3`) | %.1f k Mcells/s, %.3f ms/step; stage kernel %.4f ms = %.0f GB/s algorithmic = **%.3f of HBM peak**; HBM traffic %s | `bench_default_run.json` |" % (
+    rows.append("| headline, 512³ WENO5 advect + Eikonal RK3 (`bench.py --full --steps 20 --warmup 3`) | %.1f k Mcells/s, %.3f ms/step; stage kernel %.4f ms = %.0f GB/s algorithmic = **%.3f of HBM peak**; HBM traffic %s | `bench_default_run.json` |" % (
         b["value"] / 1e3, b["ms_per_step"], r["avg_launch_ms"], r["achieved"], r["frac"],
         "%.2f GB per launch (%.2f × algorithmic)" % (r["traffic"] / 1e9, r["traffic"] / r["algorithmic_bytes_per_launch"]) if r.get("traffic") else "n/a"))
     c = b.get("cpu_baseline")
@@ -53,7 +53,7 @@ def configs_table():
     f = os.path.join(P, "cpu_full.json")
     if os.path.exists(f):
         c = json.load(open(f))["cpu_baseline"]
-        rows.append("| the full CPU sample of SURVEY.md §8d (`bench.py --cpu-full`) | %.2f Mcells/s on 1 core: %s | `cpu_full.json` |" % (c["value"], c["sample"]))
+        rows.append("| the full CPU sample of SURVEY.md §8d (`bench.py --full --cpu-full`) | %.2f Mcells/s on 1 core: %s | `cpu_full.json` |" % (c["value"], c["sample"]))
     c2 = json.load(open(os.path.join(P, "bench_config2.json")))["detail"]
     rows.append("| config 2, 2048² Zalesak | advection %.4f ms/step (stage %.4f ms, %.1f k Mcells/s), frozen-sign reinitialisation %.4f ms/step | `bench_config2.json`, `kernel_stats_config2.csv` |" % (
         c2["advect_ms_per_step"], c2["advect_stage_ms"], c2["advect_Mcells_s"] / 1e3, c2["reinit_ms_per_step"]))

@@ -21,7 +21,7 @@ LSM_STAGE_TAIL=0 python3 tools/timeline_probe.py 512 > $OUT/timeline_probe_no_ta
 (cd tools && python3 tail_probe.py && LSM_STAGE_TAIL=0 python3 tail_probe.py) > $OUT/tail_probe.jsonl 2> $OUT/tail_probe.err
 python3 tools/make_profile_summary.py $OUT $OUT/pmc_per_dispatch.json > $OUT/summary.log 2>&1
 mkdir -p profiles/$RND && cp $OUT/pmc_per_dispatch.json profiles/$RND/pmc_per_dispatch.json   # the bench line below reads it (same build, same box)
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+python3 bench.py --full --steps 20 --warmup 3 > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
 for c in 2 3 5; do python3 bench.py --config $c > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err; done
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c3 -- python3 bench.py --config 3 --steps 4 > /dev/null 2> $OUT/trace_c3.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c2 -- python3 bench.py --config 2 --steps 20 > /dev/null 2> $OUT/trace_c2.err
