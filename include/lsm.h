@@ -38,8 +38,9 @@ enum {
     LSM_ERR_INVALID = -1,    /* bad argument / unsupported combination */
     LSM_ERR_HIP = -2,        /* a HIP runtime call failed */
     LSM_ERR_NO_DEVICE = -3,
-    LSM_ERR_COMM = -4        /* multi-GPU: a peer rank left / aborted / did not answer in time, or RCCL failed; the
+    LSM_ERR_COMM = -4,       /* multi-GPU: a peer rank left / aborted / did not answer in time, or RCCL failed; the
                                 communicator stays failed (lsm_comm_detach + a new attach to go on) */
+    LSM_ERR_NOT_CONVERGED = -5   /* an iterative solve (lsm_advance_i2oe) broke down or did not reach its tolerance */
 };
 
 /* CartesianGrid (src/meshes.jl:1-5): lower/upper corner and node counts of the GLOBAL grid.
@@ -216,6 +217,24 @@ int lsm_advance_rk2(LsmHandle* h, const LsmTerm* terms, int nterms, void* phi, v
                     double tc, double dt, LsmStageHook hook, void* user);
 int lsm_advance_rk3(LsmHandle* h, const LsmTerm* terms, int nterms, void* phi, void* buf1, void* buf2,
                     double tc, double dt, LsmStageHook hook, void* user);
+
+/* ---- SemiImplicitI2OE (src/timestepping.jl:204-426): ONE step of the semi-implicit I2OE scheme for a single AdvectionTerm,
+ *      phi := A⁻¹ rhs with the reference's global system (:254-362; fac = dt/(2·Πh), inflow implicit, outflow explicit, face
+ *      velocity ½(v_p + v_q) or v_p at a LinearExtrapolationBC ghost).  The velocity is term->coeff at time tc (CONST, ROTATION,
+ *      SEPARABLE, FIELD); term->scheme is ignored, as in the reference.  The reference solves with a sparse direct solver; this
+ *      call runs unpreconditioned BiCGSTAB, matrix-free, from x₀ = ϕ until ‖r‖₂ ≤ rtol·‖rhs‖₂ (the recursive residual), at most
+ *      max_iters iterations, with every scalar on the device and the host reading the solver's status once per chunk of
+ *      iterations.  Results therefore match the reference to the tolerance, not bitwise, and both arithmetic modes run the same
+ *      solver.  Float32 storage: fp64 arithmetic throughout, the result rounded on store (LSM_DTYPE_F32).
+ *      iters_out / rel_residual_out (may be NULL): iterations taken and ‖r‖₂/‖rhs‖₂.  Synchronous.
+ *      LSM_ERR_INVALID (nothing runs): a term other than LSM_TERM_ADVECTION, fewer than 3 nodes in a dimension, a boundary
+ *      condition other than periodic, NeumannBC (ExtrapolationBC degree 0) or LinearExtrapolationBC (degree 1), a communicator
+ *      attached (single device only).  LSM_ERR_NOT_CONVERGED: breakdown (ρ, ω or r̂·v zero, or a non-finite value) or max_iters
+ *      reached; lsm_last_error gives the iterations and the residual, and phi is left unchanged.
+ *      The solver's device buffers (9 vectors + the face coefficients, ≈ 12 doubles per node in 3-D) are kept on the handle,
+ *      grown on first use and freed by lsm_destroy. */
+int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, double dt, double rtol, int max_iters, int* iters_out,
+                     double* rel_residual_out);
 
 /* ---- multi-GPU: the grid is cut into slabs of the LAST dimension, one handle per slab (lsm_create with an
  *      LsmSlab and LSM_BC_NONE on the faces towards neighbouring ranks — on BOTH faces of every rank when that dimension

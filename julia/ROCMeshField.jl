@@ -289,6 +289,36 @@ function _hook(terms, fields)
     return @cfunction($cb, Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Float64))
 end
 
+# SemiImplicitI2OE (src/timestepping.jl:207-244): the step loop of the reference with the global solve on the device
+# (lsm_advance_i2oe: matrix-free BiCGSTAB to ‖r‖₂ ≤ 1e-13‖rhs‖₂ instead of the sparse direct solve).  The reference's checks
+# come first and throw its ArgumentErrors; a solve that breaks down or runs out of iterations is an ErrorException.
+function LSM._integrate!(ls, ϕ::ROCMeshField, integrator::LSM.SemiImplicitI2OE, terms, tc, tf, Δt_max, prehook, posthook;
+                         rtol = 1.0e-13, max_iters = 500)
+    LSM._validate_i2oe_setup(ϕ, terms)
+    ϕ.h.world > 1 && throw(ArgumentError("SemiImplicitI2OE runs on a single device: a slab decomposition is not supported"))
+    for d in 1:length(ϕ.bcs), bc in ϕ.bcs[d]
+        bc isa Union{LSM.PeriodicBC, LSM.ExtrapolationBC{0}, LSM.ExtrapolationBC{1}} ||
+            error("boundary condition $bc is not supported by SemiImplicitI2OE")
+    end
+    term = only(terms)
+    α = LSM.cfl(integrator)
+    while tc <= tf - eps(tc)
+        prehook(ls)
+        LSM.update_term!(term, ϕ, tc)
+        Δt = min(Δt_max, α * LSM.compute_cfl(terms, ϕ, tc), tf - tc)
+        ts = [_term(term, ϕ, tc)]
+        iters, res = Ref{Cint}(0), Ref{Float64}(0.0)
+        code = ccall((:lsm_advance_i2oe, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{LsmTerm}, Ptr{Cvoid}, Float64, Float64, Float64, Cint, Ref{Cint}, Ref{Float64}),
+            ϕ.h.ptr, ts, pointer(ϕ.buf), tc, Δt, rtol, max_iters, iters, res)
+        _check(ϕ.h.ptr, code, "lsm_advance_i2oe")
+        tc += Δt
+        ls.t = tc
+        posthook(ls)
+    end
+    ls.t = tf
+    return nothing
+end
+
 LSM._alloc_buffers(::LSM.ForwardEuler, ϕ::ROCMeshField) = (copy(ϕ),)
 LSM._alloc_buffers(::Union{LSM.RK2, LSM.RK3}, ϕ::ROCMeshField) = (copy(ϕ), copy(ϕ))
 

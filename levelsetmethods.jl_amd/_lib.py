@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 GHOST = 3
 MAX_TERMS = 8
-OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_COMM = 0, -1, -2, -3, -4
+OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_COMM, ERR_NOT_CONVERGED = 0, -1, -2, -3, -4, -5
 BC_PERIODIC, BC_EXTRAPOLATION, BC_SYMMETRY, BC_NONE = 0, 1, 2, 3
 TERM_ADVECTION, TERM_NORMAL_MOTION, TERM_CURVATURE, TERM_EIKONAL = 0, 1, 2, 3
 SCHEME_UPWIND, SCHEME_WENO5 = 0, 1
@@ -93,6 +93,8 @@ _SIGS = [
                                   C.c_double, StageHook, C.c_void_p]),
     ("lsm_advance_rk3", C.c_int, [_H, C.POINTER(LsmTerm), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                   C.c_double, StageHook, C.c_void_p]),
+    ("lsm_advance_i2oe", C.c_int, [_H, C.POINTER(LsmTerm), C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("lsm_comm_unique_id", C.c_int, [C.c_void_p]),
     ("lsm_comm_attach_rccl", C.c_int, [_H, C.c_void_p, C.c_int, C.c_int]),
     ("lsm_comm_attach_local", C.c_int, [C.POINTER(_H), C.c_int]),
@@ -213,7 +215,11 @@ class LsmCommError(LsmError):
     """LSM_ERR_COMM: a peer rank left, aborted or did not answer in time; the communicator stays failed."""
 
 
+class LsmNotConvergedError(LsmError):
+    """LSM_ERR_NOT_CONVERGED: an iterative solve (lsm_advance_i2oe) broke down or did not reach its tolerance."""
+
+
 def check(handle, code, what=""):
     if code != OK:
         msg = lib().lsm_last_error(handle)
-        raise (LsmCommError if code == ERR_COMM else LsmError)(f"{what} failed ({code}): {msg.decode() if msg else ''}")
+        raise {ERR_COMM: LsmCommError, ERR_NOT_CONVERGED: LsmNotConvergedError}.get(code, LsmError)(f"{what} failed ({code}): {msg.decode() if msg else ''}")

@@ -974,6 +974,20 @@ class RK3(TimeIntegrator):
     name, _describe = "rk3", "RK3 (3rd order TVD Runge-Kutta)"
 
 
+class SemiImplicitI2OE(TimeIntegrator):
+    """SemiImplicitI2OE(cfl = 2.0) — the semi-implicit I2OE scheme for one AdvectionTerm (src/timestepping.jl:68-92,204-426).
+    Every step solves the reference's global linear system on the device (lsm_advance_i2oe: matrix-free BiCGSTAB) instead of
+    the reference's sparse direct solve.  Extra keywords of this implementation, not part of `show`: `rtol`, the tolerance on
+    ‖r‖₂/‖rhs‖₂, and `max_iters`, the iterations a step may take before it fails with LsmNotConvergedError."""
+    name, _describe = "i2oe", "SemiImplicitI2OE (semi-implicit advection, Mikula et al.)"
+
+    def __init__(self, cfl=2.0, *, rtol=1e-13, max_iters=500):
+        super().__init__(cfl)
+        self.rtol, self.max_iters = float(rtol), int(max_iters)
+        if not self.rtol > 0 or self.max_iters < 1:
+            raise ValueError("SemiImplicitI2OE: rtol must be positive and max_iters at least 1")
+
+
 def _jl_min(*xs):
     m = xs[0]
     for x in xs[1:]:
@@ -1513,6 +1527,8 @@ def integrate_(ls, tf, dt=float("inf"), prehook=None, posthook=None):
     tc = ls.current_time()
     if not tf >= tc:
         raise ValueError(f"final time {tf} must be ≥ initial time {tc}: the level-set equation cannot be solved back in time")
+    if isinstance(ls.integrator, SemiImplicitI2OE):
+        return _integrate_i2oe(ls, tc, tf, dt, prehook, posthook)
     alpha = ls.integrator.cfl
     while tc <= tf - _eps(tc):
         if prehook is not None:
@@ -1526,6 +1542,56 @@ def integrate_(ls, tf, dt=float("inf"), prehook=None, posthook=None):
         if ls._range_checked_at % 64 == 0:
             ls._check_range()
         ls.update_band()   # re-tube before the posthook (no-op on a full grid) — src/timestepping.jl:115
+        if posthook is not None:
+            posthook(ls)
+    ls.t = tf
+    return ls
+
+
+def _bc_jl(bc):
+    if isinstance(bc, SymmetryBC):
+        return "SymmetryBC()"
+    if isinstance(bc, PeriodicBC):
+        return "PeriodicBC()"
+    return f"ExtrapolationBC{{{bc.degree}}}()"
+
+
+def _validate_i2oe(ls):
+    """The reference's checks (src/timestepping.jl:204-205,236-244,366-369), made on the host before any step."""
+    if ls.band:
+        raise ValueError("SemiImplicitI2OE requires a full-grid MeshField, got ROCNarrowBandMeshField")
+    if not (len(ls.terms) == 1 and isinstance(ls.terms[0], AdvectionTerm)):
+        raise ValueError("SemiImplicitI2OE requires exactly one AdvectionTerm")
+    if not all(n >= 3 for n in ls.mesh_.n):
+        raise ValueError("SemiImplicitI2OE requires at least 3 grid nodes along each dimension")
+    for sides in ls.bcs:
+        for bc in sides:
+            if not (isinstance(bc, PeriodicBC) or (isinstance(bc, ExtrapolationBC) and bc.degree <= 1)):
+                raise ValueError(f"boundary condition {_bc_jl(bc)} is not supported by SemiImplicitI2OE")
+    if ls.comm is not None and ls.world > 1:
+        raise ValueError("SemiImplicitI2OE runs on a single device: a slab decomposition (comm) is not supported")
+
+
+def _integrate_i2oe(ls, tc, tf, dt, prehook, posthook):
+    """_integrate!(ls, ϕ::MeshField, ::SemiImplicitI2OE, ...) — src/timestepping.jl:207-233: one device solve per step
+    (lsm_advance_i2oe); no update_band!.  The iterations and the relative residual of the last step are kept in
+    ls.i2oe_last, the iterations of all steps in ls.i2oe_iters."""
+    _validate_i2oe(ls)
+    integ = ls.integrator
+    ls.i2oe_iters = 0
+    while tc <= tf - _eps(tc):
+        if prehook is not None:
+            prehook(ls)
+        ls._update_terms(ls.state, tc)
+        step = _jl_min(dt, integ.cfl * ls.compute_cfl(tc), tf - tc)
+        ls.i2oe_last = ls.backend.advance_i2oe(_terms_c(ls.terms), ls.state.buf, tc, step, integ.rtol, integ.max_iters)
+        ls.i2oe_iters += ls.i2oe_last[0]
+        ls.state.ghosts_dirty = True
+        tc += step
+        ls.t = tc
+        ls._range_checked_at += 1
+        if ls._range_checked_at % 64 == 0:
+            ls._check_range()
         if posthook is not None:
             posthook(ls)
     ls.t = tf

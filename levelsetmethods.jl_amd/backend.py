@@ -144,6 +144,13 @@ class HipBackend:
             code = self.lib.lsm_advance_rk3(self.h, terms_c, nterms, self.ptr(phi), self.ptr(b1), self.ptr(b2), tc, dt, cb, None)
         L.check(self.h, code, f"lsm_advance_{which}")
 
+    def advance_i2oe(self, term_c, phi, tc, dt, rtol, max_iters):
+        """One SemiImplicitI2OE step (lsm_advance_i2oe); returns (iterations, ‖r‖₂/‖rhs‖₂)."""
+        it, rel = C.c_int(0), C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_advance_i2oe(self.h, term_c, self.ptr(phi), tc, dt, rtol, max_iters, C.byref(it), C.byref(rel)),
+                "lsm_advance_i2oe")
+        return it.value, rel.value
+
     def check_range(self, t):
         """(ok, max|ϕ|): is the field inside the domain of the handle's arithmetic mode (include/lsm.h, LSM_FAST_MAX_ABS)?"""
         ok, m = C.c_int(), C.c_double()

@@ -191,6 +191,7 @@ int lsm_create(const LsmGrid* grid, const LsmBc bc[LSM_MAX_DIM][2], const LsmSla
     h->status_ticket = 0;
     h->mredirect = false;
     h->reinit_ws = nullptr;
+    h->i2oe_ws = nullptr;
     h->d_pf_flag = nullptr;
     memset(&h->band_cfl, 0, sizeof(h->band_cfl));
     h->cfl_prefetched = false;
@@ -314,6 +315,7 @@ void lsm_destroy(LsmHandle* h) {
     (void)hipFree(h->d_result);
     if (h->d_pf_flag) (void)hipFree(h->d_pf_flag);
     reinit_workspace_free(h->reinit_ws);
+    i2oe_workspace_free(h->i2oe_ws);
     (void)hipHostFree(h->h_result);
     if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;

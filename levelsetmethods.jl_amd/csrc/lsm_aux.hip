@@ -1019,3 +1019,7 @@ void launch_eikonal_sign(int /*ndim*/, const int n[3], long long s1, long long s
 }
 
 }  // namespace lsm
+
+// SemiImplicitI2OE (lsm_advance_i2oe) is compiled in this translation unit.  make does not track the include: touch this
+// file after editing lsm_i2oe.hip.
+#include "lsm_i2oe.hip"

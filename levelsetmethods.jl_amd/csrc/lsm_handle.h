@@ -6,6 +6,7 @@
 
 #include "lsm_internal.h"
 
+namespace lsm { struct I2oeWorkspace; }   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
 struct LsmComm;   // lsm_comm.hip: slab communicator (RCCL or in-process), NULL on a single-device handle
 
 struct LsmHandle {
@@ -87,6 +88,7 @@ struct LsmHandle {
     std::vector<hipEvent_t> ev_start, ev_stop;
     size_t ev_used;
     lsm::ReinitWorkspace* reinit_ws;   // reinitialize!'s device buffers, kept between calls (grow-only)
+    lsm::I2oeWorkspace* i2oe_ws;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
     LsmComm* comm;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
     bool yredirect;                // ... and those of dimension 2 (3-D)
     bool mredirect;                // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
@@ -104,3 +106,4 @@ int lsm_fail(LsmHandle* h, int code, const std::string& msg);
 bool lsm_comm_overlap(const LsmHandle* h);
 int lsm_host_sync(LsmHandle* h, const char* what);   // host wait for h->stream that an RCCL peer's silence cannot hang (lsm_comm.hip)
 int lsm_comm_band_overlap(const LsmHandle* h);   // overlap depth declared by lsm_band_overlap_config (0 = none)
+namespace lsm { void i2oe_workspace_free(I2oeWorkspace* w); }   // lsm_i2oe.hip
