@@ -1338,17 +1338,30 @@ __global__ void __launch_bounds__(128) interp_points_kernel(ReinitArgs a, long l
     }
 }
 static bool interp_matrix(int order, int ndim, double M[36], int* nv_out, double* lambda);
-int interp_run(int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], int order,
-               const void* phi, int f32, long long npts, const double* pts, double* val, double* grad, double* hess, hipStream_t stream, const char** err) {
-    ReinitArgs a;
+// the arguments of every kernel here: reinitialize! and NewtonSDF, or InterpolatedField (`interp`: its messages, no solver settings)
+static int setup_args(ReinitArgs& a, int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3],
+                      const double h[3], int order, int upsample, int maxiters, double xtol, double ftol, const void* phi, int f32,
+                      const unsigned char* mask, const char** err, bool interp = false) {
     a.ndim = ndim;
     for (int d = 0; d < 3; ++d) { a.n[d] = n[d]; a.goff[d] = goff[d]; a.lc[d] = lc[d]; a.h[d] = h[d]; }
     a.s1 = s1; a.s2 = s2; a.origin = origin;
-    a.order = order; a.upsample = 1; a.maxiters = 1; a.xtol = a.ftol = 0.0;
-    a.phi = phi; a.f32 = f32; a.mask = nullptr;
-    if (!interp_matrix(order, ndim, a.M, &a.nv, &a.lambda)) { *err = "InterpolatedField: order must be in 1..5"; return 1; }
+    a.order = order; a.upsample = upsample; a.maxiters = maxiters; a.xtol = xtol; a.ftol = ftol;
+    a.phi = phi; a.f32 = f32; a.mask = mask;
+    if (!interp_matrix(order, ndim, a.M, &a.nv, &a.lambda)) {
+        *err = interp ? "InterpolatedField: order must be in 1..5" : "reinitialize: order must be in 1..5";
+        return 1;
+    }
     a.off = -((a.nv - 1) - 1) / 2;
-    if (a.nv + a.off - 1 > LSM_GHOST + 1 || -a.off > LSM_GHOST) { *err = "InterpolatedField: stencil exceeds the ghost layers"; return 1; }
+    if (a.nv + a.off - 1 > LSM_GHOST + 1 || -a.off > LSM_GHOST) {
+        *err = interp ? "InterpolatedField: stencil exceeds the ghost layers" : "reinitialize: stencil exceeds the ghost layers";
+        return 1;
+    }
+    return 0;
+}
+int interp_run(int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], int order,
+               const void* phi, int f32, long long npts, const double* pts, double* val, double* grad, double* hess, hipStream_t stream, const char** err) {
+    ReinitArgs a;
+    if (int r = setup_args(a, ndim, n, goff, s1, s2, origin, lc, h, order, 1, 1, 0.0, 0.0, phi, f32, nullptr, err, true)) return r;
     for (int d = 0; d < ndim; ++d)
         if (n[d] < 2) { *err = "InterpolatedField: at least two nodes per dimension"; return 1; }
     if (npts <= 0) return 0;
@@ -1359,6 +1372,30 @@ int interp_run(int ndim, const int n[3], const int goff[3], long long s1, long l
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
+// a device buffer that only grows: re-allocated when a call needs more than it holds (the set of a NewtonSDF object is built once;
+// the workspace of reinitialize! lives on the handle and stops allocating after the first calls).  Frees itself.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;            // bytes
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    hipError_t alloc(size_t bytes) {
+        release();
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    hipError_t grow(size_t bytes) { return p && cap >= bytes ? hipSuccess : alloc(bytes + bytes / 4 + 256); }   // headroom: the band's size drifts
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
 // ---- the interface samples of a field and the structures that index them (candidate cells, samples per cell, occupancy
 // bits and blocks): built once per reinitialize! call, or kept in a NewtonSDF object for point queries
 struct SampleSet {
@@ -1368,59 +1405,31 @@ struct SampleSet {
     unsigned cap_nodes_e = 0, cap_cand_e = 0;   // entries the node list / the per-candidate buffers were launched with (launch_samples)
     DevCount dn{nullptr, 0, 0}, dc{nullptr, 0, 0};   // the two lengths as the kernels of this round see them
     long long nwork = 0;       // active nodes (band) or all nodes
-    int* cand_id = nullptr;
-    long long *cand_cell = nullptr, *maybe = nullptr, *node_list = nullptr;
-    unsigned* counters = nullptr;      // [0] maybe cells, [1] nfail, [2] nfar, [3] band nodes, [4] start points, [5] candidate cells, [6] retried nodes
-    double* pts = nullptr;
-    unsigned char *valid = nullptr, *cnt = nullptr, *blk = nullptr;
-    unsigned long long* sup = nullptr;      // occupied blocks per super-block (reinit_sup_kernel)
-    unsigned long long* bits = nullptr;
-    unsigned long long* starts = nullptr;   // start points to project: candidate id | slot << 32
-    // bytes allocated behind each pointer (grow(): a buffer is re-allocated only when a call needs more — the set of a NewtonSDF
-    // object is built once; the workspace of reinitialize! lives on the handle and stops allocating after the first calls)
-    size_t cap_cand_id = 0, cap_cand_cell = 0, cap_maybe = 0, cap_node_list = 0, cap_counters = 0, cap_pts = 0, cap_valid = 0, cap_cnt = 0, cap_blk = 0,
-           cap_bits = 0, cap_starts = 0, cap_sup = 0;
-    // workspace only: cand_id == -1, bits == 0 and blk == 0 everywhere for a grid of `clean_cells` cells — the state every band call
-    // starts from, and restores by un-marking its own candidate cells (reinit_unmark_kernel) instead of clearing arrays of the size of the grid
+    DevBuf<int> cand_id;
+    DevBuf<long long> cand_cell, maybe, node_list;
+    // [0] maybe cells, [1] nfail, [2] nfar, [3] band nodes, [4] start points, [5] candidate cells, [6] retried nodes; [8..9] NewtonSDF's
+    // sample count (64 bits)
+    DevBuf<unsigned> counters;
+    DevBuf<double> pts;
+    DevBuf<unsigned char> valid, cnt, blk;
+    DevBuf<unsigned long long> sup;      // occupied blocks per super-block (reinit_sup_kernel)
+    DevBuf<unsigned long long> bits;
+    DevBuf<unsigned long long> starts;   // start points to project: candidate id | slot << 32
+    // cand_id == -1, blk == 0 and bits == 0 everywhere for a grid of `clean_cells` cells (-1: not known).  Every band round starts from
+    // that state (reset_cells clears the three arrays when it is not known); a workspace's round ends in it again by un-marking its own
+    // candidate cells (reinit_unmark_kernel), and reinit_run records it then — the next round skips the clearing of grid-sized arrays.
     long long clean_cells = -1;
-    void release() {
-        (void)hipFree(cand_id); (void)hipFree(cand_cell); (void)hipFree(maybe); (void)hipFree(node_list); (void)hipFree(counters);
-        (void)hipFree(pts); (void)hipFree(valid); (void)hipFree(cnt); (void)hipFree(blk); (void)hipFree(sup); (void)hipFree(bits); (void)hipFree(starts);
-        cand_id = nullptr; cand_cell = maybe = node_list = nullptr; counters = nullptr; pts = nullptr; valid = cnt = blk = nullptr; sup = nullptr; bits = nullptr; starts = nullptr;
-        cap_cand_id = cap_cand_cell = cap_maybe = cap_node_list = cap_counters = cap_pts = cap_valid = cap_cnt = cap_blk = cap_bits = cap_starts = cap_sup = 0;
-        cap_nodes_e = cap_cand_e = 0;
-        clean_cells = -1;
-    }
 };
-template <class T>
-static hipError_t grow(T*& p, size_t& cap, size_t bytes, bool* fresh = nullptr) {
-    if (fresh) *fresh = false;
-    if (p && cap >= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;          // headroom: the band's size drifts from call to call
-    const hipError_t e = hipMalloc((void**)&p, want);
-    if (e == hipSuccess) { cap = want; if (fresh) *fresh = true; }
-    return e;
-}
 // the device buffers of reinitialize! kept between calls on one handle (LsmHandle::reinit_ws): eleven hipMalloc / hipFree pairs per
 // call were more than a third of a band call's 3.8 ms at 256³
 struct ReinitWorkspace {
     SampleSet ss;
-    long long* seeds = nullptr;
-    unsigned* retry = nullptr;         // nodes whose solve from the nearest sample failed (second pass of the closest-point kernel)
-    long long* foot = nullptr;         // cell of the first-order closest-point estimate per node
-    size_t cap_seeds = 0, cap_retry = 0, cap_foot = 0;
+    DevBuf<long long> seeds;
+    DevBuf<unsigned> retry;            // nodes whose solve from the nearest sample failed (second pass of the closest-point kernel)
+    DevBuf<long long> foot;            // cell of the first-order closest-point estimate per node
     unsigned last_nodes = 0, last_cand = 0;      // band nodes and candidate cells of the previous call: what the next one is launched for
 };
-void reinit_workspace_free(ReinitWorkspace* w) {
-    if (!w) return;
-    w->ss.release();
-    (void)hipFree(w->seeds);
-    (void)hipFree(w->retry);
-    (void)hipFree(w->foot);
-    delete w;
-}
+void reinit_workspace_free(ReinitWorkspace* w) { delete w; }
 // the second level of the far-field search: per super-block of 8^N blocks the mask of its occupied blocks, 8 words each (bit
 // b0 + 8·(b1 + 8·b2) of them), written whole from the block bytes
 __global__ void __launch_bounds__(256) reinit_sup_kernel(ReinitArgs a, const unsigned char* blk, unsigned long long* sup, long long nwords) {
@@ -1451,27 +1460,30 @@ __global__ void __launch_bounds__(256) reinit_unmark_kernel(ReinitArgs a, const 
     }
 }
 
-static int setup_args(ReinitArgs& a, int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3],
-                      const double h[3], int order, int upsample, int maxiters, double xtol, double ftol, const void* phi, int f32,
-                      const unsigned char* mask, const char** err) {
-    a.ndim = ndim;
-    for (int d = 0; d < 3; ++d) { a.n[d] = n[d]; a.goff[d] = goff[d]; a.lc[d] = lc[d]; a.h[d] = h[d]; }
-    a.s1 = s1; a.s2 = s2; a.origin = origin;
-    a.order = order; a.upsample = upsample; a.maxiters = maxiters; a.xtol = xtol; a.ftol = ftol;
-    a.phi = phi; a.f32 = f32; a.mask = mask;
-    if (!interp_matrix(order, ndim, a.M, &a.nv, &a.lambda)) { *err = "reinitialize: order must be in 1..5"; return 1; }
-    a.off = -((a.nv - 1) - 1) / 2;
-    if (a.nv + a.off - 1 > LSM_GHOST + 1 || -a.off > LSM_GHOST) { *err = "reinitialize: stencil exceeds the ghost layers"; return 1; }
-    return 0;
+// the clean state of SampleSet::clean_cells, before the cells kernel: kept when a workspace holds it (`keep_clean`), else cleared here —
+// cand_id of a band (a dense field's cells kernel writes every cell's), blk and bits of every field
+static hipError_t reset_cells(SampleSet& ss, long long nc, size_t nblk, size_t nwords, bool keep_clean, hipStream_t stream) {
+    const size_t id_bytes = sizeof(int) * (size_t)nc, bits_bytes = sizeof(unsigned long long) * nwords;
+    const bool clean = keep_clean && ss.a.mask && ss.clean_cells == nc && ss.cand_id.cap >= id_bytes && ss.blk.cap >= nblk && ss.bits.cap >= bits_bytes;
+    ss.clean_cells = -1;                       // until the caller has restored the state at the end of the round
+    hipError_t e = ss.cand_id.grow(id_bytes);
+    if (e == hipSuccess) e = ss.blk.grow(nblk);
+    if (e == hipSuccess) e = ss.bits.grow(bits_bytes);
+    if (clean || e != hipSuccess) return e;
+    if (ss.a.mask) e = hipMemsetAsync(ss.cand_id, 0xFF, id_bytes, stream);      // -1 everywhere; the cells kernel visits the band only
+    if (e == hipSuccess) e = hipMemsetAsync(ss.blk, 0, nblk, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ss.bits, 0, bits_bytes, stream);
+    return e;
 }
 
-#define RE_HIP(call) do { if ((call) != hipSuccess) { *err = #call; ss.release(); return 2; } } while (0)
+#define RE_HIP(call) do { if ((call) != hipSuccess) { *err = #call; return 2; } } while (0)
 // Candidate cells -> interface samples -> per-cell counts, occupancy bits, blocks and super-blocks (steps 1 and 2 above) — launched
 // without waiting for anything: the number of band nodes and of candidate cells stay on the device (DevCount), the buffers are sized
 // for `want_nodes` / `want_cand` entries (what the previous call needed, with headroom) and the caller checks afterwards whether
 // both fitted (samples_fit) — if not it launches again with what it has learnt.  `count_only`: stop behind the candidate-cell test
 // (a first call: nothing is known yet, the rest of the round would work on a handful of cells).  ss.a is set.
 // `keep_clean`: ss is a workspace whose cand_id / bits / blk are restored by the caller after the call (band fields only).
+// On failure the caller releases ss.
 static int launch_samples(SampleSet& ss, long long total, hipStream_t stream, const char** err, bool keep_clean, unsigned want_nodes, unsigned want_cand,
                           bool count_only = false) {
     const ReinitArgs& a = ss.a;
@@ -1482,51 +1494,45 @@ static int launch_samples(SampleSet& ss, long long total, hipStream_t stream, co
     ss.S = 1;
     for (int d = 0; d < ndim; ++d) ss.S *= a.upsample + 1;
     const int S = ss.S;
-    bool fresh_id = false, fresh_blk = false, fresh_bits = false;
-    RE_HIP(grow(ss.cand_id, ss.cap_cand_id, sizeof(int) * (size_t)nc, &fresh_id));
-    RE_HIP(grow(ss.counters, ss.cap_counters, 8 * sizeof(unsigned)));
+    RE_HIP(ss.counters.grow(10 * sizeof(unsigned)));
     RE_HIP(hipMemsetAsync(ss.counters, 0, 8 * sizeof(unsigned), stream));
     size_t nblk = 1, nsupw = 8;                          // block bytes; words of `sup` (8 per super-block of 8^N blocks)
     for (int d = 0; d < ndim; ++d) { nblk *= (size_t)((n[d] - 1 + RB - 1) / RB); nsupw *= (size_t)(((n[d] - 1 + RB - 1) / RB + 7) / 8); }
     size_t nwords = (size_t)((n[0] - 1 + 63) / 64);
     for (int d = 1; d < ndim; ++d) nwords *= (size_t)(n[d] - 1);
-    RE_HIP(grow(ss.blk, ss.cap_blk, nblk, &fresh_blk));
-    RE_HIP(grow(ss.sup, ss.cap_sup, sizeof(unsigned long long) * nsupw));
-    RE_HIP(grow(ss.bits, ss.cap_bits, sizeof(unsigned long long) * nwords, &fresh_bits));
-    const bool clean = keep_clean && a.mask && ss.clean_cells == nc && !fresh_id && !fresh_blk && !fresh_bits;
-    ss.clean_cells = -1;                       // until the caller has restored the state at the end of the call
+    RE_HIP(ss.sup.grow(sizeof(unsigned long long) * nsupw));
     // band fields: the compact list of the active nodes first — candidate cells, the distance computation and the
     // commit all run over it (the band is ~1 % of a 3-D grid)
     const long long nodes = (long long)n[0] * n[1] * n[2];
-    if (nodes > 0xffffffffll) { *err = "reinitialize: more than 2^32 nodes"; ss.release(); return 1; }
+    if (nodes > 0xffffffffll) { *err = "reinitialize: more than 2^32 nodes"; return 1; }
     if (a.mask) {
-        RE_HIP(grow(ss.node_list, ss.cap_node_list, sizeof(long long) * (size_t)(want_nodes ? want_nodes : 1)));
-        ss.cap_nodes_e = (unsigned)std::min<size_t>(ss.cap_node_list / sizeof(long long), 0xffffffffu);
+        RE_HIP(ss.node_list.grow(sizeof(long long) * (size_t)(want_nodes ? want_nodes : 1)));
+        ss.cap_nodes_e = (unsigned)std::min<size_t>(ss.node_list.cap / sizeof(long long), 0xffffffffu);
         const long long nvec = (total + 15) / 16;
         const unsigned gl = (unsigned)((nvec + 255) / 256 > 16384 ? 16384 : (nvec + 255) / 256);
         hipLaunchKernelGGL(reinit_band_nodes_kernel, dim3(gl), dim3(256), 0, stream, a, total, ss.node_list, (long long)ss.cap_nodes_e, ss.counters + 3);
-        if (!clean) RE_HIP(hipMemsetAsync(ss.cand_id, 0xFF, sizeof(int) * (size_t)nc, stream));     // -1 everywhere; the cells kernel visits the band only
         ss.dn = DevCount{ss.counters + 3, ss.cap_nodes_e, 0};
     } else {
         ss.cap_nodes_e = (unsigned)nodes;
         ss.dn = DevCount{nullptr, 0, nodes};
     }
+    RE_HIP(reset_cells(ss, nc, nblk, nwords, keep_clean, stream));
     // the cells looked at: those whose lowest corner is a band node, or all of them
     const long long ncell_work = a.mask ? (long long)ss.cap_nodes_e : nc, ncell_grid = a.mask ? (long long)(want_nodes ? want_nodes : 1) : nc;
     const unsigned gb = (unsigned)((ncell_grid + 255) / 256 > 65535 ? 65535 : (ncell_grid + 255) / 256);
-    RE_HIP(grow(ss.maybe, ss.cap_maybe, sizeof(long long) * (size_t)(ncell_work ? ncell_work : 1)));
+    RE_HIP(ss.maybe.grow(sizeof(long long) * (size_t)(ncell_work ? ncell_work : 1)));
     hipLaunchKernelGGL(reinit_cells_kernel, dim3(gb), dim3(256), 0, stream, a, ss.cand_id, ss.maybe, ss.counters, ss.node_list, ss.dn);
     // samples: S slots per candidate cell, for at most cap_cand_e of them
     const size_t wantc = want_cand ? want_cand : 1;
-    RE_HIP(grow(ss.pts, ss.cap_pts, sizeof(double) * 3 * wantc * S));
-    RE_HIP(grow(ss.valid, ss.cap_valid, wantc * S));
-    RE_HIP(grow(ss.cnt, ss.cap_cnt, wantc));
-    RE_HIP(grow(ss.starts, ss.cap_starts, sizeof(unsigned long long) * wantc * S));
-    const size_t capc = std::min(std::min(ss.cap_pts / (sizeof(double) * 3 * S), ss.cap_valid / S), std::min(ss.cap_cnt, ss.cap_starts / (sizeof(unsigned long long) * S)));
+    RE_HIP(ss.pts.grow(sizeof(double) * 3 * wantc * S));
+    RE_HIP(ss.valid.grow(wantc * S));
+    RE_HIP(ss.cnt.grow(wantc));
+    RE_HIP(ss.starts.grow(sizeof(unsigned long long) * wantc * S));
+    const size_t capc = std::min(std::min(ss.pts.cap / (sizeof(double) * 3 * S), ss.valid.cap / S), std::min(ss.cnt.cap, ss.starts.cap / (sizeof(unsigned long long) * S)));
     ss.cap_cand_e = want_cand ? (unsigned)std::min<size_t>(capc, 0xffffffffu) : 0u;
     ss.dc = DevCount{ss.counters + 5, ss.cap_cand_e, 0};
     // the list of candidate cells (as long as the "maybe" list could be)
-    RE_HIP(grow(ss.cand_cell, ss.cap_cand_cell, sizeof(long long) * (size_t)(ncell_work ? ncell_work : 1)));
+    RE_HIP(ss.cand_cell.grow(sizeof(long long) * (size_t)(ncell_work ? ncell_work : 1)));
     {
         const dim3 g2((unsigned)((ncell_grid / 2 + 256) / 256 > 65535 ? 65535 : (ncell_grid / 2 + 256) / 256)), b2(256);
 #define LSM_CELLS2(NV_, NC_, ND_) hipLaunchKernelGGL((reinit_cells2_kernel<NV_, NC_, ND_>), g2, b2, 0, stream, a, ss.maybe, ss.counters, ss.cand_id, ss.cand_cell, ss.counters + 5, ss.cap_cand_e)
@@ -1542,10 +1548,6 @@ static int launch_samples(SampleSet& ss, long long total, hipStream_t stream, co
     }
     if (count_only) return 0;          // the caller wants the two counts first (nothing is known about this field yet)
     if (ss.cap_cand_e) RE_HIP(hipMemsetAsync(ss.valid, 0, (size_t)ss.cap_cand_e * S, stream));
-    if (!clean) {
-        RE_HIP(hipMemsetAsync(ss.blk, 0, nblk, stream));
-        RE_HIP(hipMemsetAsync(ss.bits, 0, sizeof(unsigned long long) * nwords, stream));
-    }
     if (ss.cap_cand_e) {
         const long long work = (long long)want_cand * S;
         const unsigned gw = (unsigned)((work + 255) / 256 > 262144 ? 262144 : (work + 255) / 256);
@@ -1580,17 +1582,13 @@ static unsigned headroom(unsigned n) { return n ? (unsigned)std::min<unsigned lo
 // returns 0 on success; out_counts = {samples kept, nodes whose solve did not converge, nodes with no sample at all}
 int reinit_run(int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, long long total, const double lc[3],
                const double h[3], int order, int upsample, int maxiters, double xtol, double ftol, void* phi, int f32, const unsigned char* mask,
-               void* out_field, hipStream_t stream, long long out_counts[3], const char** err, ReinitWorkspace** wsp) {
-    // the buffers live in the caller's workspace (the handle's) when there is one: no allocation after the first calls
-    ReinitWorkspace local;
-    if (wsp && !*wsp) *wsp = new ReinitWorkspace();
-    ReinitWorkspace& W = wsp ? **wsp : local;
+               void* out_field, hipStream_t stream, long long out_counts[3], const char** err, ReinitWorkspace** workspace) {
+    if (!*workspace) *workspace = new ReinitWorkspace();      // the handle's, created by its first call: no allocation after the first calls
+    ReinitWorkspace& W = **workspace;
     SampleSet& ss = W.ss;
-    auto done = [&](int rc) {
-        if (!wsp) { ss.release(); (void)hipFree(W.seeds); (void)hipFree(W.retry); (void)hipFree(W.foot); W.seeds = nullptr; W.retry = nullptr; W.foot = nullptr; }
-        return rc;
-    };
-    if (int r = setup_args(ss.a, ndim, n, goff, s1, s2, origin, lc, h, order, upsample, maxiters, xtol, ftol, phi, f32, mask, err)) return done(r);
+    if (int r = setup_args(ss.a, ndim, n, goff, s1, s2, origin, lc, h, order, upsample, maxiters, xtol, ftol, phi, f32, mask, err)) return r;
+    // the one exit of a failed call: every buffer goes, and the next call starts as a first call
+    auto fail = [&](int rc) { W = ReinitWorkspace(); return rc; };
     const ReinitArgs& a = ss.a;
     long long nc = 1;
     for (int d = 0; d < ndim; ++d) nc *= n[d] - 1;
@@ -1601,15 +1599,15 @@ int reinit_run(int ndim, const int n[3], const int goff[3], long long s1, long l
     for (int round = 0;; ++round) {
         // nothing known about the band or about its candidate cells (the first call on the handle): a round that only counts them
         const bool count_only = (a.mask && W.last_nodes == 0) || W.last_cand == 0;
-        if (int r = launch_samples(ss, total, stream, err, wsp != nullptr, std::max(headroom(W.last_nodes), ss.cap_nodes_e), std::max(headroom(W.last_cand), ss.cap_cand_e),
+        if (int r = launch_samples(ss, total, stream, err, true, std::max(headroom(W.last_nodes), ss.cap_nodes_e), std::max(headroom(W.last_cand), ss.cap_cand_e),
                                    count_only))
-            return r;     // (launch_samples released ss)
+            return fail(r);
         const int S = ss.S;
         const long long nwork = ss.cap_nodes_e;          // what the per-node buffers and grids are sized for
         if (nwork && !count_only) {
-            if (grow(W.seeds, W.cap_seeds, sizeof(long long) * NSEED * (size_t)nwork) != hipSuccess) { *err = "hipMalloc(seeds)"; ss.release(); return done(2); }
-            if (grow(W.retry, W.cap_retry, sizeof(unsigned) * (size_t)nwork) != hipSuccess) { *err = "hipMalloc(retry)"; ss.release(); return done(2); }
-            if (grow(W.foot, W.cap_foot, sizeof(long long) * (size_t)nwork) != hipSuccess) { *err = "hipMalloc(foot)"; ss.release(); return done(2); }
+            if (W.seeds.grow(sizeof(long long) * NSEED * (size_t)nwork) != hipSuccess) { *err = "hipMalloc(seeds)"; return fail(2); }
+            if (W.retry.grow(sizeof(unsigned) * (size_t)nwork) != hipSuccess) { *err = "hipMalloc(retry)"; return fail(2); }
+            if (W.foot.grow(sizeof(long long) * (size_t)nwork) != hipSuccess) { *err = "hipMalloc(foot)"; return fail(2); }
             long long* seeds = W.seeds;
             const long long ngrid = a.mask ? (long long)std::max(headroom(W.last_nodes), 1u) : nwork;      // nodes expected
             const unsigned gsr = (unsigned)((ngrid + 255) / 256 > 262144 ? 262144 : (ngrid + 255) / 256);
@@ -1645,17 +1643,16 @@ int reinit_run(int ndim, const int n[3], const int goff[3], long long s1, long l
                                out_field, phi, ss.node_list, ss.dn, ss.dc);
         }
         hipError_t e = hipMemcpyAsync(cn, ss.counters, sizeof(cn), hipMemcpyDeviceToHost, stream);
-        // a workspace serving a band goes back to its clean state by un-marking this round's candidate cells (behind everything that read
-        // them; cells beyond the buffers' capacity were never marked)
-        const bool restore = wsp && a.mask && e == hipSuccess;
-        if (restore) {
+        // a band round (it started clean: reset_cells) goes back to the clean state by un-marking its candidate cells (behind everything
+        // that read them; cells beyond the buffers' capacity were never marked)
+        if (a.mask && e == hipSuccess) {
             const unsigned gu = (std::max(headroom(W.last_cand), 256u) + 255) / 256;
             hipLaunchKernelGGL(reinit_unmark_kernel, dim3(gu), dim3(256), 0, stream, a, ss.cand_cell, ss.dc, ss.cand_id, ss.blk, ss.bits);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) { *err = "reinitialize: device error"; if (wsp) ss.release(); return done(2); }
-        if (restore) ss.clean_cells = nc;
+        if (e != hipSuccess) { *err = "reinitialize: device error"; return fail(2); }
+        if (a.mask) ss.clean_cells = nc;
         const bool fit = samples_fit(ss, cn);
         const bool nodes_fit = !a.mask || cn[3] <= ss.cap_nodes_e;
         W.last_nodes = a.mask ? cn[3] : 0u;
@@ -1665,10 +1662,10 @@ int reinit_run(int ndim, const int n[3], const int goff[3], long long s1, long l
             cn[1] = 0; cn[2] = (unsigned)ss.nwork;
             break;
         }
-        if (round >= 4) { *err = "reinitialize: the lists did not fit their buffers after five rounds"; if (wsp) ss.release(); return done(2); }
+        if (round >= 4) { *err = "reinitialize: the lists did not fit their buffers after five rounds"; return fail(2); }
     }
     out_counts[0] = ss.ncand; out_counts[1] = cn[1]; out_counts[2] = cn[2];
-    return done(0);
+    return 0;
 }
 #undef RE_HIP
 
@@ -1678,9 +1675,10 @@ int reinit_run(int ndim, const int n[3], const int goff[3], long long s1, long l
 // the seed cell's patch, further near samples as fall-back seeds -> sign(dot(x - cp, ∇p(cp))) · ‖x - cp‖.
 struct SdfObject {
     SampleSet ss;
-    void* phi_copy = nullptr;
-    unsigned char* mask_copy = nullptr;
+    DevBuf<void> phi_copy;
+    DevBuf<unsigned char> mask_copy;
     hipStream_t stream = nullptr;
+    unsigned long long* nsamples() const { return (unsigned long long*)(ss.counters + 8); }    // a slot of its own (sdf_samples_kernel)
 };
 
 // One thread per query point.  The nearest sample: Chebyshev shells of cells around the (clamped) cell of x, occupied
@@ -1858,39 +1856,36 @@ int sdf_build(int ndim, const int n[3], const int goff[3], long long s1, long lo
               const unsigned char* mask, hipStream_t stream, SdfObject** out, long long* nsamples, const char** err) {
     SdfObject* o = new SdfObject();
     o->stream = stream;
+    auto fail = [&](int rc, const char* what) { if (what) *err = what; delete o; return rc; };
     const size_t bytes = (size_t)total * (f32 ? 4 : 8);
-    auto bail = [&](const char* what) { *err = what; (void)hipFree(o->phi_copy); (void)hipFree(o->mask_copy); o->ss.release(); delete o; return 2; };
-    if (hipMalloc(&o->phi_copy, bytes) != hipSuccess) return bail("hipMalloc(phi copy)");
-    if (hipMemcpyAsync(o->phi_copy, phi, bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return bail("copy of phi");
+    if (o->phi_copy.alloc(bytes) != hipSuccess) return fail(2, "hipMalloc(phi copy)");
+    if (hipMemcpyAsync(o->phi_copy, phi, bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail(2, "copy of phi");
     if (mask) {
-        if (hipMalloc((void**)&o->mask_copy, (size_t)total) != hipSuccess) return bail("hipMalloc(mask copy)");
-        if (hipMemcpyAsync(o->mask_copy, mask, (size_t)total, hipMemcpyDeviceToDevice, stream) != hipSuccess) return bail("copy of mask");
+        if (o->mask_copy.alloc((size_t)total) != hipSuccess) return fail(2, "hipMalloc(mask copy)");
+        if (hipMemcpyAsync(o->mask_copy, mask, (size_t)total, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail(2, "copy of mask");
     }
-    if (int r = setup_args(o->ss.a, ndim, n, goff, s1, s2, origin, lc, h, order, upsample, maxiters, xtol, ftol, o->phi_copy, f32, o->mask_copy, err)) {
-        (void)hipFree(o->phi_copy); (void)hipFree(o->mask_copy); delete o; return r;
-    }
+    if (int r = setup_args(o->ss.a, ndim, n, goff, s1, s2, origin, lc, h, order, upsample, maxiters, xtol, ftol, o->phi_copy, f32, o->mask_copy, err))
+        return fail(r, nullptr);
     // rounds of launch_samples until the node list and the candidate cells fit their buffers (a fresh object: two or three)
     unsigned want_nodes = 0, want_cand = 0;
     for (int round = 0;; ++round) {
-        if (int r = launch_samples(o->ss, total, stream, err, false, want_nodes, want_cand)) { (void)hipFree(o->phi_copy); (void)hipFree(o->mask_copy); delete o; return r; }
+        if (int r = launch_samples(o->ss, total, stream, err, false, want_nodes, want_cand)) return fail(r, nullptr);
         unsigned cn[8];
         if (hipMemcpyAsync(cn, o->ss.counters, sizeof(cn), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-            return bail("candidate counts");
+            return fail(2, "candidate counts");
         if (samples_fit(o->ss, cn)) break;
-        if (round >= 3) return bail("NewtonSDF: the lists did not fit their buffers after four rounds");
+        if (round >= 3) return fail(2, "NewtonSDF: the lists did not fit their buffers after four rounds");
         want_nodes = std::max(want_nodes, mask ? cn[3] : 0u);
         want_cand = std::max(want_cand, cn[5]);
     }
-    unsigned long long* cnt = nullptr;
     unsigned long long hc = 0;
-    if (hipMalloc((void**)&cnt, 8) != hipSuccess || hipMemsetAsync(cnt, 0, 8, stream) != hipSuccess) return bail("hipMalloc(count)");
+    if (hipMemsetAsync(o->nsamples(), 0, 8, stream) != hipSuccess) return fail(2, "sample count");
     if (o->ss.ncand)
         hipLaunchKernelGGL(sdf_samples_kernel, dim3((o->ss.ncand + 255) / 256), dim3(256), 0, stream, ndim, o->ss.ncand, o->ss.S, o->ss.pts, o->ss.cnt,
-                           (double*)nullptr, cnt);
-    hipError_t e = hipMemcpyAsync(&hc, cnt, 8, hipMemcpyDeviceToHost, stream);
+                           (double*)nullptr, o->nsamples());
+    hipError_t e = hipMemcpyAsync(&hc, o->nsamples(), 8, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(cnt);
-    if (e != hipSuccess) return bail("sample count");
+    if (e != hipSuccess) return fail(2, "sample count");
     *nsamples = (long long)hc;
     *out = o;
     return 0;
@@ -1912,22 +1907,13 @@ int sdf_eval(SdfObject* o, long long npts, const double* xs, double* dist, doubl
     return 0;
 }
 int sdf_samples(SdfObject* o, double* out, const char** err) {
-    unsigned long long* cnt = nullptr;
-    if (hipMalloc((void**)&cnt, 8) != hipSuccess || hipMemsetAsync(cnt, 0, 8, o->stream) != hipSuccess) { *err = "hipMalloc(count)"; return 2; }
+    if (hipMemsetAsync(o->nsamples(), 0, 8, o->stream) != hipSuccess) { *err = "NewtonSDF samples: device error"; return 2; }
     if (o->ss.ncand)
         hipLaunchKernelGGL(sdf_samples_kernel, dim3((o->ss.ncand + 255) / 256), dim3(256), 0, o->stream, o->ss.a.ndim, o->ss.ncand, o->ss.S, o->ss.pts,
-                           o->ss.cnt, out, cnt);
-    const hipError_t e = hipStreamSynchronize(o->stream);
-    (void)hipFree(cnt);
-    if (e != hipSuccess) { *err = "NewtonSDF samples: device error"; return 2; }
+                           o->ss.cnt, out, o->nsamples());
+    if (hipStreamSynchronize(o->stream) != hipSuccess) { *err = "NewtonSDF samples: device error"; return 2; }
     return 0;
 }
-void sdf_free(SdfObject* o) {
-    if (!o) return;
-    o->ss.release();
-    (void)hipFree(o->phi_copy);
-    (void)hipFree(o->mask_copy);
-    delete o;
-}
+void sdf_free(SdfObject* o) { delete o; }
 
 }  // namespace lsm

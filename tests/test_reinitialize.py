@@ -171,6 +171,39 @@ def test_a_band_that_outgrows_the_previous_calls_buffers(lsm, n):
 
 
 @pytest.mark.gpu
+def test_a_first_band_call_whose_workspace_lands_on_recycled_memory(lsm):
+    """The first band call on a handle clears the candidate ids, occupancy bits and blocks it starts from, whatever memory its
+    workspace was given: device memory is filled with 0xFF and freed before a new handle makes its first call, which must then
+    equal a second call on that handle and the call of a handle whose workspace was allocated before the poisoning.  (Whether the
+    allocator hands the poisoned pages to the library's hipMalloc is not guaranteed: the test makes it likely, not certain.)"""
+    import torch
+    n = (56, 56, 56)
+    grid = lsm.CartesianGrid((-1.0,) * 3, (1.0,) * 3, n)
+
+    def band():
+        return _device_field(lsm, _field(n, lambda X: np.sqrt(sum(x ** 2 for x in X)) * 1.3 - 0.6), grid, lsm.ExtrapolationBC(2), band_layers=3)
+
+    ref = band().current_state()
+    lsm.reinitialize_(ref)
+    want, m = ref.values().copy(), ref.active_mask()
+    poison = torch.full((256 << 20,), 0xFF, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    del poison
+    torch.cuda.empty_cache()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        st = band().current_state()
+        lsm.reinitialize_(st)
+        first = st.values().copy()
+        assert (st.active_mask() == m).all()
+        st.copy_(band().current_state())
+        lsm.reinitialize_(st)
+    assert (st.active_mask() == m).all()
+    assert np.abs(first[m] - want[m]).max() < 1e-12
+    assert np.abs(st.values()[m] - first[m]).max() < 1e-12
+
+
+@pytest.mark.gpu
 def test_gpu_reference_tests_dense(lsm):
     """test/test-reinitializer.jl:71-100 through the host API: 2-D 100² (error < 2 sqrt(eps), volume preserved) and
     3-D 31³ with upsample 4 (error < 5e-3)."""
