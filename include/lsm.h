@@ -372,6 +372,26 @@ int lsm_sdf_eval(LsmSdf* s, int64_t npoints, const void* points, void* distances
 int lsm_sdf_samples(LsmSdf* s, void* points_out);
 void lsm_sdf_destroy(LsmSdf* s);
 
+/* ---- quadrature(ϕ; interpolation_order, quadrature_order, surface) (src/LevelSetMethods.jl:103-126,
+ *      ext/ImplicitIntegrationExt.jl): nodes and weights integrating over {ψ < 0} (surface = 0) or {ψ = 0} (surface = 1) of
+ *      the piecewise interpolant ψ of degree interpolation_order (1..5), quadrature_order (1..20) Gauss–Legendre points per
+ *      direction, by R. Saye's algorithm on every cell's Bernstein patch.  phi: a dense field (its ghost
+ *      layers are refilled on entry; mask NULL) or a prepared band stage input with its mask (surface only; the band's
+ *      active cells).  Single device.  Cells are linear indices over the (n-1)^N cells, axis 0 fastest, ascending.
+ *      lsm_quad_create: counts[4] := {cut cells with nodes, nodes, full cells, boxes that reached the depth limit}.
+ *      lsm_quad_read copies into device buffers (each may be NULL): cells ncut int64; offsets ncut+1 int64 (the nodes of
+ *      cut cell i are offsets[i]..offsets[i+1]-1); coords nodes x ndim doubles (point-major); weights nodes doubles;
+ *      full_cells nfull int64 (volume: cells whose coefficients are all < 0; their rule is the tensor rule mapped to the
+ *      cell); rule_coords q^ndim x ndim and rule_weights q^ndim doubles, that rule on the unit cell.  lsm_quad_total: the
+ *      sum of every weight, full cells included.  Synchronous. */
+typedef struct LsmQuad LsmQuad;
+int lsm_quad_create(LsmHandle* h, void* phi, const void* mask, int interpolation_order, int quadrature_order, int surface,
+                    LsmQuad** out, int64_t* counts);
+int lsm_quad_read(LsmQuad* s, void* cells, void* offsets, void* coords, void* weights, void* full_cells, void* rule_coords,
+                  void* rule_weights);
+int lsm_quad_total(LsmQuad* s, double* total);
+void lsm_quad_destroy(LsmQuad* s);
+
 /* ---- NarrowBandMeshField (src/meshfield.jl:314-588) on the device.
  *      The band is a byte mask (1 = active node) over the same padded index space as the values
  *      (allocate LsmLayout.total bytes; ghost entries stay 0).  Values stay in the dense padded array.

@@ -472,6 +472,34 @@ function sample_points(sdf::ROCNewtonSDF, ndim::Integer)
     return out
 end
 
+# quadrature(ϕ; interpolation_order, quadrature_order, surface) (src/LevelSetMethods.jl:103-126, ext/ImplicitIntegrationExt.jl):
+# the device arrays of the result.  cells / full_cells are 0-based linear cell indices (axis 1 fastest); the nodes of cut cell i
+# (1-based) are the columns offsets[i]+1 : offsets[i+1] of coords (ndim x nodes).  rule_coords / rule_weights: the tensor rule of
+# a full cell on the unit cell.  INTEGRATION.md shows how an ImplicitIntegration-aware extension wraps them into the Dict.
+function quadrature_arrays(ϕ::ROCMeshField; interpolation_order, quadrature_order, surface = false, mask = nothing)
+    out, c = Ref{Ptr{Cvoid}}(), zeros(Int64, 4)
+    _check(ϕ.h.ptr, ccall((:lsm_quad_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), mask === nothing ? C_NULL : pointer(mask), interpolation_order, quadrature_order, surface, out, c), "lsm_quad_create")
+    q = out[]
+    try
+        ncut, nnodes, nfull, nfallback = c
+        N, m = ndims(ϕ), quadrature_order^ndims(ϕ)
+        cells, offsets, full = ROCVector{Int64}(undef, ncut), ROCVector{Int64}(undef, ncut + 1), ROCVector{Int64}(undef, nfull)
+        coords, weights = ROCMatrix{Float64}(undef, N, nnodes), ROCVector{Float64}(undef, nnodes)
+        rule_coords, rule_weights = ROCMatrix{Float64}(undef, N, m), ROCVector{Float64}(undef, m)
+        _check(ϕ.h.ptr, ccall((:lsm_quad_read, libhiplsm), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            q, pointer(cells), pointer(offsets), pointer(coords), pointer(weights), pointer(full), pointer(rule_coords), pointer(rule_weights)),
+            "lsm_quad_read")
+        total = Ref{Float64}()
+        _check(ϕ.h.ptr, ccall((:lsm_quad_total, libhiplsm), Cint, (Ptr{Cvoid}, Ref{Float64}), q, total), "lsm_quad_total")
+        nfallback > 0 && @warn "quadrature: $nfallback boxes reached the subdivision limit and got the low-order rule"
+        return (; cells, offsets, coords, weights, full_cells = full, rule_coords, rule_weights, total = total[], nfallback)
+    finally
+        ccall((:lsm_quad_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), q)
+    end
+end
+
 # reinitialize!(ϕ; ...) (src/reinitializer.jl:12-42)
 function LSM.reinitialize!(ϕ::ROCMeshField; order = 3, upsample = 2, maxiters = 20, xtol = nothing, ftol = nothing)
     xt, ft = something(xtol, sqrt(eps(Float64))), something(ftol, sqrt(eps(Float64)))

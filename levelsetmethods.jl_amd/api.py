@@ -1879,3 +1879,173 @@ def current_state(ls):
 
 def current_time(ls):
     return ls.current_time()
+
+
+# ----------------------------------------------------------------------------- quadrature (ext/ImplicitIntegrationExt.jl)
+
+_BAND_VOLUME_MSG = ("volume integrals (surface=false) are not supported on NarrowBandMeshField. "
+                    "Use a full MeshField for volume integrals, or pass surface=true for surface integrals.")
+
+
+class Quadrature:
+    """ImplicitIntegration.Quadrature: nodes `coords` (m, N) and `weights` (m,)."""
+
+    def __init__(self, coords, weights):
+        self.coords, self.weights = coords, weights
+
+    def __len__(self):
+        return len(self.weights)
+
+    def __repr__(self):
+        return f"Quadrature with {len(self)} nodes in ℝ{_superscript(self.coords.shape[1])}"
+
+
+class CellQuadratures:
+    """quadrature(…)'s result: a mapping from 0-based cell tuples to their `Quadrature`, as the reference's `Dict`.  Cut cells
+    in bulk: `cells` (ncut, N), `offsets` (ncut + 1; the nodes of cut cell i are offsets[i]:offsets[i+1]), `coords`, `weights`.
+    Full cells (volume: every coefficient < 0): `full_cells` (nfull, N) and `rule`, the tensor rule on the unit cell; their
+    nodes are made on request.  `total()`: the sum of every weight, on the device; `nfallback`: boxes that reached the
+    subdivision limit and got the low-order rule."""
+
+    def __init__(self, backend, mesh, handle, counts, q, surface):
+        self.mesh, self.quadrature_order, self.surface = mesh, int(q), bool(surface)
+        self._backend, self._h = backend, handle
+        self.ncut, self.nnodes, self.nfull, self.nfallback = counts
+        cells, offsets, coords, weights, full, rx, rw = backend.quad_read(handle, counts, q)
+        self._dims = np.array([k - 1 for k in mesh.n], dtype=np.int64)
+        self._cut_lin, self._full_lin = cells.cpu().numpy(), full.cpu().numpy()
+        self.offsets = offsets.cpu().numpy()
+        self.coords, self.weights = coords.cpu().numpy(), weights.cpu().numpy()
+        self.rule = Quadrature(rx.cpu().numpy(), rw.cpu().numpy())
+        self.cells, self.full_cells = self._unlin(self._cut_lin), self._unlin(self._full_lin)
+        self._h_vec = np.array(mesh.meshsize(), dtype=np.float64)
+        self._lc = np.array(mesh.lc, dtype=np.float64)
+
+    def _unlin(self, lin):
+        out, r = np.empty((len(lin), len(self._dims)), dtype=np.int64), np.asarray(lin, dtype=np.int64)
+        for d, k in enumerate(self._dims):
+            out[:, d] = r % k
+            r = r // k
+        return out
+
+    def _lin(self, I):
+        I = (I,) if isinstance(I, (int, np.integer)) else tuple(I)
+        if len(I) != len(self._dims) or not all(0 <= int(I[d]) < self._dims[d] for d in range(len(I))):
+            raise KeyError(I)
+        lin, s = 0, 1
+        for d, k in enumerate(self._dims):
+            lin += int(I[d]) * s
+            s *= int(k)
+        return lin
+
+    def _full_nodes(self, cells):
+        """nodes and weights of full cells (rows of `full_cells`): the unit rule mapped to each cell"""
+        lo = self._lc + cells.astype(np.float64) * self._h_vec                    # (c, N)
+        x = lo[:, None, :] + self.rule.coords[None, :, :] * self._h_vec         # (c, m, N)
+        w = np.broadcast_to(self.rule.weights * float(np.prod(self._h_vec)), x.shape[:2])
+        return x.reshape(-1, x.shape[-1]), w.reshape(-1)
+
+    def __getitem__(self, I):
+        lin = self._lin(I)
+        i = int(np.searchsorted(self._cut_lin, lin))
+        if i < self.ncut and self._cut_lin[i] == lin:
+            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+            return Quadrature(self.coords[a:b], self.weights[a:b])
+        j = int(np.searchsorted(self._full_lin, lin))
+        if j < self.nfull and self._full_lin[j] == lin:
+            return Quadrature(*self._full_nodes(self.full_cells[j:j + 1]))
+        raise KeyError(I)
+
+    def __contains__(self, I):
+        try:
+            self[I]
+        except KeyError:
+            return False
+        return True
+
+    def __len__(self):
+        return self.ncut + self.nfull
+
+    def keys(self):
+        lin = np.concatenate([self._cut_lin, self._full_lin])
+        return [tuple(int(v) for v in I) for I in self._unlin(np.sort(lin))]
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def values(self):
+        return [self[I] for I in self.keys()]
+
+    def items(self):
+        return [(I, self[I]) for I in self.keys()]
+
+    def total(self):
+        """Σ of every weight, full cells included (computed on the device)"""
+        return self._backend.quad_total(self._h)
+
+    def __repr__(self):
+        return (f"CellQuadratures: {self.ncut} cut cells ({self.nnodes} nodes), {self.nfull} full cells, "
+                f"quadrature_order = {self.quadrature_order}, surface = {str(self.surface).lower()}")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self._backend.quad_destroy(h)
+            except Exception:
+                pass
+
+
+def quadrature(phi, *, interpolation_order=None, quadrature_order, surface=False):
+    """quadrature(ϕ; interpolation_order, quadrature_order, surface = false) / quadrature(itp::InterpolatedField; quadrature_order,
+    surface = false) (src/LevelSetMethods.jl:103-126, ext/ImplicitIntegrationExt.jl): nodes and weights integrating over ϕ < 0, or
+    over ϕ = 0 with surface = True, of the piecewise interpolant of degree interpolation_order, quadrature_order Gauss–Legendre
+    points per direction, computed on the device.  ϕ: a device field (dense or narrow band: surface only) or an
+    InterpolatedField.  Returns a CellQuadratures; warns when some boxes got the low-order fallback."""
+    import warnings
+    if isinstance(phi, InterpolatedField):
+        if interpolation_order is not None:
+            raise TypeError("quadrature(::InterpolatedField) takes no keyword interpolation_order: the field fixes it")
+        field, order = phi.phi, phi.order
+    elif isinstance(phi, ROCMeshField):
+        if interpolation_order is None:
+            raise TypeError("quadrature(ϕ) needs the keyword interpolation_order (or pass an InterpolatedField)")
+        field, order = phi, interpolation_order
+    else:
+        raise TypeError("quadrature takes a device field (ROCMeshField / ROCNarrowBandMeshField) or an InterpolatedField")
+    band = isinstance(field, ROCNarrowBandMeshField)
+    if band and not surface:
+        raise ValueError(_BAND_VOLUME_MSG)
+    if int(order) != order or not 1 <= int(order) <= 5:
+        raise ValueError("interpolation_order must be in 1..5")
+    if int(quadrature_order) != quadrature_order or not 1 <= int(quadrature_order) <= 20:
+        raise ValueError("quadrature_order must be in 1..20")
+    b = field.backend
+    if getattr(b, "slab", None) is not None:
+        raise ValueError("quadrature of a slab-decomposed field (a field with a comm) is not supported")
+    if field.bcs is None:
+        raise ValueError("the field needs boundary conditions: the interpolation stencils reach outside the grid")
+    mask = None
+    if band:
+        field.prepare(field.buf)
+        mask = field.mask
+    h, counts = b.quad_create(field.buf, mask, int(order), int(quadrature_order), surface)
+    field.ghosts_dirty = False
+    q = CellQuadratures(b, field.mesh, h, counts, int(quadrature_order), surface)
+    if q.nfallback:
+        warnings.warn(f"quadrature: {q.nfallback} boxes reached the subdivision limit and got the low-order rule")
+    return q
+
+
+def integrate(f, q, chunk=1 << 16):
+    """Σ f(x)·w over the nodes of one Quadrature, or of every cell of a CellQuadratures (full cells `chunk` at a time).
+    f maps an (m, N) array of points to (m,) values."""
+    if isinstance(q, Quadrature):
+        return float(np.dot(np.asarray(f(q.coords), dtype=np.float64), q.weights)) if len(q) else 0.0
+    if not isinstance(q, CellQuadratures):
+        raise TypeError("integrate(f, q): q is a Quadrature or a CellQuadratures")
+    s = float(np.dot(np.asarray(f(q.coords), dtype=np.float64), q.weights)) if q.nnodes else 0.0
+    for a in range(0, q.nfull, chunk):
+        x, w = q._full_nodes(q.full_cells[a:a + chunk])
+        s += float(np.dot(np.asarray(f(x), dtype=np.float64), w))
+    return s

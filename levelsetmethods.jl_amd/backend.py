@@ -272,6 +272,35 @@ class HipBackend:
     def sdf_destroy(self, sdf):
         self.lib.lsm_sdf_destroy(sdf)
 
+    # ---- quadrature results (lsm_quad_*)
+    def quad_create(self, phi, mask, interpolation_order, quadrature_order, surface):
+        """returns (result handle, (ncut, nnodes, nfull, nfallback))"""
+        out, cnt = C.c_void_p(), (C.c_int64 * 4)()
+        L.check(self.h, self.lib.lsm_quad_create(self.h, self.ptr(phi), self.ptr(mask), int(interpolation_order), int(quadrature_order),
+                                                 int(bool(surface)), C.byref(out), cnt), "lsm_quad_create")
+        return out, tuple(int(v) for v in cnt)
+
+    def quad_read(self, quad, counts, q):
+        """the result's device arrays: cells, offsets, coords, weights, full cells, rule coords, rule weights"""
+        t, N = self.torch, self.ndim
+        ncut, nnodes, nfull, _ = counts
+        i64 = dict(dtype=t.int64, device=self.device)
+        f64 = dict(dtype=t.float64, device=self.device)
+        cells, offsets, full = t.empty(ncut, **i64), t.empty(ncut + 1, **i64), t.empty(nfull, **i64)
+        coords, weights = t.empty((nnodes, N), **f64), t.empty(nnodes, **f64)
+        rule_x, rule_w = t.empty((q ** N, N), **f64), t.empty(q ** N, **f64)
+        L.check(self.h, self.lib.lsm_quad_read(quad, self.ptr(cells), self.ptr(offsets), self.ptr(coords), self.ptr(weights), self.ptr(full),
+                                               self.ptr(rule_x), self.ptr(rule_w)), "lsm_quad_read")
+        return cells, offsets, coords, weights, full, rule_x, rule_w
+
+    def quad_total(self, quad):
+        out = C.c_double()
+        L.check(self.h, self.lib.lsm_quad_total(quad, C.byref(out)), "lsm_quad_total")
+        return float(out.value)
+
+    def quad_destroy(self, quad):
+        self.lib.lsm_quad_destroy(quad)
+
     def extend_along_normals(self, F, phi, frozen, nb_iters, cfl, interface_band, min_norm):
         work = [self.alloc()] + [self.alloc_side() for _ in range(self.ndim)]   # F staging + the normal components
         w = [self.ptr(x) for x in work] + [None] * (4 - len(work))

@@ -1723,6 +1723,50 @@ void lsm_sdf_destroy(LsmSdf* s) {
     delete s;
 }
 
+// quadrature (src/LevelSetMethods.jl:103-126, ext/ImplicitIntegrationExt.jl): build once, copy the arrays out, total of the weights
+struct LsmQuad { LsmHandle* h; QuadObject* o; };
+int lsm_quad_create(LsmHandle* h, void* phi, const void* mask, int interpolation_order, int quadrature_order, int surface, LsmQuad** out,
+                    int64_t* counts) {
+    if (!h || !phi || !out) return h ? fail(h, LSM_ERR_INVALID, "lsm_quad_create: null argument") : LSM_ERR_INVALID;
+    if (mask && !surface)
+        return fail(h, LSM_ERR_INVALID, "lsm_quad_create: volume integrals (surface = 0) are not supported on a narrow band");
+    LSM_TRY(check_single_device(h));
+    if (!mask) LSM_TRY(lsm_fill_ghosts(h, phi, 7, nullptr));
+    const int N = h->grid.ndim;
+    double lc[3] = {0, 0, 0};
+    for (int d = 0; d < N; ++d) lc[d] = h->grid.lc[d];
+    const char* err = nullptr;
+    QuadObject* o = nullptr;
+    long long c[4] = {0, 0, 0, 0};
+    const int r = quad_build(N, h->nloc, h->goff, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, interpolation_order, quadrature_order,
+                             surface, phi, is_f32(h), (const unsigned char*)mask, h->stream, &o, c, &err);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_quad_create");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_quad_create");
+    *out = new LsmQuad{h, o};
+    if (counts)
+        for (int i = 0; i < 4; ++i) counts[i] = c[i];
+    return LSM_OK;
+}
+int lsm_quad_read(LsmQuad* s, void* cells, void* offsets, void* coords, void* weights, void* full_cells, void* rule_coords, void* rule_weights) {
+    if (!s) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (quad_read(s->o, (long long*)cells, (long long*)offsets, (double*)coords, (double*)weights, (long long*)full_cells, (double*)rule_coords,
+                  (double*)rule_weights, &err))
+        return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_quad_read");
+    return LSM_OK;
+}
+int lsm_quad_total(LsmQuad* s, double* total) {
+    if (!s || !total) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (quad_total(s->o, total, &err)) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_quad_total");
+    return LSM_OK;
+}
+void lsm_quad_destroy(LsmQuad* s) {
+    if (!s) return;
+    quad_free(s->o);
+    delete s;
+}
+
 int lsm_cfl_cache(LsmHandle* h, int enable) {
     if (!h) return LSM_ERR_INVALID;
     h->cfl_cache_on = enable != 0;

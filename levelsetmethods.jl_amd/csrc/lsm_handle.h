@@ -107,3 +107,13 @@ bool lsm_comm_overlap(const LsmHandle* h);
 int lsm_host_sync(LsmHandle* h, const char* what);   // host wait for h->stream that an RCCL peer's silence cannot hang (lsm_comm.hip)
 int lsm_comm_band_overlap(const LsmHandle* h);   // overlap depth declared by lsm_band_overlap_config (0 = none)
 namespace lsm { void i2oe_workspace_free(I2oeWorkspace* w); }   // lsm_i2oe.hip
+namespace lsm {   // lsm_quad.hip (compiled through lsm_reinit.hip): quadrature results
+struct QuadObject;
+int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3],
+               int order, int q, int surface, const void* phi, int f32, const unsigned char* mask, hipStream_t stream, QuadObject** out,
+               long long counts_out[4], const char** err);
+int quad_read(QuadObject* o, long long* cells, long long* offsets, double* coords, double* weights, long long* full, double* rule_x, double* rule_w,
+              const char** err);
+int quad_total(QuadObject* o, double* total, const char** err);
+void quad_free(QuadObject* o);
+}

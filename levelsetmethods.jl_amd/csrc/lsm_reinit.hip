@@ -1916,4 +1916,8 @@ int sdf_samples(SdfObject* o, double* out, const char** err) {
 }
 void sdf_free(SdfObject* o) { delete o; }
 
+// quadrature (lsm_quad_*) is compiled in this translation unit, on the patch set-up above.  make does not track the include: touch
+// this file after editing lsm_quad.hip.
+#include "lsm_quad.hip"
+
 }  // namespace lsm
