@@ -118,6 +118,16 @@ int* lsm_tuning_field(LsmTuning& t, const char* name) {
 }
 }  // namespace lsm
 
+// also runs on lsm_create's failure paths, where the streams may not exist yet; the buffers free themselves after this
+LsmHandle::~LsmHandle() {
+    for (auto e : ev_start) (void)hipEventDestroy(e);
+    for (auto e : ev_stop) (void)hipEventDestroy(e);
+    if (cfl_stream) (void)hipStreamDestroy(cfl_stream);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+    reinit_workspace_free(reinit_ws);
+    i2oe_workspace_free(i2oe_ws);
+}
+
 extern "C" {
 
 int lsm_set_tuning(LsmHandle* h, const char* name, int value) {
@@ -184,27 +194,6 @@ int lsm_create(const LsmGrid* grid, const LsmBc bc[LSM_MAX_DIM][2], const LsmSla
     h->grid = *grid;
     memcpy(h->bc, bc, sizeof(h->bc));
     h->dtype = dtype; h->mode = mode; h->device = device;
-    h->prof = false; h->ev_used = 0; h->prof_every = 1; h->prof_seen = 0;
-    h->comm = nullptr;
-    h->ghost_depth = LSM_GHOST;
-    h->slab_depth_valid = LSM_GHOST;     // a slab's ghosts are the host's to make valid before its first step (include/lsm.h)
-    h->status_ticket = 0;
-    h->mredirect = false;
-    h->reinit_ws = nullptr;
-    h->i2oe_ws = nullptr;
-    h->d_pf_flag = nullptr;
-    memset(&h->band_cfl, 0, sizeof(h->band_cfl));
-    h->cfl_prefetched = false;
-    h->d_stamp = nullptr;
-    h->d_tail_ctr = nullptr; h->tail_ticket = 0;
-    h->xredirect = false;
-    h->yredirect = false;
-    h->cfl_cache_on = true;
-    h->d_cand_count = nullptr;
-    h->d_ring = nullptr; h->nring = 0; h->d_miss = nullptr; h->d_count = nullptr; h->d_work = nullptr; h->d_tiles_old = nullptr; h->work_cap = 0; h->halo_n_key = nullptr; h->halo_n = 0;
-    h->band_mask = nullptr; h->band_tiles = nullptr; h->band_mc = 0; h->band_list = nullptr; h->band_nlist = 0;
-    h->d_act_list = nullptr; h->d_work_list = nullptr; h->d_lcounts = nullptr; h->lists_tiles = nullptr; h->lists_mc = 0;
-    h->lists_host_valid = false; h->nact = h->nwork = h->nface = 0;
     h->tune = lsm_tuning_env();
     h->no_lists = h->tune.band_no_lists != 0;
     h->band_bytes = h->tune.band_bytes != 0;
@@ -268,22 +257,21 @@ int lsm_create(const LsmGrid* grid, const LsmBc bc[LSM_MAX_DIM][2], const LsmSla
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     h->own_stream = true;
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_partial, sizeof(double) * 2 * MAXB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tail_ctr, LSM_TAIL_SLOTS * sizeof(unsigned));
+    if (e == hipSuccess) e = h->d_partial.alloc(sizeof(double) * 2 * MAXB);
+    if (e == hipSuccess) e = h->d_tail_ctr.alloc(LSM_TAIL_SLOTS * sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(h->d_tail_ctr, 0, LSM_TAIL_SLOTS * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_flag, sizeof(int));
-    h->cfl_stream = nullptr; h->c_partial = h->c_result = h->ch_result = nullptr; h->c_flag = nullptr;
+    if (e == hipSuccess) e = h->d_flag.alloc(sizeof(int));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->cfl_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->c_partial, sizeof(double) * 2 * MAXB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->c_flag, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->c_result, sizeof(double) * 2);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h->ch_result, sizeof(double) * 2, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_w, sizeof(h->w));
+    if (e == hipSuccess) e = h->c_partial.alloc(sizeof(double) * 2 * MAXB);
+    if (e == hipSuccess) e = h->c_flag.alloc(sizeof(int));
+    if (e == hipSuccess) e = h->c_result.alloc(sizeof(double) * 2);
+    if (e == hipSuccess) e = h->ch_result.alloc(sizeof(double) * 2);
+    if (e == hipSuccess) e = h->d_w.alloc(sizeof(h->w));
     if (e == hipSuccess) e = hipMemcpy(h->d_w, h->w, sizeof(h->w), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_result, sizeof(double) * 16);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_result, sizeof(double) * 16, hipHostMallocMapped);
+    if (e == hipSuccess) e = h->d_result.alloc(sizeof(double) * 16);
+    if (e == hipSuccess) e = h->h_result.alloc(sizeof(double) * 16, hipHostMallocMapped);
     if (e == hipSuccess) { memset(h->h_result, 0, sizeof(double) * 16); e = hipHostGetDevicePointer((void**)&h->h_result_dev, h->h_result, 0); }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_pf_flag, sizeof(int) * 4);
+    if (e == hipSuccess) e = h->d_pf_flag.alloc(sizeof(int) * 4);
     if (e != hipSuccess) {
         std::string m = std::string("lsm_create: ") + hipGetErrorString(e);
         delete h;
@@ -297,27 +285,7 @@ void lsm_destroy(LsmHandle* h) {
     if (!h) return;
     (void)lsm_comm_detach(h);
     (void)hipSetDevice(h->device);
-    if (h->d_stamp) (void)hipFree(h->d_stamp);
-    if (h->d_tail_ctr) (void)hipFree(h->d_tail_ctr);
     (void)hipStreamSynchronize(h->stream);
-    for (auto e : h->ev_start) (void)hipEventDestroy(e);
-    for (auto e : h->ev_stop) (void)hipEventDestroy(e);
-    for (auto& e : h->cfl_cand) (void)hipFree(e.d_cand);
-    if (h->d_cand_count) (void)hipFree(h->d_cand_count);
-    (void)hipFree(h->d_partial);
-    (void)hipFree(h->d_flag);
-    if (h->cfl_stream) (void)hipStreamDestroy(h->cfl_stream);
-    (void)hipFree(h->c_partial); (void)hipFree(h->c_flag); (void)hipFree(h->c_result);
-    if (h->ch_result) (void)hipHostFree(h->ch_result);
-    (void)hipFree(h->d_w);
-    if (h->d_ring) { (void)hipFree(h->d_ring); (void)hipFree(h->d_miss); (void)hipFree(h->d_count); }
-    if (h->d_work) { (void)hipFree(h->d_work); (void)hipFree(h->d_act_list); (void)hipFree(h->d_work_list); (void)hipFree(h->d_lcounts); (void)hipFree(h->d_tiles_old); }
-    (void)hipFree(h->d_result);
-    if (h->d_pf_flag) (void)hipFree(h->d_pf_flag);
-    reinit_workspace_free(h->reinit_ws);
-    i2oe_workspace_free(h->i2oe_ws);
-    (void)hipHostFree(h->h_result);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -684,9 +652,9 @@ int lsm_compute_cfl(LsmHandle* h, const LsmTerm* terms, int nterms, const void* 
                     if (memcmp(&e.key, &tm, sizeof(LsmTerm)) == 0) { cand = &e; break; }
                 if (!cand) {
                     const unsigned cap = 8192;
-                    if (!h->d_cand_count) LSM_HIP(h, hipMalloc((void**)&h->d_cand_count, sizeof(unsigned)));
-                    long long* buf = nullptr;
-                    LSM_HIP(h, hipMalloc((void**)&buf, cap * sizeof(long long)));
+                    if (!h->d_cand_count) LSM_HIP(h, h->d_cand_count.alloc(sizeof(unsigned)));
+                    DevBuf<long long> buf;
+                    LSM_HIP(h, buf.alloc(cap * sizeof(long long)));
                     CflArgs b = a;
                     b.partial = h->d_partial; b.nanflag = h->d_flag;      // one-off search on the main stream, synchronised
                     b.coeff.tfac = 1.0;
@@ -702,11 +670,9 @@ int lsm_compute_cfl(LsmHandle* h, const LsmTerm* terms, int nterms, const void* 
                     LSM_SYNC(h);
                     LSM_HIP(h, hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
                     if (!flag && cnt >= 1 && cnt <= cap) {     // NaN tables or a flat maximum: keep sweeping the grid
-                        if (h->cfl_cand.size() > 16) { for (auto& e : h->cfl_cand) (void)hipFree(e.d_cand); h->cfl_cand.clear(); }
-                        h->cfl_cand.push_back({tm, buf, cnt});
+                        if (h->cfl_cand.size() > 16) h->cfl_cand.clear();
+                        h->cfl_cand.push_back({tm, std::move(buf), cnt});
                         cand = &h->cfl_cand.back();
-                    } else {
-                        (void)hipFree(buf);
                     }
                 }
             }
@@ -962,7 +928,7 @@ int lsm_debug_stamp(LsmHandle* h, int enable, double* clock_ghz, double* loop_us
     if (!h) return LSM_ERR_INVALID;
     LSM_HIP(h, hipSetDevice(h->device));
     if (enable) {
-        if (!h->d_stamp) LSM_HIP(h, hipMalloc((void**)&h->d_stamp, sizeof(unsigned long long) * 4 * 16384));
+        if (!h->d_stamp) LSM_HIP(h, h->d_stamp.alloc(sizeof(unsigned long long) * 4 * 16384));
         LSM_HIP(h, hipMemsetAsync(h->d_stamp, 0, sizeof(unsigned long long) * 4 * 16384, h->stream));
         return LSM_OK;
     }
@@ -1163,25 +1129,27 @@ static int ensure_ring(LsmHandle* h) {
     h->nring_lds = h->nring;
     for (int r = h->nring - 1; r >= 0; --r)
         if (std::abs((int)off[r][0]) > 3 || std::abs((int)off[r][1]) > 3 || std::abs((int)off[r][2]) > 3) h->nring_lds = r;
-    LSM_HIP(h, hipMalloc((void**)&h->d_ring, off.size() * 3));
-    LSM_HIP(h, hipMemcpy(h->d_ring, off.data(), off.size() * 3, hipMemcpyHostToDevice));
-    LSM_HIP(h, hipMalloc((void**)&h->d_miss, sizeof(int)));
-    LSM_HIP(h, hipMalloc((void**)&h->d_count, sizeof(unsigned long long)));
+    DevBuf<signed char> ring;      // the handle's only once all three buffers are ready
+    LSM_HIP(h, ring.alloc(off.size() * 3));
+    LSM_HIP(h, hipMemcpy(ring, off.data(), off.size() * 3, hipMemcpyHostToDevice));
+    LSM_HIP(h, h->d_miss.alloc(sizeof(int)));
+    LSM_HIP(h, h->d_count.alloc(sizeof(unsigned long long)));
     LSM_HIP(h, hipMemset(h->d_miss, 0, sizeof(int)));
+    h->d_ring = std::move(ring);
     return LSM_OK;
 }
 
-// handle-owned scratch for the per-tile work flags
+// handle-owned scratch for the per-tile work flags and tile lists, all sized for the same tile count: d_lcounts, allocated last,
+// is there only when the others are
 static int ensure_work(LsmHandle* h, int64_t ntiles) {
-    if (h->work_cap >= ntiles) return LSM_OK;
-    if (h->d_work) { (void)hipFree(h->d_work); (void)hipFree(h->d_act_list); (void)hipFree(h->d_work_list); (void)hipFree(h->d_lcounts); (void)hipFree(h->d_tiles_old); }
-    LSM_HIP(h, hipMalloc((void**)&h->d_work, (size_t)ntiles));
-    LSM_HIP(h, hipMalloc((void**)&h->d_tiles_old, (size_t)ntiles));
-    LSM_HIP(h, hipMalloc((void**)&h->d_act_list, (size_t)ntiles * sizeof(int)));
-    LSM_HIP(h, hipMalloc((void**)&h->d_work_list, (size_t)ntiles * sizeof(int)));
-    LSM_HIP(h, hipMalloc((void**)&h->d_lcounts, 4 * sizeof(unsigned)));
-    h->work_cap = ntiles;
+    if (h->d_lcounts && h->d_work.cap >= (size_t)ntiles) return LSM_OK;
     h->lists_tiles = nullptr; h->lists_host_valid = false;
+    h->d_work.release(); h->d_tiles_old.release(); h->d_act_list.release(); h->d_work_list.release(); h->d_lcounts.release();
+    LSM_HIP(h, h->d_work.alloc((size_t)ntiles));
+    LSM_HIP(h, h->d_tiles_old.alloc((size_t)ntiles));
+    LSM_HIP(h, h->d_act_list.alloc((size_t)ntiles * sizeof(int)));
+    LSM_HIP(h, h->d_work_list.alloc((size_t)ntiles * sizeof(int)));
+    LSM_HIP(h, h->d_lcounts.alloc(4 * sizeof(unsigned)));
     return LSM_OK;
 }
 
@@ -1773,7 +1741,6 @@ int lsm_cfl_cache(LsmHandle* h, int enable) {
     h->cfl_cache.clear();
     h->band_cfl.armed = h->band_cfl.valid = h->band_cfl.pending = false;   // a prefetched band Δt goes with the cache
     h->band_cfl.nterms = 0;
-    for (auto& e : h->cfl_cand) (void)hipFree(e.d_cand);
     h->cfl_cand.clear();
     return LSM_OK;
 }

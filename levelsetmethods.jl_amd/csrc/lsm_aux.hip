@@ -1,7 +1,7 @@
 // lsm_aux.hip — the small kernels around the stage kernel: ghost-layer fill, CFL reduction,
 // extrema, Eikonal sign map.  Built with -ffp-contract=off: ghost values and the CFL minimum are
 // bit-for-bit those of the reference arithmetic (they cost nothing next to a stage).
-#include "lsm_internal.h"
+#include "lsm_handle.h"
 
 namespace lsm {
 
@@ -864,14 +864,13 @@ int launch_band_volume(int ndim, const int n[3], long long s1, long long s2, lon
                        const unsigned char* mask, double* out, hipStream_t s) {
     const int n0 = n[0], n1 = ndim > 1 ? n[1] : 1, n2 = ndim > 2 ? n[2] : 1;
     const long long nlines = (long long)n1 * n2;
-    long long *cnt = nullptr, *g0 = nullptr, *g1 = nullptr;
-    double* hsum = nullptr;
-    int *near = nullptr, *neg0 = nullptr, *neg1 = nullptr;
-    auto cleanup = [&]() { (void)hipFree(cnt); (void)hipFree(g0); (void)hipFree(g1); (void)hipFree(hsum); (void)hipFree(near); (void)hipFree(neg0); (void)hipFree(neg1); };
-    if (hipMalloc((void**)&cnt, 8 * nlines) != hipSuccess || hipMalloc((void**)&g0, 8 * nlines) != hipSuccess ||
-        hipMalloc((void**)&g1, 8 * nlines) != hipSuccess || hipMalloc((void**)&hsum, 8 * nlines) != hipSuccess ||
-        hipMalloc((void**)&near, 4 * nlines) != hipSuccess || hipMalloc((void**)&neg0, 4 * nlines) != hipSuccess ||
-        hipMalloc((void**)&neg1, 4 * nlines) != hipSuccess) { cleanup(); return 1; }
+    DevBuf<long long> cnt, g0, g1;
+    DevBuf<double> hsum;
+    DevBuf<int> near, neg0, neg1;
+    if (cnt.alloc(8 * nlines) != hipSuccess || g0.alloc(8 * nlines) != hipSuccess || g1.alloc(8 * nlines) != hipSuccess ||
+        hsum.alloc(8 * nlines) != hipSuccess || near.alloc(4 * nlines) != hipSuccess || neg0.alloc(4 * nlines) != hipSuccess ||
+        neg1.alloc(4 * nlines) != hipSuccess)
+        return 1;
     const int x0 = n0 / 2 - 1;                                   // the reference's 1-based n1 ÷ 2
     long long wb = (nlines * 64 + 255) / 256;
     hipLaunchKernelGGL(band_lines_kernel, dim3((unsigned)(wb > 65535 ? 65535 : wb)), dim3(256), 0, s, ndim, n0, n1, n2, s1, s2, origin, dmin, v, f32,
@@ -881,9 +880,7 @@ int launch_band_volume(int ndim, const int n[3], long long s1, long long s2, lon
     hipLaunchKernelGGL(band_lines_minplus_kernel, dim3(lb), dim3(256), 0, s, 1, n1, n2, g0, neg0, g1, neg1);
     hipLaunchKernelGGL(band_lines_minplus_kernel, dim3(lb), dim3(256), 0, s, 2, n1, n2, g1, neg1, g0, neg0);
     hipLaunchKernelGGL(band_lines_final_kernel, dim3(1), dim3(256), 0, s, nlines, n0, cnt, hsum, near, g0, neg0, scale, out);
-    const bool ok = hipStreamSynchronize(s) == hipSuccess;
-    cleanup();
-    return ok ? 0 : 1;
+    return hipStreamSynchronize(s) == hipSuccess ? 0 : 1;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -139,20 +139,17 @@ struct LsmComm {
     std::atomic<bool> failed;  // a call failed half-way, a peer is gone, or lsm_comm_abort was called: LSM_ERR_COMM from now on
     ncclComm_t nccl;
     std::atomic<bool> nccl_aborted;   // ncclCommAbort has run (once): `nccl` is gone — never used again, never destroyed
-    double* d_dt;              // device scalar of the Δt all-reduce
-    double* h_dt;              // pinned host scalar
+    lsm::DevBuf<double> d_dt;          // device scalar of the Δt all-reduce
+    lsm::PinnedBuf<double> h_dt;       // host scalar
     LocalGroup* grp;
     // slab-decomposed NarrowBandMeshField (lsm_band_overlap_*): W planes of each neighbour held as planes of this slab
     int band_W;
-    unsigned* d_idx[4];        // band nodes (byte offsets within the plane range) of [send up, recv dn, send dn, recv up]
-    size_t idx_cap[4];
+    lsm::DevBuf<unsigned> d_idx[4];    // band nodes (byte offsets within the plane range) of [send up, recv dn, send dn, recv up]
     unsigned n_idx[4];
-    char* d_pack[4];           // packed values of those nodes
-    size_t pack_cap[4];
-    unsigned* d_nz_counts;     // scratch of the ordered compaction: per-chunk counts / offsets, and the four totals
-    size_t nz_cap;
-    unsigned* d_nz_total;      // 4 totals
-    unsigned* h_nz_total;      // pinned
+    lsm::DevBuf<char> d_pack[4];       // packed values of those nodes
+    lsm::DevBuf<unsigned> d_nz_counts; // scratch of the ordered compaction: per-chunk counts / offsets, and the four totals
+    lsm::DevBuf<unsigned> d_nz_total;  // 4 totals
+    lsm::PinnedBuf<unsigned> h_nz_total;
 };
 
 namespace {
@@ -235,18 +232,16 @@ int make_comm(LsmHandle* h, int transport, int rank, int world, LsmComm** out) {
     c->wrap_dn = face_dn && rank == 0;
     c->wrap_up = face_up && rank == world - 1;
     c->overlap = h->tune.slab_overlap != 0;
-    c->seq = 0; c->pending = false; c->failed.store(false); c->nccl = nullptr; c->nccl_aborted.store(false); c->d_dt = nullptr; c->h_dt = nullptr; c->grp = nullptr;
+    c->seq = 0; c->pending = false; c->failed.store(false); c->nccl = nullptr; c->nccl_aborted.store(false); c->grp = nullptr;
     c->stream = nullptr;
     for (auto& e : c->ev_ready) e = nullptr;
     for (auto& e : c->ev_done) e = nullptr;
     c->band_W = 0;
-    for (int k = 0; k < 4; ++k) { c->d_idx[k] = nullptr; c->idx_cap[k] = 0; c->n_idx[k] = 0; c->d_pack[k] = nullptr; c->pack_cap[k] = 0; }
-    c->d_nz_counts = nullptr; c->nz_cap = 0; c->d_nz_total = nullptr; c->h_nz_total = nullptr;
+    for (int k = 0; k < 4; ++k) c->n_idx[k] = 0;
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_dt, sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_dt, sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = c->d_dt.alloc(sizeof(double));
+    if (e == hipSuccess) e = c->h_dt.alloc(sizeof(double));
     if (e != hipSuccess) {
-        if (c->d_dt) (void)hipFree(c->d_dt);
         delete c;
         return lsm_fail(h, LSM_ERR_HIP, std::string("lsm_comm_attach: ") + hipGetErrorString(e));
     }
@@ -289,12 +284,6 @@ void free_comm(LsmHandle* h, LsmComm* c) {
         for (auto e : c->ev_done) if (e) (void)hipEventDestroy(e);
         if (c->stream) (void)hipStreamDestroy(c->stream);
     }
-    if (c->d_dt) (void)hipFree(c->d_dt);
-    if (c->h_dt) (void)hipHostFree(c->h_dt);
-    for (int k = 0; k < 4; ++k) { if (c->d_idx[k]) (void)hipFree(c->d_idx[k]); if (c->d_pack[k]) (void)hipFree(c->d_pack[k]); }
-    if (c->d_nz_counts) (void)hipFree(c->d_nz_counts);
-    if (c->d_nz_total) (void)hipFree(c->d_nz_total);
-    if (c->h_nz_total) (void)hipHostFree(c->h_nz_total);
     if (g) {
         bool last;
         { std::lock_guard<std::mutex> lk(g->mu); last = --g->refs == 0; }
@@ -767,13 +756,13 @@ int lsm_band_overlap_config(LsmHandle* h, int64_t overlap) {
     if (overlap < 1 || h->nloc[N - 1] < need)
         return lsm_fail(h, LSM_ERR_INVALID, "lsm_band_overlap_config: the slab must hold `overlap` planes of each neighbour and at least as many of its own");
     if (c->wrap_up || c->wrap_dn) return lsm_fail(h, LSM_ERR_INVALID, "lsm_band_overlap_config: PeriodicBC is not supported on a NarrowBandMeshField");
+    if (!c->d_nz_total || !c->h_nz_total) {
+        COMM_HIP(h, hipSetDevice(h->device));
+        COMM_HIP(h, c->d_nz_total.alloc(4 * sizeof(unsigned)));
+        COMM_HIP(h, c->h_nz_total.alloc(4 * sizeof(unsigned)));
+    }
     c->band_W = (int)overlap;
     for (int k = 0; k < 4; ++k) c->n_idx[k] = 0;
-    if (!c->d_nz_total) {
-        COMM_HIP(h, hipSetDevice(h->device));
-        COMM_HIP(h, hipMalloc((void**)&c->d_nz_total, 4 * sizeof(unsigned)));
-        COMM_HIP(h, hipHostMalloc((void**)&c->h_nz_total, 4 * sizeof(unsigned), hipHostMallocDefault));
-    }
     return LSM_OK;
 }
 
@@ -795,12 +784,7 @@ int lsm_band_overlap_mask(LsmHandle* h, void* mask) {
     // band nodes of the four plane ranges, in index order
     const unsigned nchunks = (unsigned)((nb + NZ_CHUNK - 1) / NZ_CHUNK);
     COMM_HIP(h, hipSetDevice(h->device));
-    if (c->nz_cap < (size_t)4 * nchunks) {
-        if (c->d_nz_counts) (void)hipFree(c->d_nz_counts);
-        c->d_nz_counts = nullptr; c->nz_cap = 0;
-        COMM_HIP(h, hipMalloc((void**)&c->d_nz_counts, (size_t)4 * nchunks * sizeof(unsigned)));
-        c->nz_cap = (size_t)4 * nchunks;
-    }
+    if (c->d_nz_counts.cap < (size_t)4 * nchunks * sizeof(unsigned)) COMM_HIP(h, c->d_nz_counts.alloc((size_t)4 * nchunks * sizeof(unsigned)));
     COMM_HIP(h, hipMemsetAsync(c->d_nz_total, 0, 4 * sizeof(unsigned), h->stream));
     for (int k = 0; k < 4; ++k) {
         if (first[k] < 0) continue;
@@ -815,17 +799,14 @@ int lsm_band_overlap_mask(LsmHandle* h, void* mask) {
     for (int k = 0; k < 4; ++k) {
         c->n_idx[k] = first[k] >= 0 ? c->h_nz_total[k] : 0u;
         if (!c->n_idx[k]) continue;
-        if (c->idx_cap[k] < c->n_idx[k]) {
-            if (c->d_idx[k]) (void)hipFree(c->d_idx[k]);
-            if (c->d_pack[k]) (void)hipFree(c->d_pack[k]);
-            c->d_idx[k] = nullptr; c->d_pack[k] = nullptr; c->idx_cap[k] = 0;
+        if (c->d_idx[k].cap < (size_t)c->n_idx[k] * sizeof(unsigned) || c->d_pack[k].cap < (size_t)c->n_idx[k] * sizeof(double)) {
             const size_t cap = (size_t)c->n_idx[k] + c->n_idx[k] / 2 + 1024;
-            COMM_HIP(h, hipMalloc((void**)&c->d_idx[k], cap * sizeof(unsigned)));
-            COMM_HIP(h, hipMalloc((void**)&c->d_pack[k], cap * sizeof(double)));
-            c->idx_cap[k] = cap;
+            COMM_HIP(h, c->d_idx[k].alloc(cap * sizeof(unsigned)));
+            COMM_HIP(h, c->d_pack[k].alloc(cap * sizeof(double)));
         }
         const unsigned char* base = (const unsigned char*)p.at(mask, first[k]);
-        hipLaunchKernelGGL(nz_write_kernel, dim3(nchunks), dim3(256), 0, h->stream, base, nb, c->d_nz_counts + (size_t)k * nchunks, c->d_idx[k], c->idx_cap[k]);
+        hipLaunchKernelGGL(nz_write_kernel, dim3(nchunks), dim3(256), 0, h->stream, base, nb, c->d_nz_counts + (size_t)k * nchunks, c->d_idx[k],
+                           c->d_idx[k].cap / sizeof(unsigned));
     }
     (void)es;
     COMM_HIP(h, hipGetLastError());

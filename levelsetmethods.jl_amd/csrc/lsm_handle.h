@@ -1,4 +1,5 @@
-// lsm_handle.h — the handle behind the C ABI (include/lsm.h), shared by lsm_api.hip and lsm_comm.hip.
+// lsm_handle.h — the handle behind the C ABI (include/lsm.h), shared by lsm_api.hip and lsm_comm.hip, and the owners of the
+// host side's device and pinned buffers.
 #pragma once
 #include <string>
 #include <utility>
@@ -6,10 +7,58 @@
 
 #include "lsm_internal.h"
 
-namespace lsm { struct I2oeWorkspace; }   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
+namespace lsm {
+// a device buffer that only grows: re-allocated when a call needs more than it holds (the set of a NewtonSDF object is built once;
+// the workspace of reinitialize! lives on the handle and stops allocating after the first calls).  Frees itself.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;            // bytes
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    hipError_t alloc(size_t bytes) {
+        release();
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    hipError_t grow(size_t bytes) { return p && cap >= bytes ? hipSuccess : alloc(bytes + bytes / 4 + 256); }   // headroom: the band's size drifts
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+};
+// its pinned-host twin (hipHostMalloc with the given flags)
+template <class T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;            // bytes
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~PinnedBuf() { release(); }
+    operator T*() const { return p; }
+    hipError_t alloc(size_t bytes, unsigned flags = hipHostMallocDefault) {
+        release();
+        const hipError_t e = hipHostMalloc((void**)&p, bytes, flags);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    void release() { (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+struct I2oeWorkspace;   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
+}  // namespace lsm
 struct LsmComm;   // lsm_comm.hip: slab communicator (RCCL or in-process), NULL on a single-device handle
 
 struct LsmHandle {
+    ~LsmHandle();        // lsm_api.hip: streams, events and workspaces; safe on a partly built handle
     LsmGrid grid;
     LsmBc bc[LSM_MAX_DIM][2];
     LsmSlab slab;
@@ -18,42 +67,41 @@ struct LsmHandle {
     int nloc[3], goff[3], gn[3];
     double h[3], h2[3], inv_h[3], inv_h2[3], dxmin;
     double w[3][2][LSM_GHOST][8];
-    hipStream_t stream;
-    bool own_stream;
-    double* d_w;         // device copy of w
-    signed char* d_ring; // narrow band: distance-sorted offset ring
-    int nring;
-    int nring_lds;       // ring entries before the first with a component beyond the LDS apron (3)
-    int* d_miss;
-    unsigned long long* d_count;
-    unsigned char* d_work;             // per-tile work flags (narrow band)
-    unsigned char* d_tiles_old;        // the old band's tile flags during an update (the new ones are written in place)
-    int64_t work_cap;
-    const unsigned char* band_mask;    // set for the duration of a *_band call
-    const unsigned char* band_tiles;
-    int band_mc;
-    const int* band_list;              // compact active-tile list for a stage (NULL = flags only)
-    unsigned band_nlist;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    lsm::DevBuf<double> d_w;             // device copy of w
+    lsm::DevBuf<signed char> d_ring;     // narrow band: distance-sorted offset ring
+    int nring = 0;
+    int nring_lds = 0;   // ring entries before the first with a component beyond the LDS apron (3)
+    lsm::DevBuf<int> d_miss;
+    lsm::DevBuf<unsigned long long> d_count;
+    lsm::DevBuf<unsigned char> d_work;        // per-tile work flags (narrow band)
+    lsm::DevBuf<unsigned char> d_tiles_old;   // the old band's tile flags during an update (the new ones are written in place)
+    const unsigned char* band_mask = nullptr;   // set for the duration of a *_band call
+    const unsigned char* band_tiles = nullptr;
+    int band_mc = 0;
+    const int* band_list = nullptr;    // compact active-tile list for a stage (NULL = flags only)
+    unsigned band_nlist = 0;
     // compact tile lists of the band last updated (built on the device by lsm_band_update, lengths read back by
     // lsm_band_status): with them the band kernels launch one block per listed tile instead of one per tile
-    int* d_act_list;
-    int* d_work_list;
-    unsigned* d_lcounts;
-    const void* lists_tiles;           // the tile-flag buffer the lists describe
-    int lists_mc;
-    bool lists_host_valid;
-    const void* halo_n_key;            // the device counter whose value lsm_band_status last read (NULL: unknown on the host)
-    long long halo_n;
-    unsigned nact, nwork, nface;       // list lengths; work tiles on a face of the grid
+    lsm::DevBuf<int> d_act_list;
+    lsm::DevBuf<int> d_work_list;
+    lsm::DevBuf<unsigned> d_lcounts;
+    const void* lists_tiles = nullptr; // the tile-flag buffer the lists describe
+    int lists_mc = 0;
+    bool lists_host_valid = false;
+    const void* halo_n_key = nullptr;  // the device counter whose value lsm_band_status last read (NULL: unknown on the host)
+    long long halo_n = 0;
+    unsigned nact = 0, nwork = 0, nface = 0;   // list lengths; work tiles on a face of the grid
     lsm::LsmTuning tune;               // tuning switches: the environment's (read once per process) unless lsm_set_tuning changed them
     bool no_lists;                     // = tune.band_no_lists: always launch over all tiles
     bool band_bytes;                   // = tune.band_bytes: byte-mask band kernels in 3-D too
-    double* d_partial;   // 2 * MAXB doubles
-    int* d_flag;
-    double* d_result;    // 16 doubles: [0..1] reductions, [2..6] lsm_band_status, [8..11] Δt of the next step prefetched by lsm_band_update
-    double* h_result;    // pinned, 16 doubles
-    double* h_result_dev;   // the same page as the device sees it: lsm_band_status's kernel writes its numbers there directly
-    unsigned long long status_ticket;   // lsm_band_status: the kernel's last store is the call's ticket ([13]); the host spins on it
+    lsm::DevBuf<double> d_partial;     // 2 * MAXB doubles
+    lsm::DevBuf<int> d_flag;
+    lsm::DevBuf<double> d_result;      // 16 doubles: [0..1] reductions, [2..6] lsm_band_status, [8..11] Δt of the next step prefetched by lsm_band_update
+    lsm::PinnedBuf<double> h_result;   // pinned and mapped, 16 doubles
+    double* h_result_dev = nullptr;    // the same page as the device sees it: lsm_band_status's kernel writes its numbers there directly
+    unsigned long long status_ticket = 0;   // lsm_band_status: the kernel's last store is the call's ticket ([13]); the host spins on it
     // Δt of a band, prefetched: when the terms of the last lsm_compute_cfl_band depend neither on t nor on a field (constants,
     // ROTATION, SEPARABLE without time factor, Eikonal), lsm_band_update runs their reductions over the NEW band right behind
     // its own kernels and lsm_band_status brings the results home in the read it does anyway — the next lsm_compute_cfl_band
@@ -66,38 +114,40 @@ struct LsmHandle {
         bool armed, pending, valid;
         int slot[LSM_MAX_TERMS];           // result slot of a node-dependent term, -1 otherwise
         double dt[LSM_MAX_TERMS];
-    } band_cfl;
-    int* d_pf_flag;      // NaN flags of the prefetched reductions (4)
+    } band_cfl = {};
+    lsm::DevBuf<int> d_pf_flag;        // NaN flags of the prefetched reductions (4)
     std::string err;
-    bool cfl_cache_on;
-    bool cfl_prefetched;   // set around lsm_compute_cfl by lsm_compute_cfl_band when band_cfl holds this call's values
+    bool cfl_cache_on = true;
+    bool cfl_prefetched = false;   // set around lsm_compute_cfl by lsm_compute_cfl_band when band_cfl holds this call's values
     std::vector<std::pair<LsmTerm, double>> cfl_cache;   // time-independent analytic coefficients
-    struct CflCand { LsmTerm key; long long* d_cand; unsigned count; };
+    struct CflCand { LsmTerm key; lsm::DevBuf<long long> d_cand; unsigned count; };
     std::vector<CflCand> cfl_cand;                       // SEPARABLE × g(t): the arg-max candidates are time-independent
-    unsigned* d_cand_count;
+    lsm::DevBuf<unsigned> d_cand_count;
     // Δt of a ϕ-independent term (constant / catalogued analytic coefficient) is reduced on a stream of its own, with
     // its own scratch: the host gets it without waiting for the stages queued on the main stream, and can queue the
     // next step behind them
-    hipStream_t cfl_stream;
-    double *c_partial, *c_result, *ch_result;
-    int* c_flag;
+    hipStream_t cfl_stream = nullptr;
+    lsm::DevBuf<double> c_partial, c_result;
+    lsm::PinnedBuf<double> ch_result;
+    lsm::DevBuf<int> c_flag;
     std::vector<const void*> cfl_seen;   // coefficient tables known to have landed
-    bool prof;
-    int prof_every;              // lsm_profile_enable(h, N): every N-th stage launch is timed
-    unsigned long long prof_seen;   // stage launches since lsm_profile_enable / lsm_profile_read
+    bool prof = false;
+    int prof_every = 1;          // lsm_profile_enable(h, N): every N-th stage launch is timed
+    unsigned long long prof_seen = 0;   // stage launches since lsm_profile_enable / lsm_profile_read
     std::vector<hipEvent_t> ev_start, ev_stop;
-    size_t ev_used;
-    lsm::ReinitWorkspace* reinit_ws;   // reinitialize!'s device buffers, kept between calls (grow-only)
-    lsm::I2oeWorkspace* i2oe_ws;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
-    LsmComm* comm;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
-    bool yredirect;                // ... and those of dimension 2 (3-D)
-    bool mredirect;                // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
-    int ghost_depth;               // ghost layers the fills write and the slab exchange sends: LSM_GHOST, or what the step in progress reads (XRedirect)
-    int slab_depth_valid;          // slab steps: ghost layers of ϕ (boundary conditions + neighbours' planes) the last step left valid
-    unsigned* d_tail_ctr;          // ring of LSM_TAIL_SLOTS ticket counters of the dynamic tail (each launch resets its own)
-    unsigned tail_ticket;          // host: launches that took a slot so far
-    bool xredirect;                // set around the stages of a whole-grid lsm_advance_*: x ghosts are resolved by the stage kernel's loads
-    unsigned long long* d_stamp;   // diagnostic build (-DLSM_STAMP): 8192 x {Δs_memtime, Δs_memrealtime, start, end} of the stage kernel's workgroups
+    size_t ev_used = 0;
+    lsm::ReinitWorkspace* reinit_ws = nullptr;   // reinitialize!'s device buffers, kept between calls (grow-only)
+    lsm::I2oeWorkspace* i2oe_ws = nullptr;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
+    LsmComm* comm = nullptr;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
+    bool yredirect = false;        // ... and those of dimension 2 (3-D)
+    bool mredirect = false;        // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
+    int ghost_depth = LSM_GHOST;   // ghost layers the fills write and the slab exchange sends: LSM_GHOST, or what the step in progress reads (XRedirect)
+    int slab_depth_valid = LSM_GHOST;   // slab steps: ghost layers of ϕ (boundary conditions + neighbours' planes) the last step left valid;
+                                        // a slab's ghosts are the host's to make valid before its first step (include/lsm.h)
+    lsm::DevBuf<unsigned> d_tail_ctr;   // ring of LSM_TAIL_SLOTS ticket counters of the dynamic tail (each launch resets its own)
+    unsigned tail_ticket = 0;      // host: launches that took a slot so far
+    bool xredirect = false;        // set around the stages of a whole-grid lsm_advance_*: x ghosts are resolved by the stage kernel's loads
+    lsm::DevBuf<unsigned long long> d_stamp;   // diagnostic build (-DLSM_STAMP): 8192 x {Δs_memtime, Δs_memrealtime, start, end} of the stage kernel's workgroups
 };
 
 // shared helpers (lsm_api.hip)
@@ -106,7 +156,7 @@ int lsm_fail(LsmHandle* h, int code, const std::string& msg);
 bool lsm_comm_overlap(const LsmHandle* h);
 int lsm_host_sync(LsmHandle* h, const char* what);   // host wait for h->stream that an RCCL peer's silence cannot hang (lsm_comm.hip)
 int lsm_comm_band_overlap(const LsmHandle* h);   // overlap depth declared by lsm_band_overlap_config (0 = none)
-namespace lsm { void i2oe_workspace_free(I2oeWorkspace* w); }   // lsm_i2oe.hip
+namespace lsm { void i2oe_workspace_free(I2oeWorkspace* w); }   // lsm_i2oe.hip: delete, where the type is complete
 namespace lsm {   // lsm_quad.hip (compiled through lsm_reinit.hip): quadrature results
 struct QuadObject;
 int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3],

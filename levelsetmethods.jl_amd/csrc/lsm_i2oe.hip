@@ -346,22 +346,14 @@ __global__ void __launch_bounds__(I2_THREADS) i2oe_store_kernel(const I2Args a) 
 }
 
 struct I2oeWorkspace {
-    double* buf = nullptr;       // solver vectors + face arrays
-    size_t cap = 0;              // doubles
-    double* partial = nullptr;   // 3 · I2_MAXB
-    I2State* st = nullptr;
-    I2State* h_st = nullptr;     // pinned
+    DevBuf<double> buf;          // solver vectors + face arrays
+    DevBuf<double> partial;      // 3 · I2_MAXB
+    DevBuf<I2State> st;
+    PinnedBuf<I2State> h_st;
     int last_iters = 0;          // iterations of the last solve: the size of the next call's first chunk
 };
 
-void i2oe_workspace_free(I2oeWorkspace* w) {
-    if (!w) return;
-    if (w->buf) (void)hipFree(w->buf);
-    if (w->partial) (void)hipFree(w->partial);
-    if (w->st) (void)hipFree(w->st);
-    if (w->h_st) (void)hipHostFree(w->h_st);
-    delete w;
-}
+void i2oe_workspace_free(I2oeWorkspace* w) { delete w; }
 
 }  // namespace lsm
 
@@ -464,16 +456,13 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
     if (!h->i2oe_ws) h->i2oe_ws = new I2oeWorkspace();
     I2oeWorkspace& W = *h->i2oe_ws;
     const size_t need = 9 * (size_t)nn + (size_t)nf_total;
-    if (W.cap < need) {
-        if (W.buf) { I2_HIP(h, hipStreamSynchronize(h->stream)); (void)hipFree(W.buf); W.buf = nullptr; W.cap = 0; }
-        I2_HIP(h, hipMalloc(&W.buf, need * sizeof(double)));
-        W.cap = need;
+    if (W.buf.cap < need * sizeof(double)) {
+        if (W.buf) I2_HIP(h, hipStreamSynchronize(h->stream));
+        I2_HIP(h, W.buf.alloc(need * sizeof(double)));
     }
-    if (!W.st) {
-        I2_HIP(h, hipMalloc(&W.partial, 3 * I2_MAXB * sizeof(double)));
-        I2_HIP(h, hipMalloc(&W.st, sizeof(I2State)));
-        I2_HIP(h, hipHostMalloc(&W.h_st, sizeof(I2State), hipHostMallocDefault));
-    }
+    if (!W.partial) I2_HIP(h, W.partial.alloc(3 * I2_MAXB * sizeof(double)));
+    if (!W.st) I2_HIP(h, W.st.alloc(sizeof(I2State)));
+    if (!W.h_st) I2_HIP(h, W.h_st.alloc(sizeof(I2State)));
     double* b = W.buf;
     a.x = b; a.r = b + nn; a.rh = b + 2 * nn; a.s = b + 3 * nn; a.t = b + 4 * nn;
     a.p[0] = b + 5 * nn; a.p[1] = b + 6 * nn; a.v[0] = b + 7 * nn; a.v[1] = b + 8 * nn;
@@ -510,7 +499,7 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
         I2_HIP(h, hipGetLastError());
         I2_HIP(h, hipMemcpyAsync(W.h_st, W.st, sizeof(I2State), hipMemcpyDeviceToHost, st));
         I2_HIP(h, hipStreamSynchronize(st));
-        if (W.h_st->status != I2_RUN || enq >= max_iters) break;
+        if (W.h_st.p->status != I2_RUN || enq >= max_iters) break;
         chunk = std::min(2 * chunk, 64);
     }
     const I2State S = *W.h_st;

@@ -27,7 +27,7 @@
 #include <cmath>
 #include <vector>
 
-#include "lsm_internal.h"
+#include "lsm_handle.h"
 
 namespace lsm {
 
@@ -1371,30 +1371,6 @@ int interp_run(int ndim, const int n[3], const int goff[3], long long s1, long l
     else hipLaunchKernelGGL(interp_points_kernel<6>, dim3(gb), dim3(128), 0, stream, a, npts, pts, val, grad, hess);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
-
-// a device buffer that only grows: re-allocated when a call needs more than it holds (the set of a NewtonSDF object is built once;
-// the workspace of reinitialize! lives on the handle and stops allocating after the first calls).  Frees itself.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;            // bytes
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    operator T*() const { return p; }
-    hipError_t alloc(size_t bytes) {
-        release();
-        const hipError_t e = hipMalloc((void**)&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    hipError_t grow(size_t bytes) { return p && cap >= bytes ? hipSuccess : alloc(bytes + bytes / 4 + 256); }   // headroom: the band's size drifts
-    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 // ---- the interface samples of a field and the structures that index them (candidate cells, samples per cell, occupancy
 // bits and blocks): built once per reinitialize! call, or kept in a NewtonSDF object for point queries
