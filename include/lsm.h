@@ -497,11 +497,14 @@ int lsm_reinitialize(LsmHandle* h, void* phi, const void* mask, void* work, int 
  * created; every handle starts from those values and lsm_set_tuning changes one handle's (tests and A/B measurements flip
  * them between launches).  None of them changes a result beyond what its description says; the whole GPU test suite passes
  * under each.  Unknown names are refused.  (Experiments that were measured and lost have no switch: their record is DESIGN.md.)
+ * The four launch-geometry switches (LSM_STAGE_TAIL, LSM_STAGE_MC, LSM_STAGE_MC2: 0 .. 65536; LSM_STAGE_TAIL_DYN: 0 .. 1000) take
+ * every value of their range — a chunk of one plane included — with the same results (tests/test_gpu_stage_geometry.py);
+ * lsm_set_tuning refuses a value outside it with LSM_ERR_INVALID, and such a value in the environment leaves the default.
  *
  *   name                    default  meaning
  *   LSM_STAGE_TAIL              16   planes per chunk of the graded tail of a dense 3-D stage launch (0: no tail)
  *   LSM_STAGE_TAIL_DYN          25   % spare workgroups of the dynamic tail (0: the static tail)
- *   LSM_STAGE_MC                 0   planes per march chunk in 3-D (0: 64, shorter on small grids)
+ *   LSM_STAGE_MC                 0   planes per march chunk in 3-D, the pair kernels included (0: 64, shorter on small grids)
  *   LSM_STAGE_MC2                0   rows per march chunk in 2-D (0: 8)
  *   LSM_PAIRS                    1   two nodes per thread for dense single-term stages (0: one node per thread)
  *   LSM_STAGE_GENERIC            0   general stage kernels instead of the plain variants (diagnostic: same results)

@@ -79,10 +79,12 @@ const LsmTuning& lsm_tuning_env() {
     static const LsmTuning t = [] {
         LsmTuning u;
         auto flag = [](const char* n) { const char* v = getenv(n); return v ? (*v && atoi(v) == 0 && v[0] == '0' ? 0 : 1) : 0; };
-        u.stage_tail = env_int("LSM_STAGE_TAIL", 16);
-        u.stage_tail_dyn = env_int("LSM_STAGE_TAIL_DYN", 25);
-        u.stage_mc = env_int("LSM_STAGE_MC", 0);
-        u.stage_mc2 = env_int("LSM_STAGE_MC2", 0);
+        // the launch-geometry switches: a value outside lsm_set_tuning's range (tuning_max) leaves the default
+        auto ranged = [](const char* n, int dflt, int hi) { const int v = env_int(n, dflt); return v < 0 || v > hi ? dflt : v; };
+        u.stage_tail = ranged("LSM_STAGE_TAIL", 16, 65536);
+        u.stage_tail_dyn = ranged("LSM_STAGE_TAIL_DYN", 25, 1000);
+        u.stage_mc = ranged("LSM_STAGE_MC", 0, 65536);
+        u.stage_mc2 = ranged("LSM_STAGE_MC2", 0, 65536);
         u.pairs = env_int("LSM_PAIRS", 1);
         u.stage_generic = flag("LSM_STAGE_GENERIC");
         u.xredirect = env_int("LSM_XREDIRECT", 1);
@@ -116,6 +118,13 @@ int* lsm_tuning_field(LsmTuning& t, const char* name) {
         if (strcmp(e.n, name) == 0) return e.p;
     return nullptr;
 }
+// the launch-geometry switches take what the launch arithmetic is written for (include/lsm.h): chunk lengths 0 .. 65536,
+// the dynamic tail's spare workgroups 0 .. 1000 %.  Every other switch is a flag or has its own rule.
+static int tuning_max(const LsmTuning& t, const int* p) {
+    if (p == &t.stage_mc || p == &t.stage_mc2 || p == &t.stage_tail) return 65536;
+    if (p == &t.stage_tail_dyn) return 1000;
+    return 0;
+}
 }  // namespace lsm
 
 // also runs on lsm_create's failure paths, where the streams may not exist yet; the buffers free themselves after this
@@ -135,6 +144,8 @@ int lsm_set_tuning(LsmHandle* h, const char* name, int value) {
     int* p = lsm_tuning_field(h->tune, name);
     if (!p) return fail(h, LSM_ERR_INVALID, std::string("lsm_set_tuning: no such switch: ") + (name ? name : "(null)"));
     if (p == &h->tune.layout_align) return fail(h, LSM_ERR_INVALID, "lsm_set_tuning: LSM_LAYOUT_ALIGN is fixed when the handle is created (environment only)");
+    if (const int hi = lsm::tuning_max(h->tune, p); hi > 0 && (value < 0 || value > hi))
+        return fail(h, LSM_ERR_INVALID, std::string("lsm_set_tuning: ") + name + " must be in 0.." + std::to_string(hi));
     *p = value;
     h->no_lists = h->tune.band_no_lists != 0;
     h->band_bytes = h->tune.band_bytes != 0;

@@ -1226,7 +1226,8 @@ bool launch_pairs(const StageArgs& a, hipStream_t s) {
     b.nb[0] = (a.n[0] + 2 * TX - 1) / (2 * TX);
     b.nb[1] = (a.n[1] + TY - 1) / TY;
     int mc = MC;
-    while (mc > 8 && (long long)b.nb[0] * b.nb[1] * ((a.me - a.mb + mc - 1) / mc) < 2048) mc /= 2;
+    if (a.tune->stage_mc > 0) mc = a.tune->stage_mc;                           // LSM_STAGE_MC: that chunk length, as in launch_tiled
+    else while (mc > 8 && (long long)b.nb[0] * b.nb[1] * ((a.me - a.mb + mc - 1) / mc) < 2048) mc /= 2;
     b.mc = mc;
     b.nb[2] = (a.me - a.mb + mc - 1) / mc;
     b.nbig = 0; b.mc_tail = 0; b.tail_wgs = 0;

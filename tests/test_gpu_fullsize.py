@@ -1,5 +1,7 @@
-"""Parity at BASELINE.json's FULL sizes through size-independent properties (the oracle needs
-minutes per step at 512³, so here the checks are analytic identities of the scheme itself):
+"""Parity at BASELINE.json's FULL sizes through size-independent properties — analytic identities of the
+scheme itself, which need no reference run.  (The oracle needs minutes per 512³ step on ONE thread; it is
+OpenMP-parallel behind `oracle.set_threads`, and tests/test_gpu_stage_geometry.py compares the 512³ headline
+step and the stage kernels' large-grid launch shapes with it directly.)  Here:
 
   * a linear field is differentiated exactly by every scheme: one RK3 step of advection with a
     constant velocity gives ϕ - Δt u·∇ϕ to rounding, Eikonal/NormalMotion see |∇ϕ| exactly,
