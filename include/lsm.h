@@ -392,6 +392,22 @@ int lsm_quad_read(LsmQuad* s, void* cells, void* offsets, void* coords, void* we
 int lsm_quad_total(LsmQuad* s, double* total);
 void lsm_quad_destroy(LsmQuad* s);
 
+/* ---- isosurface(ϕ, level): the interface {ϕ = level} as an indexed mesh — what export_surface_mesh gets from marching
+ *      cubes over values(ϕ) (ext/MMGSurfaceExt.jl:48-50) and what ext/MakieExt.jl draws (contour!(…; levels = [0]) in
+ *      2-D, an iso-volume in 3-D).  Marching simplices on the Freudenthal subdivision of every cell (2 triangles in 2-D,
+ *      6 tetrahedra in 3-D): a watertight, consistently oriented mesh of the zero set of the
+ *      piecewise-linear interpolant with shared vertices; normals point from ϕ < level to ϕ >= level.  phi: a dense field
+ *      (mask NULL) or a band field with its mask (the cells whose corners are all band nodes); only the interior is read:
+ *      no ghost fill, stale ghosts do not matter.  2-D and 3-D, single device, level finite; an empty result is LSM_OK.
+ *      lsm_iso_create: counts[2] := {vertices, elements}.  lsm_iso_read copies into device buffers (each may be NULL):
+ *      vertices nv x ndim doubles (point-major), ordered by the grid node that owns the vertex's edge (axis 0 fastest);
+ *      elements ne x ndim int64, 0-based vertex numbers (segments in 2-D, triangles in 3-D), ordered by cell.
+ *      Synchronous. */
+typedef struct LsmIso LsmIso;
+int lsm_iso_create(LsmHandle* h, const void* phi, const void* mask, double level, LsmIso** out, int64_t* counts);
+int lsm_iso_read(LsmIso* s, void* vertices, void* elements);
+void lsm_iso_destroy(LsmIso* s);
+
 /* ---- NarrowBandMeshField (src/meshfield.jl:314-588) on the device.
  *      The band is a byte mask (1 = active node) over the same padded index space as the values
  *      (allocate LsmLayout.total bytes; ghost entries stay 0).  Values stay in the dense padded array.

@@ -500,6 +500,41 @@ function quadrature_arrays(ϕ::ROCMeshField; interpolation_order, quadrature_ord
     end
 end
 
+# isosurface: the interface {ϕ = level} as an indexed mesh (include/lsm.h, lsm_iso_*): vertices ndim x nv, elements ndim x ne
+# with 0-based vertex numbers (segments in 2-D, triangles in 3-D), both on the device.  `mask`: a band field's byte mask.
+function isosurface_arrays(ϕ::ROCMeshField; level = 0.0, mask = nothing)
+    out, c = Ref{Ptr{Cvoid}}(), zeros(Int64, 2)
+    _check(ϕ.h.ptr, ccall((:lsm_iso_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), mask === nothing ? C_NULL : pointer(mask), level, out, c), "lsm_iso_create")
+    s = out[]
+    try
+        nv, ne = c
+        vertices, elements = ROCMatrix{Float64}(undef, ndims(ϕ), nv), ROCMatrix{Int64}(undef, ndims(ϕ), ne)
+        _check(ϕ.h.ptr, ccall((:lsm_iso_read, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), s, pointer(vertices), pointer(elements)), "lsm_iso_read")
+        return (; vertices, elements)
+    finally
+        ccall((:lsm_iso_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), s)
+    end
+end
+
+# export_surface_mesh(ϕ, output) (ext/MMGSurfaceExt.jl:35-80) up to the remesher: the Medit .mesh file the reference hands to mmgs
+# (_write_3D_triangular_mesh, :82-102), from the device's mesh.  The mmgs pass is not part of this library.
+function LSM.export_surface_mesh(ϕ::ROCMeshField, output::String; level = 0.0, hgrad = nothing, hmin = nothing, hmax = nothing, hausd = nothing)
+    ndims(ϕ) == 3 || throw(ArgumentError("export_mesh of $(ndims(ϕ)) dimensional level-set not supported."))
+    all(isnothing, (hgrad, hmin, hmax, hausd)) ||
+        error("export_surface_mesh: the mmgs remeshing pass is not part of this library; the file written without hgrad, hmin, hmax, hausd is its input")
+    m = isosurface_arrays(ϕ; level)
+    vertices, triangles = Array(m.vertices), Array(m.elements)
+    open(output, "w") do io
+        println(io, "MeshVersionFormatted 1\nDimension 3\n\nVertices\n", size(vertices, 2))
+        foreach(v -> println(io, v[1], ' ', v[2], ' ', v[3], " 1"), eachcol(vertices))
+        println(io, "\nTriangles\n", size(triangles, 2))
+        foreach(t -> println(io, t[1] + 1, ' ', t[2] + 1, ' ', t[3] + 1, " 1"), eachcol(triangles))
+        println(io, "\nEnd")
+    end
+    return output
+end
+
 # reinitialize!(ϕ; ...) (src/reinitializer.jl:12-42)
 function LSM.reinitialize!(ϕ::ROCMeshField; order = 3, upsample = 2, maxiters = 20, xtol = nothing, ftol = nothing)
     xt, ft = something(xtol, sqrt(eps(Float64))), something(ftol, sqrt(eps(Float64)))

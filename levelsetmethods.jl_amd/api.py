@@ -2049,3 +2049,99 @@ def integrate(f, q, chunk=1 << 16):
         x, w = q._full_nodes(q.full_cells[a:a + chunk])
         s += float(np.dot(np.asarray(f(x), dtype=np.float64), w))
     return s
+
+
+# ----------------------------------------------------------------------------- interface meshes (ext/MMGSurfaceExt.jl, ext/MakieExt.jl)
+
+_REMESH_MSG = ("export_surface_mesh(…; {name}): the mmgs remeshing pass (mmgs_O3 of ext/MMGSurfaceExt.jl) is not part of this library; "
+               "the file written without these keywords is its input")
+
+
+class InterfaceMesh:
+    """isosurface(…)'s result: the interface {ϕ = level} as an indexed mesh.  `vertices` (nv, N) float64, `elements` (ne, N)
+    int64, 0-based: segments in 2-D, triangles in 3-D, oriented so that a triangle's (v1 − v0) × (v2 − v0), a segment's
+    (Δy, −Δx), points from ϕ < level to ϕ >= level.  `mesh`: the grid; `level`; len() = ne."""
+
+    def __init__(self, vertices, elements, mesh=None, level=0.0):
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+        self.elements = np.ascontiguousarray(elements, dtype=np.int64)
+        self.mesh, self.level = mesh, float(level)
+
+    @property
+    def ndim(self):
+        return int(self.vertices.shape[1])
+
+    def __len__(self):
+        return int(self.elements.shape[0])
+
+    def measure(self):
+        """total length (2-D) or area (3-D) of the elements, computed on the host"""
+        if not len(self):
+            return 0.0
+        p = self.vertices[self.elements]
+        if self.ndim == 2:
+            return float(np.hypot(*(p[:, 1] - p[:, 0]).T).sum())
+        return float(0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1).sum())
+
+    def __repr__(self):
+        kind = "segments" if self.ndim == 2 else "triangles"
+        return f"InterfaceMesh in ℝ{_superscript(self.ndim)}: {len(self.vertices)} vertices, {len(self)} {kind}, level = {_jl_float(self.level)}"
+
+
+def isosurface(phi, level=0.0):
+    """The interface {ϕ = level} of a device field as an indexed mesh, extracted on the device: marching
+    simplices on the Freudenthal subdivision of every cell — watertight, consistently oriented, shared vertices.  What
+    export_surface_mesh gets from marching cubes (ext/MMGSurfaceExt.jl:48-50) and ext/MakieExt.jl draws.  ϕ: a ROCMeshField, a
+    ROCNarrowBandMeshField (the cells whose corners are all band nodes) or a LevelSetEquation (its current_state()).  Only the
+    interior is read.  Returns an InterfaceMesh."""
+    if isinstance(phi, LevelSetEquation):
+        phi = phi.current_state()
+    if not isinstance(phi, ROCMeshField):
+        raise TypeError("isosurface takes a device field (ROCMeshField / ROCNarrowBandMeshField) or a LevelSetEquation, "
+                        f"not {type(phi).__name__}")
+    N = phi.mesh.ndim
+    if N == 1:
+        raise ValueError("isosurface of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    b = phi.backend
+    if getattr(b, "slab", None) is not None:
+        raise ValueError("isosurface of a slab-decomposed field (a field with a comm) is not supported")
+    level = float(level)
+    if not math.isfinite(level):
+        raise ValueError("isosurface: level must be finite")
+    mask = phi.mask if isinstance(phi, ROCNarrowBandMeshField) else None
+    h, counts = b.iso_create(phi.buf, mask, level)
+    try:
+        verts, elems = b.iso_read(h, counts)
+        return InterfaceMesh(verts.cpu().numpy(), elems.cpu().numpy(), phi.mesh, level)
+    finally:
+        b.iso_destroy(h)
+
+
+def _write_3D_triangular_mesh(path, vertices, triangles):
+    """ext/MMGSurfaceExt.jl:82-102: a Medit .mesh file of 0-based triangles (written 1-based), every reference 1"""
+    with open(path, "w") as f:
+        f.write("MeshVersionFormatted 1\nDimension 3\n\nVertices\n")
+        f.write(f"{len(vertices)}\n")
+        f.writelines(f"{_jl_float(x)} {_jl_float(y)} {_jl_float(z)} 1\n" for x, y, z in np.asarray(vertices, dtype=np.float64).tolist())
+        f.write("\nTriangles\n")
+        f.write(f"{len(triangles)}\n")
+        f.writelines(f"{i + 1} {j + 1} {k + 1} 1\n" for i, j, k in np.asarray(triangles, dtype=np.int64).tolist())
+        f.write("\nEnd\n")
+
+
+def export_surface_mesh(phi_or_eq, output, level=0.0, hgrad=None, hmin=None, hmax=None, hausd=None):
+    """export_surface_mesh(ϕ, output; hgrad, hmin, hmax, hausd) (ext/MMGSurfaceExt.jl:35-80) up to the remesher: the zero
+    contour of a 3-D field (a device field or a LevelSetEquation; beyond the reference, also an InterfaceMesh already extracted,
+    which makes the writer usable without a device) written as the Medit
+    .mesh file the reference hands to mmgs.  The remeshing keywords raise NotImplementedError.  Returns `output`."""
+    if isinstance(phi_or_eq, LevelSetEquation):
+        phi_or_eq = phi_or_eq.current_state()
+    N = phi_or_eq.ndim if isinstance(phi_or_eq, InterfaceMesh) else getattr(getattr(phi_or_eq, "mesh", None), "ndim", None)
+    if N is not None and N != 3:
+        raise ValueError(f"export_mesh of {N} dimensional level-set not supported.")
+    for name, value in (("hgrad", hgrad), ("hmin", hmin), ("hmax", hmax), ("hausd", hausd)):
+        if value is not None:
+            raise NotImplementedError(_REMESH_MSG.format(name=name))
+    m = phi_or_eq if isinstance(phi_or_eq, InterfaceMesh) else isosurface(phi_or_eq, level)
+    _write_3D_triangular_mesh(output, m.vertices, m.elements)
+    return output

@@ -301,6 +301,25 @@ class HipBackend:
     def quad_destroy(self, quad):
         self.lib.lsm_quad_destroy(quad)
 
+    # ---- interface meshes (lsm_iso_*)
+    def iso_create(self, phi, mask, level):
+        """returns (result handle, (vertices, elements))"""
+        out, cnt = C.c_void_p(), (C.c_int64 * 2)()
+        L.check(self.h, self.lib.lsm_iso_create(self.h, self.ptr(phi), self.ptr(mask), float(level), C.byref(out), cnt), "lsm_iso_create")
+        return out, tuple(int(v) for v in cnt)
+
+    def iso_read(self, iso, counts):
+        """the result's device arrays: vertices (nv, N) float64, elements (ne, N) int64"""
+        t, N = self.torch, self.ndim
+        nv, ne = counts
+        verts = t.empty((nv, N), dtype=t.float64, device=self.device)
+        elems = t.empty((ne, N), dtype=t.int64, device=self.device)
+        L.check(self.h, self.lib.lsm_iso_read(iso, self.ptr(verts), self.ptr(elems)), "lsm_iso_read")
+        return verts, elems
+
+    def iso_destroy(self, iso):
+        self.lib.lsm_iso_destroy(iso)
+
     def extend_along_normals(self, F, phi, frozen, nb_iters, cfl, interface_band, min_norm):
         work = [self.alloc()] + [self.alloc_side() for _ in range(self.ndim)]   # F staging + the normal components
         w = [self.ptr(x) for x in work] + [None] * (4 - len(work))

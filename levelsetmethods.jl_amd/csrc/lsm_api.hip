@@ -1746,6 +1746,40 @@ void lsm_quad_destroy(LsmQuad* s) {
     delete s;
 }
 
+// isosurface (ext/MMGSurfaceExt.jl:48-50, ext/MakieExt.jl): build once, copy the vertices and the elements out
+struct LsmIso { LsmHandle* h; IsoObject* o; };
+int lsm_iso_create(LsmHandle* h, const void* phi, const void* mask, double level, LsmIso** out, int64_t* counts) {
+    if (!h || !phi || !out) return h ? fail(h, LSM_ERR_INVALID, "lsm_iso_create: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_iso_create: a 1-dimensional field has no interface mesh (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_iso_create: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    if (!std::isfinite(level)) return fail(h, LSM_ERR_INVALID, "lsm_iso_create: level must be finite");
+    double lc[3] = {0, 0, 0};
+    for (int d = 0; d < N; ++d) lc[d] = h->grid.lc[d];
+    const char* err = nullptr;
+    IsoObject* o = nullptr;
+    long long c[2] = {0, 0};
+    const int r = iso_build(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, level, phi, is_f32(h), (const unsigned char*)mask,
+                            h->stream, &o, c, &err);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_iso_create");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_iso_create");
+    *out = new LsmIso{h, o};
+    if (counts) { counts[0] = c[0]; counts[1] = c[1]; }
+    return LSM_OK;
+}
+int lsm_iso_read(LsmIso* s, void* vertices, void* elements) {
+    if (!s) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (iso_read(s->o, (double*)vertices, (long long*)elements, &err)) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_iso_read");
+    return LSM_OK;
+}
+void lsm_iso_destroy(LsmIso* s) {
+    if (!s) return;
+    iso_free(s->o);
+    delete s;
+}
+
 int lsm_cfl_cache(LsmHandle* h, int enable) {
     if (!h) return LSM_ERR_INVALID;
     h->cfl_cache_on = enable != 0;
