@@ -408,6 +408,22 @@ int lsm_iso_create(LsmHandle* h, const void* phi, const void* mask, double level
 int lsm_iso_read(LsmIso* s, void* vertices, void* elements);
 void lsm_iso_destroy(LsmIso* s);
 
+/* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
+ *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
+ *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at
+ *      lsm_iso's cut vertices, without Steiner points: a conforming mesh of triangles (2-D) or tetrahedra
+ *      (3-D) of non-negative signed volume whose boundary inside the box is exactly lsm_iso's mesh.  phi: a dense field; a
+ *      band mask is refused (a band does not hold the interior); only the interior of phi is read: no ghost fill.  2-D and
+ *      3-D, single device, level finite; an empty result is LSM_OK.  lsm_vol_create: counts[3] := {vertices, elements,
+ *      interface elements}.  lsm_vol_read copies into device buffers (each may be NULL): vertices nv x ndim doubles
+ *      (point-major), ordered by the grid node that owns them (axis 0 fastest; the node itself if inside, then the cut
+ *      vertices of its edges); elements ne x (ndim + 1) int64, 0-based vertex numbers, ordered by cell; interface ni x ndim
+ *      int64: lsm_iso's elements, in its order and orientation, in this mesh's vertex numbers.  Synchronous. */
+typedef struct LsmVol LsmVol;
+int lsm_vol_create(LsmHandle* h, const void* phi, const void* mask, double level, LsmVol** out, int64_t* counts);
+int lsm_vol_read(LsmVol* s, void* vertices, void* elements, void* interface_elements);
+void lsm_vol_destroy(LsmVol* s);
+
 /* ---- NarrowBandMeshField (src/meshfield.jl:314-588) on the device.
  *      The band is a byte mask (1 = active node) over the same padded index space as the values
  *      (allocate LsmLayout.total bytes; ghost entries stay 0).  Values stay in the dense padded array.

@@ -535,6 +535,48 @@ function LSM.export_surface_mesh(ϕ::ROCMeshField, output::String; level = 0.0, 
     return output
 end
 
+# volume_mesh: the interior {ϕ < level} as a body-fitted simplicial mesh (include/lsm.h, lsm_vol_*): vertices ndim x nv, elements
+# (ndim + 1) x ne (triangles in 2-D, tetrahedra in 3-D), interface ndim x ni (isosurface's elements), 0-based vertex numbers, all on
+# the device.  Dense fields only: a band does not hold the interior.
+function volume_mesh_arrays(ϕ::ROCMeshField; level = 0.0)
+    out, c = Ref{Ptr{Cvoid}}(), zeros(Int64, 3)
+    _check(ϕ.h.ptr, ccall((:lsm_vol_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), C_NULL, level, out, c), "lsm_vol_create")
+    s = out[]
+    try
+        nv, ne, ni = c
+        N = ndims(ϕ)
+        vertices, elements, interface = ROCMatrix{Float64}(undef, N, nv), ROCMatrix{Int64}(undef, N + 1, ne), ROCMatrix{Int64}(undef, N, ni)
+        _check(ϕ.h.ptr, ccall((:lsm_vol_read, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            s, pointer(vertices), pointer(elements), pointer(interface)), "lsm_vol_read")
+        return (; vertices, elements, interface)
+    finally
+        ccall((:lsm_vol_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), s)
+    end
+end
+
+# export_volume_mesh(ϕ, output) (ext/MMGVolumeExt.jl) up to the remesher: the splitting of the grid's Kuhn triangulation along ϕ = level
+# that mmg2d_O3 / mmg3d_O3 -ls starts with, as a Medit .mesh file.  References: vertices 1, elements 3 (the ϕ < 0 subdomain),
+# interface 10.  The remeshing pass is not part of this library.
+function LSM.export_volume_mesh(ϕ::ROCMeshField, output::String; level = 0.0, hgrad = nothing, hmin = nothing, hmax = nothing, hausd = nothing)
+    N = ndims(ϕ)
+    N in (2, 3) || throw(ArgumentError("export_mesh of $N dimensional level-set not supported."))
+    all(isnothing, (hgrad, hmin, hmax, hausd)) ||
+        error("export_volume_mesh: the mmg2d_O3 / mmg3d_O3 remeshing pass is not part of this library; the file written without hgrad, hmin, hmax, hausd is the splitting it starts from")
+    m = volume_mesh_arrays(ϕ; level)
+    vertices, elements, interface = Array(m.vertices), Array(m.elements), Array(m.interface)
+    open(output, "w") do io
+        println(io, "MeshVersionFormatted 1\nDimension ", N, "\n\nVertices\n", size(vertices, 2))
+        foreach(v -> println(io, join(v, ' '), " 1"), eachcol(vertices))
+        println(io, "\n", N == 2 ? "Triangles" : "Tetrahedra", "\n", size(elements, 2))
+        foreach(t -> println(io, join(t .+ 1, ' '), " 3"), eachcol(elements))
+        println(io, "\n", N == 2 ? "Edges" : "Triangles", "\n", size(interface, 2))
+        foreach(t -> println(io, join(t .+ 1, ' '), " 10"), eachcol(interface))
+        println(io, "\nEnd")
+    end
+    return output
+end
+
 # reinitialize!(ϕ; ...) (src/reinitializer.jl:12-42)
 function LSM.reinitialize!(ϕ::ROCMeshField; order = 3, upsample = 2, maxiters = 20, xtol = nothing, ftol = nothing)
     xt, ft = something(xtol, sqrt(eps(Float64))), something(ftol, sqrt(eps(Float64)))

@@ -2145,3 +2145,109 @@ def export_surface_mesh(phi_or_eq, output, level=0.0, hgrad=None, hmin=None, hma
     m = phi_or_eq if isinstance(phi_or_eq, InterfaceMesh) else isosurface(phi_or_eq, level)
     _write_3D_triangular_mesh(output, m.vertices, m.elements)
     return output
+
+
+# ----------------------------------------------------------------------------- meshes of the interior (ext/MMGVolumeExt.jl)
+
+_BAND_MESH_MSG = ("volume_mesh is not supported on NarrowBandMeshField: a band does not hold the interior. "
+                  "Use a full MeshField for the volume mesh, or isosurface for the interface.")
+_REMESH_VOLUME_MSG = ("export_volume_mesh(…; {name}): the remeshing pass (mmg2d_O3 / mmg3d_O3 of ext/MMGVolumeExt.jl) is not part of this "
+                      "library; the file written without these keywords is the level-set splitting it starts from")
+
+
+class DomainMesh:
+    """volume_mesh(…)'s result: the interior {ϕ < level} as a body-fitted simplicial mesh.  `vertices` (nv, N) float64;
+    `elements` (ne, N + 1) int64, 0-based: triangles in 2-D, tetrahedra in 3-D, of non-negative signed volume
+    det[v1 − v0, …]; `interface` (ni, N) int64: the elements of isosurface(ϕ, level), in its order and orientation (normals
+    pointing out of the mesh), in this mesh's vertex numbers.  `mesh`: the grid; `level`; len() = ne."""
+
+    def __init__(self, vertices, elements, interface, mesh=None, level=0.0):
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+        self.elements = np.ascontiguousarray(elements, dtype=np.int64)
+        self.interface = np.ascontiguousarray(interface, dtype=np.int64)
+        self.mesh, self.level = mesh, float(level)
+
+    @property
+    def ndim(self):
+        return int(self.vertices.shape[1])
+
+    def __len__(self):
+        return int(self.elements.shape[0])
+
+    def measure(self):
+        """Σ signed element volumes (areas in 2-D), computed on the host"""
+        if not len(self):
+            return 0.0
+        p = self.vertices[self.elements]
+        d = p[:, 1:] - p[:, :1]
+        if self.ndim == 2:
+            return float(0.5 * (d[:, 0, 0] * d[:, 1, 1] - d[:, 0, 1] * d[:, 1, 0]).sum())
+        return float((d[:, 0] * np.cross(d[:, 1], d[:, 2])).sum() / 6.0)
+
+    def __repr__(self):
+        kind, ikind = ("triangles", "segments") if self.ndim == 2 else ("tetrahedra", "triangles")
+        return (f"DomainMesh in ℝ{_superscript(self.ndim)}: {len(self.vertices)} vertices, {len(self)} {kind}, "
+                f"{len(self.interface)} interface {ikind}, level = {_jl_float(self.level)}")
+
+
+def volume_mesh(phi, level=0.0):
+    """The interior {ϕ < level} of a dense device field as a body-fitted simplicial mesh, built on the device:
+    every simplex of the Freudenthal subdivision that the level crosses is split at isosurface's cut vertices — the first
+    phase of mmg2d_O3 / mmg3d_O3 -ls in export_volume_mesh (ext/MMGVolumeExt.jl), without the remesher.  Conforming, no Steiner
+    points, every signed volume >= 0, and the boundary inside the box is exactly isosurface(ϕ, level).  ϕ: a ROCMeshField or a
+    LevelSetEquation (its current_state()).  Only the interior of the field is read.  Returns a DomainMesh."""
+    if isinstance(phi, LevelSetEquation):
+        phi = phi.current_state()
+    if not isinstance(phi, ROCMeshField):
+        raise TypeError("volume_mesh takes a device field (ROCMeshField) or a LevelSetEquation, " f"not {type(phi).__name__}")
+    if isinstance(phi, ROCNarrowBandMeshField):
+        raise ValueError(_BAND_MESH_MSG)
+    N = phi.mesh.ndim
+    if N == 1:
+        raise ValueError("volume_mesh of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    b = phi.backend
+    if getattr(b, "slab", None) is not None:
+        raise ValueError("volume_mesh of a slab-decomposed field (a field with a comm) is not supported")
+    level = float(level)
+    if not math.isfinite(level):
+        raise ValueError("volume_mesh: level must be finite")
+    h, counts = b.vol_create(phi.buf, None, level)
+    try:
+        verts, elems, iface = b.vol_read(h, counts)
+        return DomainMesh(verts.cpu().numpy(), elems.cpu().numpy(), iface.cpu().numpy(), phi.mesh, level)
+    finally:
+        b.vol_destroy(h)
+
+
+def _write_domain_mesh(path, m):
+    """a Medit .mesh file of a DomainMesh: 0-based numbers written 1-based; references 1 (vertices), 3 (elements), 10 (interface)"""
+    N = m.ndim
+    ekind, ikind = ("Triangles", "Edges") if N == 2 else ("Tetrahedra", "Triangles")
+    with open(path, "w") as f:
+        f.write(f"MeshVersionFormatted 1\nDimension {N}\n\nVertices\n{len(m.vertices)}\n")
+        f.writelines(" ".join(_jl_float(x) for x in row) + " 1\n" for row in m.vertices.tolist())
+        f.write(f"\n{ekind}\n{len(m.elements)}\n")
+        f.writelines(" ".join(str(i + 1) for i in row) + " 3\n" for row in m.elements.tolist())
+        f.write(f"\n{ikind}\n{len(m.interface)}\n")
+        f.writelines(" ".join(str(i + 1) for i in row) + " 10\n" for row in m.interface.tolist())
+        f.write("\nEnd\n")
+
+
+def export_volume_mesh(phi_or_eq, output, level=0.0, hgrad=None, hmin=None, hmax=None, hausd=None):
+    """export_volume_mesh(ϕ, output; hgrad, hmin, hmax, hausd) (ext/MMGVolumeExt.jl) up to the remesher: the interior {ϕ < level}
+    of a 2-D or 3-D field (a dense device field or a LevelSetEquation; also a DomainMesh already built, which makes the writer
+    usable without a device) written as a Medit .mesh file, numbers formatted as export_surface_mesh formats them.  This file's
+    convention, the labels MMG's level-set mode gives its output: vertices carry reference 1; the elements (`Triangles` in 2-D,
+    `Tetrahedra` in 3-D) reference 3, the ϕ < 0 subdomain; the interface (`Edges` in 2-D, `Triangles` in 3-D) reference 10.  The
+    remeshing keywords raise NotImplementedError.  Returns `output`."""
+    if isinstance(phi_or_eq, LevelSetEquation):
+        phi_or_eq = phi_or_eq.current_state()
+    N = phi_or_eq.ndim if isinstance(phi_or_eq, DomainMesh) else getattr(getattr(phi_or_eq, "mesh", None), "ndim", None)
+    if N is not None and N not in (2, 3):
+        raise ValueError(f"export_mesh of {N} dimensional level-set not supported.")
+    for name, value in (("hgrad", hgrad), ("hmin", hmin), ("hmax", hmax), ("hausd", hausd)):
+        if value is not None:
+            raise NotImplementedError(_REMESH_VOLUME_MSG.format(name=name))
+    m = phi_or_eq if isinstance(phi_or_eq, DomainMesh) else volume_mesh(phi_or_eq, level)
+    _write_domain_mesh(output, m)
+    return output

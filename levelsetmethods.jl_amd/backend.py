@@ -320,6 +320,30 @@ class HipBackend:
     def iso_destroy(self, iso):
         self.lib.lsm_iso_destroy(iso)
 
+    # ---- meshes of the interior (lsm_vol_*)
+    def vol_create(self, phi, mask, level):
+        """returns (result handle, (vertices, elements, interface elements)); a band's mask is refused by the library"""
+        if not self.torch.is_tensor(phi) or not phi.is_cuda:
+            raise TypeError(f"vol_create takes a device buffer of this backend, not {type(phi).__name__}")
+        if self.slab is not None:     # a one-rank group's slab is the whole grid with no communicator: the library could not tell
+            raise L.LsmError("vol_create: this backend holds a slab of a decomposed grid; lsm_vol_create works on the whole grid of one device")
+        out, cnt = C.c_void_p(), (C.c_int64 * 3)()
+        L.check(self.h, self.lib.lsm_vol_create(self.h, self.ptr(phi), self.ptr(mask), float(level), C.byref(out), cnt), "lsm_vol_create")
+        return out, tuple(int(v) for v in cnt)
+
+    def vol_read(self, vol, counts):
+        """the result's device arrays: vertices (nv, N) float64, elements (ne, N + 1) int64, interface (ni, N) int64"""
+        t, N = self.torch, self.ndim
+        nv, ne, ni = counts
+        verts = t.empty((nv, N), dtype=t.float64, device=self.device)
+        elems = t.empty((ne, N + 1), dtype=t.int64, device=self.device)
+        iface = t.empty((ni, N), dtype=t.int64, device=self.device)
+        L.check(self.h, self.lib.lsm_vol_read(vol, self.ptr(verts), self.ptr(elems), self.ptr(iface)), "lsm_vol_read")
+        return verts, elems, iface
+
+    def vol_destroy(self, vol):
+        self.lib.lsm_vol_destroy(vol)
+
     def extend_along_normals(self, F, phi, frozen, nb_iters, cfl, interface_band, min_norm):
         work = [self.alloc()] + [self.alloc_side() for _ in range(self.ndim)]   # F staging + the normal components
         w = [self.ptr(x) for x in work] + [None] * (4 - len(work))

@@ -1780,6 +1780,42 @@ void lsm_iso_destroy(LsmIso* s) {
     delete s;
 }
 
+// volume_mesh (ext/MMGVolumeExt.jl up to the remesher): build once, copy the vertices, the elements and the interface elements out
+struct LsmVol { LsmHandle* h; VolObject* o; };
+int lsm_vol_create(LsmHandle* h, const void* phi, const void* mask, double level, LsmVol** out, int64_t* counts) {
+    if (!h || !phi || !out) return h ? fail(h, LSM_ERR_INVALID, "lsm_vol_create: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_vol_create: a 1-dimensional field has no volume mesh (2-D and 3-D only)");
+    if (mask) return fail(h, LSM_ERR_INVALID, "lsm_vol_create: a narrow band does not hold the interior (dense fields only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_vol_create: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    if (!std::isfinite(level)) return fail(h, LSM_ERR_INVALID, "lsm_vol_create: level must be finite");
+    double lc[3] = {0, 0, 0};
+    for (int d = 0; d < N; ++d) lc[d] = h->grid.lc[d];
+    const char* err = nullptr;
+    VolObject* o = nullptr;
+    long long c[3] = {0, 0, 0};
+    const int r = vol_build(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, level, phi, is_f32(h), h->stream, &o, c, &err);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_vol_create");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_vol_create");
+    *out = new LsmVol{h, o};
+    if (counts)
+        for (int i = 0; i < 3; ++i) counts[i] = c[i];
+    return LSM_OK;
+}
+int lsm_vol_read(LsmVol* s, void* vertices, void* elements, void* interface_elements) {
+    if (!s) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (vol_read(s->o, (double*)vertices, (long long*)elements, (long long*)interface_elements, &err))
+        return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_vol_read");
+    return LSM_OK;
+}
+void lsm_vol_destroy(LsmVol* s) {
+    if (!s) return;
+    vol_free(s->o);
+    delete s;
+}
+
 int lsm_cfl_cache(LsmHandle* h, int enable) {
     if (!h) return LSM_ERR_INVALID;
     h->cfl_cache_on = enable != 0;

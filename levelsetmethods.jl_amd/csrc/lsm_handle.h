@@ -174,3 +174,10 @@ int iso_build(int ndim, const int n[3], long long s1, long long s2, long long or
 int iso_read(IsoObject* o, double* verts, long long* elems, const char** err);
 void iso_free(IsoObject* o);
 }
+namespace lsm {   // lsm_vol.hip: meshes of the interior
+struct VolObject;
+int vol_build(int ndim, const int n[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], double level,
+              const void* phi, int f32, hipStream_t stream, VolObject** out, long long counts_out[3], const char** err);
+int vol_read(VolObject* o, double* verts, long long* elems, long long* iface, const char** err);
+void vol_free(VolObject* o);
+}
