@@ -424,6 +424,39 @@ int lsm_vol_create(LsmHandle* h, const void* phi, const void* mask, double level
 int lsm_vol_read(LsmVol* s, void* vertices, void* elements, void* interface_elements);
 void lsm_vol_destroy(LsmVol* s);
 
+/* ---- render(ϕ, camera): pictures of the interface — what ext/MakieExt.jl:142-171 draws.  3-D: volume!(ϕ; algorithm = :iso,
+ *      isovalue = level), the first hit of a ray march through the trilinear interpolant, shaded by its gradient; 2-D:
+ *      contourf! under contour! at the level, a band's active cells tinted (tests/_render_ref.py restates
+ *      every operation).  phi: a dense field (mask NULL) or a band field with its mask (a sample whose cell has a corner off
+ *      the band is void: off-band values decide nothing); only the interior is read: no ghost fill.  2-D and 3-D, single
+ *      device, level finite.
+ *      lsm_render_create builds the table of bricks (8 cells per axis: void / outside / inside / mixed, one byte each) that
+ *      lets rays step over uniform regions (3-D; nothing in 2-D) and BORROWS phi and mask: both must stay alive, and phi
+ *      unchanged, between create / refresh and the last draw that follows.  lsm_render_refresh rebuilds the table after phi (or
+ *      the band) changed in place.  Both are asynchronous on the handle's stream.
+ *      lsm_render_draw writes one picture of width x height pixels, row 0 at the top, into device buffers (each may be NULL):
+ *      rgba height x width x 4 bytes (4-byte aligned); 3-D: depth height x width doubles (distance along the unit ray, +inf
+ *      where nothing is hit) and normal height x width x 3 doubles (unit gradient at the hit, pointing to ϕ increasing, 0 where
+ *      nothing is hit); 2-D: cls height x width bytes (0 outside, 1 inside, 2 line, 3 void, 4 / 5 active band cell outside /
+ *      inside), normal unused.  Asynchronous on `stream`.
+ *      camera (3-D; may be NULL in 2-D): eye[3], forward[3] (unit), right_s[3], up_s[3], orthographic flag.  Pixel (i, j) has
+ *      sx = 2(i + 1/2)/width - 1, sy = 1 - 2(j + 1/2)/height; perspective: origin eye, direction forward + sx right_s +
+ *      sy up_s, normalised; orthographic (flag != 0): origin eye + sx right_s + sy up_s, direction forward.
+ *      style, 3-D, 9 doubles:  [0..2] colour of the surface (0..255 each), [3..5] background, [6] ambient in 0..1, [7] step:
+ *      sample spacing in units of the smallest meshsize (>= 1/1024), [8] bisections of a bracket (0..30).
+ *      style, 2-D, 23 doubles: [0] line width in pixels, [1..4] extent x0, x1, y0, y1 (x1 > x0, y1 > y0; y1 is the top row),
+ *      [5..22] rgb of the classes 0..5.
+ *      lsm_render_bricks (synchronous): dims[3] := bricks per axis (0 in 2-D); table (device, may be NULL): one byte per brick,
+ *      axis 0 fastest: bits 0..1 the state (0 void, 1 outside, 2 inside, 3 mixed), bit 2 set if rays may step over it (the
+ *      brick and its 26 neighbours in the grid have the same state, not mixed). */
+typedef struct LsmRender LsmRender;
+int lsm_render_create(LsmHandle* h, const void* phi, const void* mask, double level, LsmRender** out);
+int lsm_render_refresh(LsmRender* s);
+int lsm_render_draw(LsmRender* s, const double camera[13], int width, int height, const double style[], void* rgba, void* depth_or_cls,
+                    void* normal, void* stream);
+int lsm_render_bricks(LsmRender* s, int64_t* dims, void* table);
+void lsm_render_destroy(LsmRender* s);
+
 /* ---- NarrowBandMeshField (src/meshfield.jl:314-588) on the device.
  *      The band is a byte mask (1 = active node) over the same padded index space as the values
  *      (allocate LsmLayout.total bytes; ghost entries stay 0).  Values stay in the dense padded array.
@@ -553,7 +586,8 @@ int lsm_reinitialize(LsmHandle* h, void* phi, const void* mask, void* work, int 
  *   LSM_STATUS_SPIN              1   lsm_band_status spins on the status kernel's ticket in pinned memory (0: stream synchronise)
  *   LSM_SLAB_OVERLAP             1   slab steps update the interface planes first (read when a communicator is attached)
  *   LSM_COMM_TIMEOUT_MS      60000   how long a rank waits for its peers before LSM_ERR_COMM
- *   LSM_LAYOUT_ALIGN             1   rows of the padded layout start on 64-byte lines (environment only: fixed by lsm_create) */
+ *   LSM_LAYOUT_ALIGN             1   rows of the padded layout start on 64-byte lines (environment only: fixed by lsm_create)
+ *   LSM_RENDER_SKIP              1   lsm_render_draw: rays step over uniform bricks (0: every lattice sample is loaded; identical pictures) */
 int lsm_set_tuning(LsmHandle* h, const char* name, int value);
 int lsm_get_tuning(const LsmHandle* h, const char* name, int* value);
 

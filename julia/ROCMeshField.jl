@@ -517,6 +517,35 @@ function isosurface_arrays(ϕ::ROCMeshField; level = 0.0, mask = nothing)
     end
 end
 
+# render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
+# 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
+# step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`
+# = nothing, `style` = 23 Float64 (line width, extent, the six class colours); returns rgba and cls W x H UInt8.  `mask`: a band
+# field's byte mask.
+function render_arrays(ϕ::ROCMeshField, camera; size = (640, 480), level = 0.0, mask = nothing,
+        style = ndims(ϕ) == 3 ? Float64[70, 130, 180, 255, 255, 255, 0.25, 0.5, 6] :
+                Float64[2, ϕ.mesh.lc[1], ϕ.mesh.hc[1], ϕ.mesh.lc[2], ϕ.mesh.hc[2], 255, 255, 255, 233, 233, 233, 0, 0, 0, 255, 255, 255, 198, 217, 234, 181, 198, 214])
+    out = Ref{Ptr{Cvoid}}()
+    _check(ϕ.h.ptr, ccall((:lsm_render_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ref{Ptr{Cvoid}}),
+        ϕ.h.ptr, pointer(ϕ.buf), mask === nothing ? C_NULL : pointer(mask), level, out), "lsm_render_create")
+    r = out[]
+    try
+        W, H = size
+        rgba = ROCArray{UInt8}(undef, 4, W, H)
+        three = ndims(ϕ) == 3
+        aux = three ? ROCMatrix{Float64}(undef, W, H) : ROCMatrix{UInt8}(undef, W, H)
+        normal = three ? ROCArray{Float64}(undef, 3, W, H) : nothing
+        cam = camera === nothing ? nothing : convert(Vector{Float64}, camera)
+        GC.@preserve cam _check(ϕ.h.ptr, ccall((:lsm_render_draw, libhiplsm), Cint,
+            (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            r, cam === nothing ? Ptr{Float64}(C_NULL) : pointer(cam), W, H, style, pointer(rgba), pointer(aux), normal === nothing ? C_NULL : pointer(normal), C_NULL), "lsm_render_draw")
+        _check(ϕ.h.ptr, ccall((:lsm_sync, libhiplsm), Cint, (Ptr{Cvoid},), ϕ.h.ptr), "lsm_sync")
+        return three ? (; rgba, depth = aux, normal) : (; rgba, cls = aux)
+    finally
+        ccall((:lsm_render_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), r)
+    end
+end
+
 # export_surface_mesh(ϕ, output) (ext/MMGSurfaceExt.jl:35-80) up to the remesher: the Medit .mesh file the reference hands to mmgs
 # (_write_3D_triangular_mesh, :82-102), from the device's mesh.  The mmgs pass is not part of this library.
 function LSM.export_surface_mesh(ϕ::ROCMeshField, output::String; level = 0.0, hgrad = nothing, hmin = nothing, hmax = nothing, hausd = nothing)

@@ -135,6 +135,12 @@ _SIGS = [
     ("lsm_iso_create", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("lsm_iso_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_iso_destroy", None, [C.c_void_p]),
+    ("lsm_render_create", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_void_p)]),
+    ("lsm_render_refresh", C.c_int, [C.c_void_p]),
+    ("lsm_render_draw", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    ("lsm_render_bricks", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    ("lsm_render_destroy", None, [C.c_void_p]),
     ("lsm_vol_create", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("lsm_vol_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_vol_destroy", None, [C.c_void_p]),

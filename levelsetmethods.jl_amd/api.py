@@ -2251,3 +2251,240 @@ def export_volume_mesh(phi_or_eq, output, level=0.0, hgrad=None, hmin=None, hmax
     m = phi_or_eq if isinstance(phi_or_eq, DomainMesh) else volume_mesh(phi_or_eq, level)
     _write_domain_mesh(output, m)
     return output
+
+
+# ----------------------------------------------------------------------------- pictures (ext/MakieExt.jl:142-171)
+
+_STYLE3 = dict(color=(70, 130, 180), background=(255, 255, 255), ambient=0.25, step=0.5, bisections=6)
+_STYLE2 = dict(fill=(233, 233, 233), line=(0, 0, 0), linewidth=2.0, cell=(198, 217, 234), background=(255, 255, 255), extent=None)
+
+
+def _rgb(name, c):
+    c = tuple(int(x) for x in c)
+    if len(c) != 3 or not all(0 <= x <= 255 for x in c):
+        raise ValueError(f"render: {name} must be three integers in 0..255")
+    return c
+
+
+class Camera:
+    """Camera(eye, lookat, up = (0, 0, 1), fov = 40.0, orthographic = None): a pinhole camera at `eye` looking at `lookat`, `fov`
+    the vertical field of view in degrees; orthographic = w: parallel rays over a window w world units high.  The library sees
+    only what vectors(width, height) computes in fp64: eye, forward, right·s_x, up·s_y and the orthographic flag."""
+
+    def __init__(self, eye, lookat, up=(0.0, 0.0, 1.0), fov=40.0, orthographic=None):
+        self.eye, self.lookat, self.up = (tuple(float(x) for x in a) for a in (eye, lookat, up))
+        if not all(len(a) == 3 for a in (self.eye, self.lookat, self.up)):
+            raise ValueError("Camera: eye, lookat and up have three components")
+        self.fov = float(fov)
+        self.orthographic = None if orthographic is None else float(orthographic)
+        if not 0.0 < self.fov < 180.0:
+            raise ValueError("Camera: fov must lie in (0, 180) degrees")
+        if self.orthographic is not None and not self.orthographic > 0.0:
+            raise ValueError("Camera: the orthographic window must be positive")
+        self.vectors(1, 1)
+
+    def vectors(self, width, height):
+        """the 13 doubles of lsm_render_draw for an image of width × height pixels"""
+        eye, lookat, up = (np.asarray(a, dtype=np.float64) for a in (self.eye, self.lookat, self.up))
+        f = lookat - eye
+        nf = np.sqrt(f @ f)
+        if not nf > 0:
+            raise ValueError("Camera: eye and lookat coincide")
+        f = f / nf
+        r = np.cross(f, up)
+        nr = np.sqrt(r @ r)
+        if not nr > 1e-12 * np.sqrt(up @ up):
+            raise ValueError("Camera: up is parallel to the view direction")
+        r = r / nr
+        u = np.cross(r, f)
+        sy = np.tan(np.radians(self.fov) / 2.0) if self.orthographic is None else 0.5 * self.orthographic
+        sx = sy * (float(width) / float(height))
+        return np.concatenate([eye, f, r * sx, u * sy, [0.0 if self.orthographic is None else 1.0]])
+
+    @classmethod
+    def fit(cls, grid, direction=(1.0, 1.0, 1.0), fov=40.0):
+        """a perspective camera on the ray from the box's centre along `direction` that sees the whole box (its bounding sphere,
+        in an image at least as wide as high)"""
+        if grid.ndim != 3:
+            raise ValueError("Camera.fit takes a 3-D grid")
+        lc, hc, dirn = (np.asarray(a, dtype=np.float64) for a in (grid.lc, grid.hc, direction))
+        if not np.sqrt(dirn @ dirn) > 0:
+            raise ValueError("Camera.fit: direction must not vanish")
+        c = 0.5 * (lc + hc)
+        rad = 0.5 * np.sqrt(((hc - lc) ** 2).sum())
+        dirn = dirn / np.sqrt(dirn @ dirn)
+        dist = 1.05 * rad / np.sin(np.radians(float(fov)) / 2.0)
+        return cls(c + dist * dirn, c, (0.0, 0.0, 1.0) if abs(dirn[2]) < 0.99 else (0.0, 1.0, 0.0), fov)
+
+    def __repr__(self):
+        kind = f"fov = {_jl_float(self.fov)}°" if self.orthographic is None else f"orthographic, window {_jl_float(self.orthographic)}"
+        return f"Camera(eye = {self.eye}, lookat = {self.lookat}, up = {self.up}, {kind})"
+
+
+def _png_bytes(rgba):
+    import struct
+    import zlib
+    a = np.ascontiguousarray(rgba, dtype=np.uint8)
+    H, W = a.shape[:2]
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    rows = np.concatenate([np.zeros((H, 1), dtype=np.uint8), a.reshape(H, W * 4)], axis=1)      # filter 0 on every row
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 6, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) +
+            chunk(b"IEND", b""))
+
+
+class Image:
+    """render(…)'s result.  `rgba` (H, W, 4) uint8, row 0 at the top.  3-D: `depth` (H, W), the distance along the unit ray (inf
+    where nothing is hit), and `normal` (H, W, 3), the unit gradient at the hit (0 where nothing is hit).  2-D: `cls` (H, W) uint8:
+    0 outside, 1 inside, 2 line, 3 void, 4 / 5 active band cell outside / inside.  save(path) writes a PNG."""
+
+    def __init__(self, rgba, depth=None, normal=None, cls=None):
+        self.rgba, self.depth, self.normal, self.cls = rgba, depth, normal, cls
+
+    @property
+    def size(self):
+        return int(self.rgba.shape[1]), int(self.rgba.shape[0])
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            f.write(_png_bytes(self.rgba))
+        return path
+
+    def __repr__(self):
+        W, H = self.size
+        if self.cls is not None:
+            return f"Image {W}×{H} of a 2-dimensional level-set: {int((self.cls == 2).sum())} line pixels, {int((self.cls == 1).sum() + (self.cls == 5).sum())} inside"
+        return f"Image {W}×{H} of a 3-dimensional level-set: {int(np.isfinite(self.depth).sum())} of {W * H} rays hit"
+
+
+class Renderer:
+    """Renderer(ϕ, level = 0.0): pictures of the interface {ϕ = level} of a device field, drawn on the device —
+    what plot(ϕ) draws through ext/MakieExt.jl: in 3-D the first hit of a ray march through the trilinear interpolant
+    (volume!(…; algorithm = :iso)), in 2-D the filled contour under its line, a band's active cells tinted.  ϕ: a ROCMeshField, a
+    ROCNarrowBandMeshField or a LevelSetEquation (its current_state()); the field is referenced, not copied.  The table of bricks
+    that lets rays step over uniform regions is built here, once; draw(…) may be called any number of times; after the field
+    changed call refresh()."""
+
+    def __init__(self, phi, level=0.0):
+        self._h = None
+        self._eq = phi if isinstance(phi, LevelSetEquation) else None
+        if self._eq is not None:
+            phi = self._eq.current_state()
+        if not isinstance(phi, ROCMeshField):
+            raise TypeError("render takes a device field (ROCMeshField / ROCNarrowBandMeshField) or a LevelSetEquation, "
+                            f"not {type(phi).__name__}")
+        if phi.mesh.ndim == 1:
+            raise ValueError("render of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+        if getattr(phi.backend, "slab", None) is not None:
+            raise ValueError("render of a slab-decomposed field (a field with a comm) is not supported")
+        self.level = float(level)
+        if not math.isfinite(self.level):
+            raise ValueError("render: level must be finite")
+        self._attach(phi)
+
+    def _attach(self, phi):
+        self.close()
+        self.phi, self.backend, self.mesh = phi, phi.backend, phi.mesh
+        self._buf, self._mask = phi.buf, phi.mask if isinstance(phi, ROCNarrowBandMeshField) else None
+        self._h = self.backend.render_create(self._buf, self._mask, self.level)
+
+    def refresh(self):
+        """rebuild the bricks after the field changed (an equation's current state may live in another buffer after a step)"""
+        if self._h is None:
+            raise ValueError("Renderer: closed")
+        phi = self._eq.current_state() if self._eq is not None else self.phi
+        if phi is not self.phi or phi.buf is not self._buf or (phi.mask if isinstance(phi, ROCNarrowBandMeshField) else None) is not self._mask:
+            self._attach(phi)
+        else:
+            self.backend.render_refresh(self._h)
+        return self
+
+    def bricks(self):
+        """(state, uniform) per brick of 8 cells per axis: state 0 void, 1 outside, 2 inside, 3 mixed (3-D)"""
+        t = self.backend.render_bricks(self._h)
+        return t & 3, (t & 4) != 0
+
+    def draw(self, camera=None, size=(640, 480), want_normal=True, **style):
+        if self._h is None:
+            raise ValueError("Renderer: closed")
+        W, H = (int(s) for s in size)
+        if W <= 0 or H <= 0:
+            raise ValueError("render: size must be (width, height) with both positive")
+        three = self.mesh.ndim == 3
+        st = dict(_STYLE3 if three else _STYLE2)
+        for k, v in style.items():
+            if k not in st:
+                raise TypeError(f"render: unknown style keyword {k!r} for a {self.mesh.ndim}-D field (known: {', '.join(st)})")
+            st[k] = v
+        if three:
+            step, nb = float(st["step"]), st["bisections"]
+            if not step > 0:
+                raise ValueError("render: step must be positive")
+            if int(nb) != nb or not 0 <= int(nb) <= 30:
+                raise ValueError("render: bisections must be an integer in 0..30")
+            if not 0.0 <= float(st["ambient"]) <= 1.0:
+                raise ValueError("render: ambient must lie in 0..1")
+            if camera is None:
+                camera = Camera.fit(self.mesh)
+            if not isinstance(camera, Camera):
+                raise TypeError("render: camera must be a Camera")
+            vec = [*_rgb("color", st["color"]), *_rgb("background", st["background"]), float(st["ambient"]), step, int(nb)]
+            rgba, depth, normal = self.backend.render_draw(self._h, camera.vectors(W, H), W, H, vec, want_normal)
+            return Image(rgba.cpu().numpy(), depth=depth.cpu().numpy(), normal=None if normal is None else normal.cpu().numpy())
+        if camera is not None:
+            raise ValueError("render: a 2-D field is drawn over `extent`, not through a camera")
+        ext = st["extent"]
+        x0, x1, y0, y1 = (self.mesh.lc[0], self.mesh.hc[0], self.mesh.lc[1], self.mesh.hc[1]) if ext is None else (float(e) for e in ext)
+        if not (x1 > x0 and y1 > y0):
+            raise ValueError("render: extent must be (x0, x1, y0, y1) with x1 > x0 and y1 > y0")
+        lw = float(st["linewidth"])
+        if not lw >= 0:
+            raise ValueError("render: linewidth must not be negative")
+        fill, line, cell, bg = (_rgb(k, st[k]) for k in ("fill", "line", "cell", "background"))
+        both = tuple(int(math.floor(float(c) * float(f) / 255.0 + 0.5)) for c, f in zip(cell, fill))
+        vec = [lw, x0, x1, y0, y1, *bg, *fill, *line, *bg, *cell, *both]
+        rgba, cls, _ = self.backend.render_draw(self._h, None, W, H, vec)
+        return Image(rgba.cpu().numpy(), cls=cls.cpu().numpy())
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.render_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def render(phi, camera=None, size=(640, 480), level=0.0, **style):
+    """One picture of the interface {ϕ = level}: Renderer(ϕ, level).draw(camera, size, **style).  Style in 3-D: color, background,
+    ambient, step (sample spacing in units of min(h)), bisections; in 2-D: fill, line, linewidth (pixels), cell, background, extent."""
+    r = Renderer(phi, level)
+    try:
+        return r.draw(camera, size, **style)
+    finally:
+        r.close()
+
+
+def record_(eq, tf, pattern, every=1, dt=float("inf"), **render_kw):
+    """integrate_(eq, tf, dt) with a posthook that saves pattern.format(k) after every `every`-th step k = 1, 2, … from one
+    Renderer (the loop behind the reference README's zalesak3d.gif).  render_kw: level and draw's arguments.  Returns the paths."""
+    every = int(every)
+    if every < 1:
+        raise ValueError("record_: every must be at least 1")
+    r = Renderer(eq, render_kw.pop("level", 0.0))
+    paths, step = [], [0]
+
+    def hook(ls):
+        step[0] += 1
+        if step[0] % every == 0:
+            paths.append(r.refresh().draw(**render_kw).save(pattern.format(step[0])))
+
+    try:
+        integrate_(eq, tf, dt, posthook=hook)
+    finally:
+        r.close()
+    return paths

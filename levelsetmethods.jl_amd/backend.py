@@ -320,6 +320,46 @@ class HipBackend:
     def iso_destroy(self, iso):
         self.lib.lsm_iso_destroy(iso)
 
+    # ---- pictures (lsm_render_*)
+    def render_create(self, phi, mask, level):
+        """the renderer of a field: builds the brick table; borrows phi and mask"""
+        if getattr(self, "slab", None) is not None:
+            raise L.LsmError("render_create: this backend holds a slab of a decomposed grid; lsm_render_create works on the whole grid of one device")
+        out = C.c_void_p()
+        L.check(self.h, self.lib.lsm_render_create(self.h, self.ptr(phi), self.ptr(mask), float(level), C.byref(out)), "lsm_render_create")
+        return out
+
+    def render_refresh(self, r):
+        L.check(self.h, self.lib.lsm_render_refresh(r), "lsm_render_refresh")
+
+    def render_draw(self, r, camera, width, height, style, want_normal=True):
+        """one picture as device tensors: (rgba (H, W, 4) uint8, depth (H, W) float64 or cls (H, W) uint8, normal (H, W, 3) or None)"""
+        t = self.torch
+        W, H = int(width), int(height)
+        if W <= 0 or H <= 0:
+            raise L.LsmError("render_draw: width and height must be positive")
+        three = self.ndim == 3
+        rgba = t.empty((H, W, 4), dtype=t.uint8, device=self.device)
+        aux = t.empty((H, W), dtype=t.float64 if three else t.uint8, device=self.device)
+        normal = t.empty((H, W, 3), dtype=t.float64, device=self.device) if three and want_normal else None
+        cam = None if camera is None else (C.c_double * 13)(*[float(x) for x in camera])
+        sty = (C.c_double * len(style))(*[float(x) for x in style])
+        L.check(self.h, self.lib.lsm_render_draw(r, cam, W, H, sty, self.ptr(rgba), self.ptr(aux), self.ptr(normal), None), "lsm_render_draw")
+        return rgba, aux, normal
+
+    def render_bricks(self, r):
+        """the brick table (nb0, nb1, nb2) uint8 on the host: bits 0..1 state, bit 2 uniform"""
+        t = self.torch
+        dims = (C.c_int64 * 3)()
+        L.check(self.h, self.lib.lsm_render_bricks(r, dims, None), "lsm_render_bricks")
+        nb = tuple(int(d) for d in dims)
+        tab = t.empty(max(nb[0] * nb[1] * nb[2], 1), dtype=t.uint8, device=self.device)
+        L.check(self.h, self.lib.lsm_render_bricks(r, dims, self.ptr(tab)), "lsm_render_bricks")
+        return tab.cpu().numpy()[:nb[0] * nb[1] * nb[2]].reshape(nb, order="F")
+
+    def render_destroy(self, r):
+        self.lib.lsm_render_destroy(r)
+
     # ---- meshes of the interior (lsm_vol_*)
     def vol_create(self, phi, mask, level):
         """returns (result handle, (vertices, elements, interface elements)); a band's mask is refused by the library"""

@@ -100,6 +100,7 @@ const LsmTuning& lsm_tuning_env() {
         u.comm_timeout_ms = env_int("LSM_COMM_TIMEOUT_MS", 60000);
         if (u.comm_timeout_ms <= 0) u.comm_timeout_ms = 60000;
         u.layout_align = env_int("LSM_LAYOUT_ALIGN", 1);
+        u.render_skip = env_int("LSM_RENDER_SKIP", 1);
         return u;
     }();
     return t;
@@ -112,7 +113,7 @@ int* lsm_tuning_field(LsmTuning& t, const char* name) {
         {"LSM_GHOST_FULL_DEPTH", &t.ghost_full_depth}, {"LSM_BAND_BRICKS", &t.band_bricks}, {"LSM_BAND_BITS", &t.band_bits},
         {"LSM_BAND_CFL_PREFETCH", &t.band_cfl_prefetch}, {"LSM_BAND_BYTES", &t.band_bytes}, {"LSM_BAND_NO_LISTS", &t.band_no_lists},
         {"LSM_STATUS_SPIN", &t.status_spin}, {"LSM_SLAB_OVERLAP", &t.slab_overlap}, {"LSM_COMM_TIMEOUT_MS", &t.comm_timeout_ms},
-        {"LSM_LAYOUT_ALIGN", &t.layout_align},
+        {"LSM_LAYOUT_ALIGN", &t.layout_align}, {"LSM_RENDER_SKIP", &t.render_skip},
     };
     for (const auto& e : tab)
         if (strcmp(e.n, name) == 0) return e.p;
@@ -1813,6 +1814,74 @@ int lsm_vol_read(LsmVol* s, void* vertices, void* elements, void* interface_elem
 void lsm_vol_destroy(LsmVol* s) {
     if (!s) return;
     vol_free(s->o);
+    delete s;
+}
+
+// render (ext/MakieExt.jl:142-171): the brick table once, then any number of pictures
+struct LsmRender { LsmHandle* h; RenderObject* o; };
+int lsm_render_create(LsmHandle* h, const void* phi, const void* mask, double level, LsmRender** out) {
+    if (!h || !phi || !out) return h ? fail(h, LSM_ERR_INVALID, "lsm_render_create: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_render_create: a 1-dimensional field has no picture (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_render_create: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    if (!std::isfinite(level)) return fail(h, LSM_ERR_INVALID, "lsm_render_create: level must be finite");
+    double lc[3] = {0, 0, 0}, hc[3] = {1, 1, 1};
+    for (int d = 0; d < N; ++d) { lc[d] = h->grid.lc[d]; hc[d] = h->grid.hc[d]; }
+    const char* err = nullptr;
+    RenderObject* o = nullptr;
+    const int r = render_build(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, hc, h->h, level, phi, is_f32(h),
+                               (const unsigned char*)mask, h->stream, &o, &err);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_render_create");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_render_create");
+    *out = new LsmRender{h, o};
+    return LSM_OK;
+}
+int lsm_render_refresh(LsmRender* s) {
+    if (!s) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (render_refresh(s->o, &err)) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_render_refresh");
+    return LSM_OK;
+}
+int lsm_render_draw(LsmRender* s, const double camera[13], int width, int height, const double style[], void* rgba, void* depth_or_cls,
+                    void* normal, void* stream) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    if (!style) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: null style");
+    if (width <= 0 || height <= 0) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: width and height must be positive");
+    if (h->grid.ndim == 3) {
+        if (!camera) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: a 3-D field needs a camera");
+        for (int i = 0; i < 13; ++i)
+            if (!std::isfinite(camera[i])) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: the camera must be finite");
+        for (int i = 0; i < 9; ++i)
+            if (!std::isfinite(style[i])) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: the style must be finite");
+        if (!(style[7] > 0)) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: step must be positive");
+        if (style[7] < 1.0 / 1024) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: step must be at least 1/1024 of the smallest meshsize");
+        if (!(style[8] >= 0 && style[8] <= 30) || style[8] != std::floor(style[8]))
+            return fail(h, LSM_ERR_INVALID, "lsm_render_draw: bisections must be an integer in 0..30");
+    } else {
+        for (int i = 0; i < 23; ++i)
+            if (!std::isfinite(style[i])) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: the style must be finite");
+        if (!(style[2] > style[1] && style[4] > style[3])) return fail(h, LSM_ERR_INVALID, "lsm_render_draw: the extent must have x1 > x0 and y1 > y0");
+    }
+    const char* err = nullptr;
+    const int r = render_draw(s->o, camera, width, height, style, h->tune.render_skip != 0, (unsigned char*)rgba, depth_or_cls, (double*)normal,
+                              stream ? (hipStream_t)stream : h->stream, &err);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_render_draw");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_render_draw");
+    return LSM_OK;
+}
+int lsm_render_bricks(LsmRender* s, int64_t* dims, void* table) {
+    if (!s || !dims) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    long long d[3];
+    if (render_bricks(s->o, d, (unsigned char*)table, &err)) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_render_bricks");
+    for (int i = 0; i < 3; ++i) dims[i] = d[i];
+    return LSM_OK;
+}
+void lsm_render_destroy(LsmRender* s) {
+    if (!s) return;
+    render_free(s->o);
     delete s;
 }
 

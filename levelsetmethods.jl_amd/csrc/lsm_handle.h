@@ -181,3 +181,13 @@ int vol_build(int ndim, const int n[3], long long s1, long long s2, long long or
 int vol_read(VolObject* o, double* verts, long long* elems, long long* iface, const char** err);
 void vol_free(VolObject* o);
 }
+namespace lsm {   // lsm_render.hip: pictures of the interface
+struct RenderObject;
+int render_build(int ndim, const int n[3], long long s1, long long s2, long long origin, const double lc[3], const double hc[3], const double h[3],
+                 double level, const void* phi, int f32, const unsigned char* mask, hipStream_t stream, RenderObject** out, const char** err);
+int render_refresh(RenderObject* o, const char** err);
+int render_draw(RenderObject* o, const double* cam, int W, int H, const double* style, int skip, unsigned char* rgba, void* depth_or_cls, double* normal,
+                hipStream_t stream, const char** err);
+int render_bricks(RenderObject* o, long long dims[3], unsigned char* table, const char** err);
+void render_free(RenderObject* o);
+}
