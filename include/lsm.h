@@ -408,6 +408,26 @@ int lsm_iso_create(LsmHandle* h, const void* phi, const void* mask, double level
 int lsm_iso_read(LsmIso* s, void* vertices, void* elements);
 void lsm_iso_destroy(LsmIso* s);
 
+/* ---- mesh_distance(mesh, grid, cutoff): from a mesh back to a level set — the inverse of lsm_iso_*.  phi_out[I] :=
+ *      s(I)·min(d(I), cutoff) over the interior of a dense field of the handle (the ghosts are left as they are: fill them
+ *      before a stencil reads them): d the exact Euclidean distance from node I to the nearest element, s = −1 where the mesh
+ *      winds around the node and +1 elsewhere (tests/_mdist_ref.py restates every operation).  vertices:
+ *      nverts x ndim doubles (point-major), elements: nelems x ndim int64, 0-based vertex numbers (segments in 2-D, triangles
+ *      in 3-D), both device buffers, oriented as lsm_iso_*'s (normals pointing out of the region that becomes phi < 0); the
+ *      mesh must be closed and consistently oriented.  0 < cutoff <= +inf: the work is the sum of the elements' bounding
+ *      boxes dilated by the cutoff, so a finite cutoff of a few cells is what a narrow band or a reinitialisation needs; nodes
+ *      beyond it carry ±sqrt(cutoff·cutoff).  All arithmetic is fp64; an f32 handle rounds on store.  The sign is a crossing
+ *      count along axis 0 with a half-open inclusion rule (a grid line through a shared edge or vertex is counted once); the
+ *      result is deterministic bit for bit.  stats[3] (may be NULL) := {nodes with d < cutoff, grid rows whose crossings do
+ *      not balance — non-zero: the mesh is open or inconsistently oriented and the signs along those rows mean nothing —,
+ *      elements skipped by the sign pass because their projection along axis 0 is degenerate}.  LSM_ERR_INVALID: a slab
+ *      handle, a 1-D grid, cutoff <= 0 or NaN, a vertex number outside 0..nverts-1 (checked on the device before anything is
+ *      addressed with it), a non-finite vertex.  An empty mesh is LSM_OK: phi_out = +sqrt(cutoff·cutoff).  stream: NULL = the
+ *      handle's.  The scratch arrays (8 bytes per node, 4 bytes per node and row) belong to the handle and only grow.
+ *      Synchronous. */
+int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_t nelems, const void* elements, double cutoff,
+                      void* phi_out, int64_t stats[3], void* stream);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

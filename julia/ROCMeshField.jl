@@ -517,6 +517,19 @@ function isosurface_arrays(ϕ::ROCMeshField; level = 0.0, mask = nothing)
     end
 end
 
+# mesh_distance!: ϕ := the signed distance to a closed, consistently oriented mesh, cut off at `cutoff` (include/lsm.h,
+# lsm_mesh_distance) — the inverse of isosurface_arrays.  vertices ndim x nv Float64 and elements ndim x ne Int64 with 0-based
+# vertex numbers, both on the device.  Returns (near, unbalanced, skipped); unbalanced != 0: the mesh is open or inconsistently
+# oriented as seen from that many grid rows.
+function mesh_distance!(ϕ::ROCMeshField, vertices::ROCMatrix{Float64}, elements::ROCMatrix{Int64}; cutoff = Inf)
+    stats = zeros(Int64, 3)
+    _check(ϕ.h.ptr, ccall((:lsm_mesh_distance, libhiplsm), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}),
+        ϕ.h.ptr, size(vertices, 2), pointer(vertices), size(elements, 2), pointer(elements), cutoff, pointer(ϕ.buf), stats, C_NULL), "lsm_mesh_distance")
+    stats[2] == 0 || error("mesh_distance: the mesh is not closed or not consistently oriented ($(stats[2]) grid rows see unbalanced crossings)")
+    return (; near = stats[1], unbalanced = stats[2], skipped = stats[3])
+end
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

@@ -2147,6 +2147,119 @@ def export_surface_mesh(phi_or_eq, output, level=0.0, hgrad=None, hmin=None, hma
     return output
 
 
+# ----------------------------------------------------------------------------- from a mesh back to a level set
+
+def read_mesh(path):
+    """The interface mesh of a Medit .mesh file, as an InterfaceMesh: the subset of the format this library writes
+    (export_surface_mesh, export_volume_mesh) — `Dimension`, `Vertices`, then `Triangles` (3-D) or `Edges` (2-D); numbers are
+    1-based in the file, references are ignored, other sections (the `Triangles` / `Tetrahedra` of a volume file) are skipped.
+    Runs on the host: no device is needed."""
+    with open(path) as f:
+        tok = f.read().split()
+    rows = {"Vertices": None, "Edges": 3, "Triangles": 4, "Quadrilaterals": 5, "Tetrahedra": 5, "Hexahedra": 9, "Corners": 1,
+            "RequiredVertices": 1, "Ridges": 1, "RequiredEdges": 1}
+    N, verts, found, i = None, None, {}, 0
+    while i < len(tok):
+        key = tok[i]
+        i += 1
+        if key == "End":
+            break
+        if key == "MeshVersionFormatted":
+            i += 1
+        elif key == "Dimension":
+            N = int(tok[i])
+            i += 1
+            if N not in (2, 3):
+                raise ValueError(f"read_mesh: Dimension {N} is not supported: 2-D and 3-D meshes only")
+        elif key in rows:
+            if N is None:
+                raise ValueError(f"read_mesh: {key} before Dimension")
+            count, width = int(tok[i]), rows[key] or N + 1
+            i += 1
+            body = tok[i:i + count * width]
+            if len(body) != count * width:
+                raise ValueError(f"read_mesh: the {key} section ends early")
+            i += count * width
+            if key == "Vertices":
+                verts = np.array([float(x) for x in body], dtype=np.float64).reshape(count, width)[:, :N]
+            else:
+                found[key] = np.array([int(x) for x in body], dtype=np.int64).reshape(count, width)[:, :width - 1]
+        else:
+            raise ValueError(f"read_mesh: unexpected keyword {key!r}")
+    if N is None:
+        raise ValueError("read_mesh: no Dimension")
+    if verts is None:
+        raise ValueError("read_mesh: no Vertices section")
+    kind = "Triangles" if N == 3 else "Edges"
+    elems = found.get(kind, np.zeros((0, N), dtype=np.int64)) - 1
+    if elems.size and (elems.min() < 0 or elems.max() >= len(verts)):
+        raise ValueError(f"read_mesh: a vertex number of the {kind} section lies outside 1..{len(verts)}")
+    return InterfaceMesh(verts, elems)
+
+
+def _mesh_arrays(mesh, what):
+    """(vertices (nv, N) float64, elements (ne, N) int64) of an InterfaceMesh or a (vertices, elements) pair"""
+    if isinstance(mesh, InterfaceMesh):
+        v, e = mesh.vertices, mesh.elements
+    else:
+        try:
+            v, e = mesh
+        except (TypeError, ValueError):
+            raise TypeError(f"{what}: mesh must be an InterfaceMesh or a (vertices, elements) pair, not {type(mesh).__name__}") from None
+        v, e = np.ascontiguousarray(v, dtype=np.float64), np.ascontiguousarray(e, dtype=np.int64)
+    if v.ndim != 2 or e.ndim != 2 or v.shape[1] not in (2, 3) or e.shape[1] != v.shape[1]:
+        raise ValueError(f"{what}: vertices (nv, N) and elements (ne, N) with N = 2 (segments) or 3 (triangles) are expected, "
+                         f"got shapes {v.shape} and {e.shape}")
+    return v, e
+
+
+def mesh_distance_(phi, mesh, cutoff=None):
+    """Overwrite a device field with the signed distance to a closed, consistently oriented mesh, computed on the device
+    (DESIGN.md §7.14): ϕ[I] = s·min(d, cutoff), d the exact Euclidean distance from node I to the nearest element (segments in
+    2-D, triangles in 3-D), s = −1 where the mesh winds around the node and +1 elsewhere — the inverse of isosurface.  `phi`: a
+    dense ROCMeshField or a LevelSetEquation (its current state), changed in place; `mesh`: an InterfaceMesh or a (vertices,
+    elements) pair, oriented as InterfaceMesh documents (normals pointing out of the region that becomes ϕ < 0); cutoff = None
+    means +inf.  Raises ValueError when the mesh is open or inconsistently oriented as seen from some grid line.  Returns ϕ."""
+    eq = phi if isinstance(phi, LevelSetEquation) else None
+    if eq is not None:
+        phi = eq.current_state()
+    if not isinstance(phi, ROCMeshField):
+        raise TypeError(f"mesh_distance_ takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
+    if isinstance(phi, ROCNarrowBandMeshField):
+        raise ValueError("mesh_distance_ is not supported on NarrowBandMeshField: the band is where the interface was, not where the "
+                         "mesh is. Use a full MeshField, then build the band from it.")
+    N = phi.mesh.ndim
+    if N == 1:
+        raise ValueError("mesh_distance_ of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    b = phi.backend
+    if getattr(b, "slab", None) is not None:
+        raise ValueError("mesh_distance_ of a slab-decomposed field (a field with a comm) is not supported")
+    v, e = _mesh_arrays(mesh, "mesh_distance_")
+    if v.shape[1] != N:
+        raise ValueError(f"mesh_distance_: a mesh in {v.shape[1]} dimensions cannot be measured on a {N} dimensional grid")
+    c = float("inf") if cutoff is None else float(cutoff)
+    if not c > 0:
+        raise ValueError("mesh_distance_: cutoff must be positive (None or inf: no cutoff)")
+    _, unbalanced, _ = b.mesh_distance(phi.buf, v, e, c)
+    phi.ghosts_dirty = True
+    if unbalanced:
+        raise ValueError(f"mesh_distance: the mesh is not closed or not consistently oriented ({unbalanced} grid rows see unbalanced crossings)")
+    return phi
+
+
+def mesh_distance(mesh, grid, cutoff=None, dtype=None, mode="fast", device=0):
+    """The signed distance to a closed mesh on `grid` as a host MeshField, usable as `ic=`: mesh_distance_ on a throwaway device
+    field.  `mesh`: an InterfaceMesh (read_mesh's, isosurface's) or a (vertices, elements) pair; dtype: float64 (default) or
+    float32 storage (the distance is computed in fp64 and rounded once)."""
+    ic = MeshField(np.zeros(grid.n, dtype=np.float64 if dtype is None else dtype, order="F"), grid, dtype=dtype)
+    eq = LevelSetEquation(terms=(NormalMotionTerm(0.0),), ic=ic, bc=NeumannBC(), mode=mode, device=device)
+    try:
+        vals = mesh_distance_(eq, mesh, cutoff).values()
+    finally:
+        eq.backend.close()
+    return MeshField(vals, grid, dtype=dtype)
+
+
 # ----------------------------------------------------------------------------- meshes of the interior (ext/MMGVolumeExt.jl)
 
 _BAND_MESH_MSG = ("volume_mesh is not supported on NarrowBandMeshField: a band does not hold the interior. "

@@ -320,6 +320,25 @@ class HipBackend:
     def iso_destroy(self, iso):
         self.lib.lsm_iso_destroy(iso)
 
+    # ---- from a mesh back to a level set (lsm_mesh_distance)
+    def mesh_distance(self, phi, vertices, elements, cutoff):
+        """ϕ := signed distance to the mesh, cut off; vertices (nv, N) float64 and elements (ne, N) int64 on the host or the
+        device.  Returns (nodes with d < cutoff, unbalanced grid rows, elements the sign pass skipped)."""
+        t = self.torch
+        if getattr(self, "slab", None) is not None:
+            raise L.LsmError("mesh_distance: this backend holds a slab of a decomposed grid; lsm_mesh_distance works on the whole grid of one device")
+        if not t.is_tensor(vertices):
+            vertices = np.array(vertices, dtype=np.float64, order="C")     # a copy torch may wrap (the caller's may be read-only)
+        if not t.is_tensor(elements):
+            elements = np.array(elements, dtype=np.int64, order="C")
+        v = t.as_tensor(vertices, dtype=t.float64, device=self.device).contiguous()
+        e = t.as_tensor(elements, dtype=t.int64, device=self.device).contiguous()
+        stats = (C.c_int64 * 3)()
+        L.check(self.h, self.lib.lsm_mesh_distance(self.h, int(v.shape[0]), self.ptr(v) if v.numel() else None, int(e.shape[0]),
+                                                   self.ptr(e) if e.numel() else None, float(cutoff), self.ptr(phi), stats, None),
+                "lsm_mesh_distance")
+        return tuple(int(s) for s in stats)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""

@@ -136,6 +136,7 @@ LsmHandle::~LsmHandle() {
     if (own_stream && stream) (void)hipStreamDestroy(stream);
     reinit_workspace_free(reinit_ws);
     i2oe_workspace_free(i2oe_ws);
+    mdist_workspace_free(mdist_ws);
 }
 
 extern "C" {
@@ -1779,6 +1780,30 @@ void lsm_iso_destroy(LsmIso* s) {
     if (!s) return;
     iso_free(s->o);
     delete s;
+}
+
+// mesh_distance: the signed distance to a closed mesh written into a dense field (lsm_mdist.hip), the inverse of lsm_iso_*
+int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_t nelems, const void* elements, double cutoff, void* phi_out,
+                      int64_t stats[3], void* stream) {
+    if (!h || !phi_out) return h ? fail(h, LSM_ERR_INVALID, "lsm_mesh_distance: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_mesh_distance: a 1-dimensional grid has no mesh to measure from (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_mesh_distance: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    if (!(cutoff > 0)) return fail(h, LSM_ERR_INVALID, "lsm_mesh_distance: cutoff must be positive (+inf: no cutoff)");
+    if (nverts < 0 || nelems < 0 || (nverts > 0 && !vertices) || (nelems > 0 && !elements))
+        return fail(h, LSM_ERR_INVALID, "lsm_mesh_distance: negative count or null array");
+    double lc[3] = {0, 0, 0};
+    for (int d = 0; d < N; ++d) lc[d] = h->grid.lc[d];
+    const char* err = nullptr;
+    long long c[3] = {0, 0, 0};
+    const int r = mdist_run(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, nverts, (const double*)vertices, nelems,
+                            (const long long*)elements, cutoff, phi_out, is_f32(h), stream ? (hipStream_t)stream : h->stream, c, &err, &h->mdist_ws);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_mesh_distance");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_mesh_distance");
+    if (stats)
+        for (int i = 0; i < 3; ++i) stats[i] = c[i];
+    return LSM_OK;
 }
 
 // volume_mesh (ext/MMGVolumeExt.jl up to the remesher): build once, copy the vertices, the elements and the interface elements out

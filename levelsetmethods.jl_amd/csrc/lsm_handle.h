@@ -54,6 +54,7 @@ struct PinnedBuf {
 };
 
 struct I2oeWorkspace;   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
+struct MdistWorkspace;  // lsm_mdist.hip: mesh_distance's scratch arrays
 }  // namespace lsm
 struct LsmComm;   // lsm_comm.hip: slab communicator (RCCL or in-process), NULL on a single-device handle
 
@@ -138,6 +139,7 @@ struct LsmHandle {
     size_t ev_used = 0;
     lsm::ReinitWorkspace* reinit_ws = nullptr;   // reinitialize!'s device buffers, kept between calls (grow-only)
     lsm::I2oeWorkspace* i2oe_ws = nullptr;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
+    lsm::MdistWorkspace* mdist_ws = nullptr;     // lsm_mesh_distance's squared distances and flip counters, kept between calls (grow-only)
     LsmComm* comm = nullptr;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
     bool yredirect = false;        // ... and those of dimension 2 (3-D)
     bool mredirect = false;        // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
@@ -190,4 +192,10 @@ int render_draw(RenderObject* o, const double* cam, int W, int H, const double* 
                 hipStream_t stream, const char** err);
 int render_bricks(RenderObject* o, long long dims[3], unsigned char* table, const char** err);
 void render_free(RenderObject* o);
+}
+namespace lsm {   // lsm_mdist.hip: from a mesh back to a level set
+int mdist_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], long long nv,
+              const double* verts, long long ne, const long long* elems, double cutoff, void* phi, int f32, hipStream_t stream, long long stats[3],
+              const char** err, MdistWorkspace** workspace);
+void mdist_workspace_free(MdistWorkspace* w);   // delete, where the type is complete
 }
