@@ -1757,13 +1757,10 @@ int lsm_iso_create(LsmHandle* h, const void* phi, const void* mask, double level
     if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_iso_create: the handle has a communicator attached (single device only)");
     LSM_TRY(check_single_device(h));
     if (!std::isfinite(level)) return fail(h, LSM_ERR_INVALID, "lsm_iso_create: level must be finite");
-    double lc[3] = {0, 0, 0};
-    for (int d = 0; d < N; ++d) lc[d] = h->grid.lc[d];
     const char* err = nullptr;
     IsoObject* o = nullptr;
     long long c[2] = {0, 0};
-    const int r = iso_build(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, level, phi, is_f32(h), (const unsigned char*)mask,
-                            h->stream, &o, c, &err);
+    const int r = iso_build(h, level, phi, (const unsigned char*)mask, &o, c, &err);
     if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_iso_create");
     if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_iso_create");
     *out = new LsmIso{h, o};
@@ -1816,12 +1813,10 @@ int lsm_vol_create(LsmHandle* h, const void* phi, const void* mask, double level
     if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_vol_create: the handle has a communicator attached (single device only)");
     LSM_TRY(check_single_device(h));
     if (!std::isfinite(level)) return fail(h, LSM_ERR_INVALID, "lsm_vol_create: level must be finite");
-    double lc[3] = {0, 0, 0};
-    for (int d = 0; d < N; ++d) lc[d] = h->grid.lc[d];
     const char* err = nullptr;
     VolObject* o = nullptr;
     long long c[3] = {0, 0, 0};
-    const int r = vol_build(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, level, phi, is_f32(h), h->stream, &o, c, &err);
+    const int r = vol_build(h, level, phi, &o, c, &err);
     if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_vol_create");
     if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_vol_create");
     *out = new LsmVol{h, o};

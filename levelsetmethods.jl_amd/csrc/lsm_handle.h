@@ -169,17 +169,15 @@ int quad_read(QuadObject* o, long long* cells, long long* offsets, double* coord
 int quad_total(QuadObject* o, double* total, const char** err);
 void quad_free(QuadObject* o);
 }
-namespace lsm {   // lsm_iso.hip: interface meshes
+namespace lsm {   // lsm_iso.hip: interface meshes (the geometry comes from the handle's grid and layout)
 struct IsoObject;
-int iso_build(int ndim, const int n[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], double level,
-              const void* phi, int f32, const unsigned char* mask, hipStream_t stream, IsoObject** out, long long counts_out[2], const char** err);
+int iso_build(const LsmHandle* h, double level, const void* phi, const unsigned char* mask, IsoObject** out, long long counts_out[2], const char** err);
 int iso_read(IsoObject* o, double* verts, long long* elems, const char** err);
 void iso_free(IsoObject* o);
 }
 namespace lsm {   // lsm_vol.hip: meshes of the interior
 struct VolObject;
-int vol_build(int ndim, const int n[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], double level,
-              const void* phi, int f32, hipStream_t stream, VolObject** out, long long counts_out[3], const char** err);
+int vol_build(const LsmHandle* h, double level, const void* phi, VolObject** out, long long counts_out[3], const char** err);
 int vol_read(VolObject* o, double* verts, long long* elems, long long* iface, const char** err);
 void vol_free(VolObject* o);
 }
