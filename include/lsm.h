@@ -428,6 +428,40 @@ void lsm_iso_destroy(LsmIso* s);
 int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_t nelems, const void* elements, double cutoff,
                       void* phi_out, int64_t stats[3], void* stream);
 
+/* ---- eikonal_(phi, speed, width, cutoff): |grad T| = s = 1/F on the dense grid, first-order Godunov upwind, solved by the
+ *      block-based fast iterative method (csrc/lsm_eikonal.hip; tests/_eikonal_ref.py restates every
+ *      operation).  phi[I] := copysign(min(T[I], cutoff), phi[I]) over the interior of a dense field of the handle (the ghosts
+ *      are left as they are: fill them before a stencil reads them).  speed NULL: s = 1, T is the distance to the interface —
+ *      a far-field redistancing in O(nodes); otherwise a device array of one double per interior node, n-shaped, axis 0
+ *      fastest (no ghosts), and T is the travel time of a front of speed F.  Inside and outside are solved as one
+ *      non-negative T.  A node is frozen (T given) or free (T starts at +inf); neighbours off the grid do not exist, whatever
+ *      the boundary condition.
+ *      The update G of a free node I: a_d = min(T[I-e_d], T[I+e_d]) over the neighbours that exist; the axes with a_d = +inf
+ *      are dropped (none left: G = +inf); the rest sorted by (a_d, d); a0 the smallest, tau = s_I·h of its axis; for k = 2, 3:
+ *      stop unless a0 + tau > a_k; over the first k axes, w_d = 1/(h_d·h_d), delta_d = a_d - a0, A = sum w, B = sum w·delta,
+ *      C = sum (w·delta)·delta - s_I·s_I, disc = B·B - A·C, stop if disc < 0, tau = (B + sqrt(disc))/A; G = a0 + tau.  I takes
+ *      T := G only when G < T.  (The quadratic is solved for T - a0: the un-shifted form cancels like (a/h)^2.)
+ *      Seeding: phi_I = 0 is frozen at T = 0.  I is crossing-adjacent when phi_I != 0 and an axis neighbour J that exists has
+ *      (phi_J > 0) != (phi_I > 0) or phi_J = 0.  width = 0 (the crossing seed, any phi): per axis sigma_d = min over such J of
+ *      h_d·(|phi_I|/(|phi_I| + |phi_J|)), T_I = s_I/sqrt(sum_d 1/(sigma_d·sigma_d)) over the axes with a crossing; every other
+ *      node is free.  width = w > 0 (phi already holds distances or times near the interface: after lsm_reinitialize, after
+ *      lsm_mesh_distance with a cutoff > w): every node with |phi_I| <= w and every crossing-adjacent node is frozen at
+ *      T_I = |phi_I|.
+ *      0 < cutoff <= +inf: nodes with T <= cutoff hold the values they hold without a cutoff, the others ±cutoff; the front
+ *      is not followed beyond it.  max_iters: the bound on the outer iterations (launches of the tile kernel); <= 0: 2·sum_d n_d.
+ *      stats[4] (may be NULL) := {frozen nodes, outer iterations, tile visits, nodes clamped at the cutoff}.
+ *      LSM_ERR_INVALID without running anything: a 1-D grid, a handle with a communicator or of a slab, a periodic dimension,
+ *      fewer than two nodes in a dimension, width < 0 or not finite, cutoff <= 0 or NaN.  (There is no mask parameter: the
+ *      values array of a band field is not a dense field, and the caller must not pass one.)  LSM_ERR_INVALID after the seed
+ *      kernel, which only reads phi: a non-finite phi (reason 1), a speed that is not finite and positive (2), no frozen node at
+ *      all: phi has no interface (3); stats := {-reason, offending nodes, 0, 0} then, and stats[0] >= 0 in every other return.  LSM_ERR_NOT_CONVERGED: the active list was not empty after max_iters outer iterations.  In every
+ *      failure phi is untouched: only the final pass writes it.  All arithmetic is fp64; an f32 handle is read once and
+ *      rounded once on store.  Neighbouring tiles run concurrently; T only decreases, so the fixed point does not depend on
+ *      the schedule beyond rounding (tests/test_gpu_eikonal.py).  stream: NULL = the handle's.  The scratch arrays (9 bytes
+ *      per node, 5 per tile) belong to the handle and only grow.  Synchronous. */
+int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, double cutoff, int64_t max_iters, int64_t stats[4],
+                void* stream);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

@@ -530,6 +530,18 @@ function mesh_distance!(ϕ::ROCMeshField, vertices::ROCMatrix{Float64}, elements
     return (; near = stats[1], unbalanced = stats[2], skipped = stats[3])
 end
 
+# eikonal!: ϕ := copysign(min(T, cutoff), ϕ), T the first-order solution of |∇T| = 1/speed over the whole grid (include/lsm.h,
+# lsm_eikonal): the far-field signed distance (speed = nothing) or travel times (speed: one Float64 per interior node on the
+# device, n-shaped).  width = 0: the crossing seed; width = w > 0: the nodes with |ϕ| <= w keep |ϕ|.  Returns (frozen, iterations,
+# visits, clamped).
+function eikonal!(ϕ::ROCMeshField; speed = nothing, width = 0.0, cutoff = Inf, max_iters = 0)
+    stats = zeros(Int64, 4)
+    _check(ϕ.h.ptr, ccall((:lsm_eikonal, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Float64, Float64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+        ϕ.h.ptr, pointer(ϕ.buf), speed === nothing ? C_NULL : pointer(speed), width, cutoff, max_iters, stats, C_NULL), "lsm_eikonal")
+    return (; frozen = stats[1], iterations = stats[2], visits = stats[3], clamped = stats[4])
+end
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

@@ -2247,17 +2247,106 @@ def mesh_distance_(phi, mesh, cutoff=None):
     return phi
 
 
-def mesh_distance(mesh, grid, cutoff=None, dtype=None, mode="fast", device=0):
+def mesh_distance(mesh, grid, cutoff=None, dtype=None, mode="fast", device=0, far=None):
     """The signed distance to a closed mesh on `grid` as a host MeshField, usable as `ic=`: mesh_distance_ on a throwaway device
     field.  `mesh`: an InterfaceMesh (read_mesh's, isosurface's) or a (vertices, elements) pair; dtype: float64 (default) or
-    float32 storage (the distance is computed in fp64 and rounded once)."""
+    float32 storage (the distance is computed in fp64 and rounded once).  far=None: nodes beyond the cutoff carry ±cutoff;
+    far="eikonal": they are filled in by eikonal_ from the nodes within the cutoff minus one cell diagonal, which hold exact
+    distances (exact near the mesh, first-order far from it, at the cost of a narrow exact pass).  Without a finite cutoff every
+    node already holds its exact distance and `far` changes nothing."""
+    if far not in (None, "eikonal"):
+        raise ValueError(f"mesh_distance: far must be None or 'eikonal', not {far!r}")
     ic = MeshField(np.zeros(grid.n, dtype=np.float64 if dtype is None else dtype, order="F"), grid, dtype=dtype)
     eq = LevelSetEquation(terms=(NormalMotionTerm(0.0),), ic=ic, bc=NeumannBC(), mode=mode, device=device)
     try:
-        vals = mesh_distance_(eq, mesh, cutoff).values()
+        mesh_distance_(eq, mesh, cutoff)
+        if far == "eikonal" and cutoff is not None and math.isfinite(float(cutoff)):
+            width = float(cutoff) - math.sqrt(sum(float(h) ** 2 for h in grid.meshsize()))
+            if not width > 0:
+                raise ValueError("mesh_distance: far='eikonal' needs a cutoff larger than one cell diagonal")
+            eikonal_(eq, width=width)
+        vals = eq.current_state().values()
     finally:
         eq.backend.close()
     return MeshField(vals, grid, dtype=dtype)
+
+
+# ----------------------------------------------------------------------------- far-field distance and travel times
+
+def eikonal_(phi, speed=None, width=None, cutoff=None, max_iters=None):
+    """Overwrite a device field with sign(ϕ)·min(T, cutoff), T the first-order Godunov solution of |∇T| = 1/speed over the whole
+    grid, solved on the device by the block-based fast iterative method.  speed=None: T is the distance to
+    the interface {ϕ = 0} — a redistancing of the whole grid in O(nodes), first-order accurate; where the exact distance of a
+    band matters, run reinitialize_ or mesh_distance_ first and pass `width`.  `speed`: a positive scalar, an array of the
+    grid's shape or a host MeshField on the same grid: T is then the travel time of a front of that speed.  width=None: the
+    nodes next to a sign change are seeded from the crossings along the grid lines (any ϕ); width = w > 0: the nodes with
+    |ϕ| <= w keep |ϕ| (ϕ already holds distances or times there).  cutoff=None means +inf: nodes with T <= cutoff hold the
+    values they hold without one, the others ±cutoff.  `max_iters` bounds the outer iterations (default 2·Σ n_d); exceeding it
+    raises a RuntimeError (LsmNotConvergedError) with ϕ unchanged.  `phi`: a dense ROCMeshField or a LevelSetEquation (its current
+    state), changed in place.  Returns ϕ."""
+    eq = phi if isinstance(phi, LevelSetEquation) else None
+    if eq is not None:
+        phi = eq.current_state()
+    if not isinstance(phi, ROCMeshField):
+        raise TypeError(f"eikonal_ takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
+    if isinstance(phi, ROCNarrowBandMeshField):
+        raise ValueError("eikonal_ is not supported on NarrowBandMeshField: the solve runs over the whole grid. "
+                         "Use a full MeshField, then build the band from it.")
+    N = phi.mesh.ndim
+    if N == 1:
+        raise ValueError("eikonal_ of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    b = phi.backend
+    if getattr(b, "slab", None) is not None:
+        raise ValueError("eikonal_ of a slab-decomposed field (a field with a comm) is not supported")
+    if phi.bcs is not None and any(bc.kind == L.BC_PERIODIC for pair in phi.bcs for bc in pair):
+        raise ValueError("eikonal_ with a PeriodicBC dimension is not supported: the front does not wrap around")
+    w = 0.0 if width is None else float(width)
+    if not (w > 0 and math.isfinite(w)) and width is not None:
+        raise ValueError("eikonal_: width must be positive and finite (None: seed from the crossings)")
+    c = float("inf") if cutoff is None else float(cutoff)
+    if not c > 0:
+        raise ValueError("eikonal_: cutoff must be positive (None or inf: no cutoff)")
+    sp = None
+    if speed is not None:
+        if isinstance(speed, MeshField):
+            if tuple(speed.mesh.n) != tuple(phi.mesh.n):
+                raise ValueError("eikonal_: the speed is a MeshField on another grid")
+            speed = speed.vals
+        if np.ndim(speed) == 0:
+            F = float(speed)
+            if not (F > 0 and math.isfinite(F)):
+                raise ValueError("eikonal_: the speed must be finite and positive")
+            sp = b.torch.full((int(np.prod(phi.mesh.n)),), F, dtype=b.torch.float64, device=b.device)     # filled on the device
+        else:
+            sp = np.asarray(speed, dtype=np.float64)
+            if sp.shape != tuple(phi.mesh.n):
+                raise ValueError(f"eikonal_: the speed has shape {sp.shape}, the grid has {tuple(phi.mesh.n)} nodes")
+    try:
+        b.eikonal(phi.buf, sp, w, c, 0 if max_iters is None else max(1, int(max_iters)))
+    except L.LsmNotConvergedError:
+        raise
+    except L.LsmError as e:
+        # what the seed kernel found in the data is the caller's argument error, as the refusals above are
+        why = {1: "phi must be finite", 2: "the speed must be finite and positive at every node",
+               3: "phi has no interface (no node is zero or next to a change of sign)"}.get(getattr(e, "reason", 0))
+        if why is None:
+            raise
+        raise ValueError(f"eikonal_: {why}") from None
+    phi.ghosts_dirty = True
+    return phi
+
+
+def eikonal(phi, speed=None, width=None, cutoff=None, max_iters=None, mode="fast", device=0):
+    """eikonal_ of a host MeshField on a throwaway device field: returns a new host MeshField, usable as `ic=`."""
+    if not isinstance(phi, MeshField):
+        raise TypeError(f"eikonal takes a host MeshField, not {type(phi).__name__}; eikonal_ works on device fields in place")
+    dtype = np.asarray(phi.vals).dtype
+    eq = LevelSetEquation(terms=(NormalMotionTerm(0.0),), ic=MeshField(phi.vals, phi.mesh, dtype=dtype), bc=NeumannBC(), mode=mode, device=device)
+    try:
+        vals = eikonal_(eq, speed, width, cutoff, max_iters).values()
+    finally:
+        eq.backend.close()
+    return MeshField(vals, phi.mesh, dtype=dtype)
 
 
 # ----------------------------------------------------------------------------- meshes of the interior (ext/MMGVolumeExt.jl)

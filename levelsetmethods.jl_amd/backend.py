@@ -339,6 +339,34 @@ class HipBackend:
                 "lsm_mesh_distance")
         return tuple(int(s) for s in stats)
 
+    # ---- far-field distance and travel times (lsm_eikonal)
+    def eikonal(self, phi, speed, width, cutoff, max_iters):
+        """ϕ := copysign(min(T, cutoff), ϕ), |∇T| = 1/speed; speed: None or an n-shaped array of float64 (host or device), axis 0
+        fastest; width 0: the crossing seed.  Returns (frozen nodes, outer iterations, tile visits, nodes clamped at the cutoff).  An
+        LsmError raised for the data carries `reason`: 1 a non-finite ϕ, 2 a speed that is not finite and positive, 3 no interface."""
+        t = self.torch
+        if getattr(self, "slab", None) is not None:
+            raise L.LsmError("eikonal: this backend holds a slab of a decomposed grid; lsm_eikonal works on the whole grid of one device")
+        sp = None
+        if speed is not None:
+            if not t.is_tensor(speed):
+                speed = np.array(speed, dtype=np.float64, order="F")            # a copy torch may wrap
+                if speed.shape != self.local_shape():
+                    raise L.LsmError(f"eikonal: the speed has shape {speed.shape}, the grid {self.local_shape()}")
+                speed = speed.reshape(-1, order="F")
+            sp = t.as_tensor(speed, dtype=t.float64, device=self.device).contiguous()
+            if sp.numel() != int(np.prod(self.local_shape())):
+                raise L.LsmError(f"eikonal: the speed has {sp.numel()} values, the grid {int(np.prod(self.local_shape()))} nodes")
+        stats = (C.c_int64 * 4)()
+        code = self.lib.lsm_eikonal(self.h, self.ptr(phi), self.ptr(sp) if sp is not None else None, float(width), float(cutoff),
+                                    int(max_iters), stats, None)
+        try:
+            L.check(self.h, code, "lsm_eikonal")
+        except L.LsmError as e:
+            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0     # include/lsm.h: what the data was refused for
+            raise
+        return tuple(int(s) for s in stats)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""

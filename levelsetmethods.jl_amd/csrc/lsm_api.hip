@@ -137,6 +137,7 @@ LsmHandle::~LsmHandle() {
     reinit_workspace_free(reinit_ws);
     i2oe_workspace_free(i2oe_ws);
     mdist_workspace_free(mdist_ws);
+    eikonal_workspace_free(eikonal_ws);
 }
 
 extern "C" {
@@ -1800,6 +1801,32 @@ int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_
     if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_mesh_distance");
     if (stats)
         for (int i = 0; i < 3; ++i) stats[i] = c[i];
+    return LSM_OK;
+}
+
+// eikonal: |∇T| = 1/F over a dense field by the block-based fast iterative method (lsm_eikonal.hip); phi := copysign(min(T, cutoff), phi)
+int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, double cutoff, int64_t max_iters, int64_t stats[4], void* stream) {
+    if (!h || !phi) return h ? fail(h, LSM_ERR_INVALID, "lsm_eikonal: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_eikonal: a 1-dimensional grid is not supported (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_eikonal: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    for (int d = 0; d < N; ++d) {
+        if (h->bc[d][0].kind == LSM_BC_PERIODIC || h->bc[d][1].kind == LSM_BC_PERIODIC)
+            return fail(h, LSM_ERR_INVALID, "lsm_eikonal: a periodic dimension is not supported (the front does not wrap)");
+        if (h->nloc[d] < 2) return fail(h, LSM_ERR_INVALID, "lsm_eikonal: at least two nodes per dimension");
+    }
+    if (!(width >= 0) || std::isinf(width)) return fail(h, LSM_ERR_INVALID, "lsm_eikonal: width must be finite and not negative (0: the crossing seed)");
+    if (!(cutoff > 0)) return fail(h, LSM_ERR_INVALID, "lsm_eikonal: cutoff must be positive (+inf: no cutoff)");
+    const char* err = nullptr;
+    long long c[4] = {0, 0, 0, 0};
+    const int r = eikonal_run(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, h->h, phi, is_f32(h), speed, width, cutoff, max_iters,
+                              stream ? (hipStream_t)stream : h->stream, c, &err, &h->eikonal_ws);
+    if (stats)
+        for (int i = 0; i < 4; ++i) stats[i] = c[i];
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_eikonal");
+    if (r == 3) return fail(h, LSM_ERR_NOT_CONVERGED, err ? err : "lsm_eikonal");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_eikonal");
     return LSM_OK;
 }
 

@@ -55,6 +55,7 @@ struct PinnedBuf {
 
 struct I2oeWorkspace;   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
 struct MdistWorkspace;  // lsm_mdist.hip: mesh_distance's scratch arrays
+struct EikonalWorkspace;   // lsm_eikonal.hip: eikonal's arrival times, frozen mask and tile lists
 }  // namespace lsm
 struct LsmComm;   // lsm_comm.hip: slab communicator (RCCL or in-process), NULL on a single-device handle
 
@@ -140,6 +141,7 @@ struct LsmHandle {
     lsm::ReinitWorkspace* reinit_ws = nullptr;   // reinitialize!'s device buffers, kept between calls (grow-only)
     lsm::I2oeWorkspace* i2oe_ws = nullptr;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
     lsm::MdistWorkspace* mdist_ws = nullptr;     // lsm_mesh_distance's squared distances and flip counters, kept between calls (grow-only)
+    lsm::EikonalWorkspace* eikonal_ws = nullptr; // lsm_eikonal's arrival times, frozen mask, tile flags and lists, kept between calls (grow-only)
     LsmComm* comm = nullptr;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
     bool yredirect = false;        // ... and those of dimension 2 (3-D)
     bool mredirect = false;        // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
@@ -196,4 +198,9 @@ int mdist_run(int ndim, const int n[3], long long s1, long long s2, long long or
               const double* verts, long long ne, const long long* elems, double cutoff, void* phi, int f32, hipStream_t stream, long long stats[3],
               const char** err, MdistWorkspace** workspace);
 void mdist_workspace_free(MdistWorkspace* w);   // delete, where the type is complete
+}
+namespace lsm {   // lsm_eikonal.hip: |∇T| = 1/F over the whole grid by the block-based fast iterative method
+int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double h[3], void* phi, int f32, const double* speed,
+                double width, double cutoff, long long max_iters, hipStream_t stream, long long stats[4], const char** err, EikonalWorkspace** workspace);
+void eikonal_workspace_free(EikonalWorkspace* w);   // delete, where the type is complete
 }
