@@ -462,6 +462,38 @@ int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_
 int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, double cutoff, int64_t max_iters, int64_t stats[4],
                 void* stream);
 
+/* ---- components(ϕ, level, side): the connected components of the set S = {ϕ < level} (side 0) or of its complement (side 1)
+ *      on the dense grid, labelled on the device by block-based union–find (csrc/lsm_cc.hip, DESIGN.md §7.16;
+ *      tests/_cc_ref.py restates the definition).  inside(I) := ϕ[I] < level, as lsm_iso_*: ϕ == level is outside.  Two nodes
+ *      of S are adjacent iff they differ by ±d for some d in {0,1}^ndim \ {0}: the edges of the Freudenthal (Kuhn)
+ *      subdivision that lsm_iso_* and lsm_vol_* cut — 6 neighbours in 2-D, 14 in 3-D, not the 4/8 or 6/26 neighbourhoods of
+ *      image libraries — so the components of side 0 are exactly the vertex-connected pieces of lsm_vol_*'s mesh.  Components
+ *      are numbered 0 … K−1 in ascending order of their smallest linear node index (axis 0 fastest); the result does not
+ *      depend on the schedule.  Only the interior of phi is read.
+ *      lsm_cc_create: stats[4] (may be NULL) := {K, nodes in S, Kuhn edges between two nodes of S in different tiles (8x8x8;
+ *      32x8 in 2-D), non-finite nodes}.  LSM_ERR_INVALID: a 1-D grid, a slab handle or one with a communicator, a periodic
+ *      dimension (the wrap would join components), level not finite, side not 0 or 1, 2^31 − 1 nodes or more, a non-finite
+ *      phi (stats[3] > 0; stats is filled).  (There is no mask parameter: the values array of a band field is not a dense
+ *      field, and the caller must not pass one.)  An empty S is LSM_OK with K = 0.
+ *      lsm_cc_read copies into device buffers (each may be NULL): labels, one int32 per interior node, n-shaped, axis 0
+ *      fastest, −1 off S; nodes int64[K]; index_sums int64[K][ndim], the sums of the 0-based node indices per axis;
+ *      bbox int32[K][2][ndim], the smallest and the largest index per axis.  All are integers: exact, whatever the order of
+ *      the additions.
+ *      lsm_cc_flip moves every node of the components k with which[k] != 0 (K bytes on the device) to the other side of
+ *      level, in place: v' = level + (level − v), two fp64 operations without contraction; for side 1, where v' is not
+ *      < level it becomes the double just below level; f32 storage is read widened, rounded once, and where the rounded
+ *      value is on the wrong side it is replaced by the neighbouring float on the right side.  *flipped := the number of
+ *      nodes written.  A first pass counts the flagged nodes that the current phi does not put on the object's side; when
+ *      there is one the call fails with LSM_ERR_INVALID and phi is untouched (phi changed since lsm_cc_create, or the
+ *      components were flipped already).  The ghosts are left as they are, and the result is no distance function near what
+ *      was removed.  The parent array (4 bytes per node) belongs to the handle and only grows; the labels (4 bytes per node)
+ *      and the statistics belong to the object.  Synchronous, on the handle's stream. */
+typedef struct LsmCc LsmCc;
+int lsm_cc_create(LsmHandle* h, const void* phi, double level, int side, LsmCc** out, int64_t stats[4]);
+int lsm_cc_read(LsmCc* s, void* labels, void* nodes, void* index_sums, void* bbox);
+int lsm_cc_flip(LsmCc* s, void* phi, const void* which, int64_t* flipped);
+void lsm_cc_destroy(LsmCc* s);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

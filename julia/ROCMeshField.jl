@@ -542,6 +542,36 @@ function eikonal!(ϕ::ROCMeshField; speed = nothing, width = 0.0, cutoff = Inf, 
     return (; frozen = stats[1], iterations = stats[2], visits = stats[3], clamped = stats[4])
 end
 
+# components: the connected components of {ϕ < level} (side = :inside) or of its complement (:outside) over the Kuhn edges
+# (include/lsm.h, lsm_cc_*), numbered by their smallest linear node index.  Returns the object `cc` (release it with
+# destroy_components; remove_components! needs it), count, labels (Int32, one per node, −1 off the set, on the device), nodes
+# (K), index_sums (ndim x K, of the 0-based indices) and bbox (ndim x 2 x K, 0-based), and the call's stats.
+function components(ϕ::ROCMeshField; level = 0.0, side = :inside)
+    out, stats = Ref{Ptr{Cvoid}}(), zeros(Int64, 4)
+    _check(ϕ.h.ptr, ccall((:lsm_cc_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), level, side === :outside ? 1 : 0, out, stats), "lsm_cc_create")
+    cc, K, N = out[], stats[1], ndims(ϕ)
+    labels = ROCArray{Int32}(undef, size(ϕ.mesh)...)
+    nodes, index_sums, bbox = ROCVector{Int64}(undef, K), ROCMatrix{Int64}(undef, N, K), ROCArray{Int32}(undef, N, 2, K)
+    _check(ϕ.h.ptr, ccall((:lsm_cc_read, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        cc, pointer(labels), K == 0 ? C_NULL : pointer(nodes), K == 0 ? C_NULL : pointer(index_sums), K == 0 ? C_NULL : pointer(bbox)), "lsm_cc_read")
+    return (; cc, count = K, labels, nodes, index_sums, bbox, stats)
+end
+
+# remove_components!: every node of the components flagged in `which` (K bytes on the device) is mirrored to the other side of
+# the level, in place; refused with ϕ untouched when ϕ no longer matches `c`.  Not a distance function afterwards near what was
+# removed: reinitialize! or eikonal! next.  Returns the number of nodes flipped.
+function remove_components!(ϕ::ROCMeshField, c, which::ROCVector{UInt8})
+    length(which) == c.count || throw(ArgumentError("which has $(length(which)) entries, there are $(c.count) components"))
+    c.count == 0 && return 0
+    flipped = Ref{Int64}(0)
+    _check(ϕ.h.ptr, ccall((:lsm_cc_flip, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}),
+        c.cc, pointer(ϕ.buf), pointer(which), flipped), "lsm_cc_flip")
+    return flipped[]
+end
+
+destroy_components(c) = ccall((:lsm_cc_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), c.cc)
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

@@ -15,7 +15,8 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   perimeter, volume, InterpolatedField, NewtonSDF, hausdorff_distance, SideField, curvature, curvature_field, gradient, gradient_field, normal, normal_field,
                   vortex_deformation, show, LocalGroup, nodeindices, cellindices, getnode, getcell, active_nodeindices, active_cellindices,
                   update_band_, quadrature, integrate, Quadrature, CellQuadratures, isosurface, export_surface_mesh, InterfaceMesh, Camera, Renderer, render, record_, Image,
-                  volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_)
+                  volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
+                  components, remove_components_, prune_, Components)
 
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
@@ -28,4 +29,5 @@ __all__ = [
     "nodeindices", "cellindices", "getnode", "getcell", "active_nodeindices", "active_cellindices", "update_band_",
     "quadrature", "integrate", "Quadrature", "CellQuadratures", "isosurface", "export_surface_mesh", "InterfaceMesh", "Camera", "Renderer", "render", "record_", "Image",
     "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
+    "components", "remove_components_", "prune_", "Components",
 ]

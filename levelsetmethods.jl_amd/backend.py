@@ -367,6 +367,44 @@ class HipBackend:
             raise
         return tuple(int(s) for s in stats)
 
+    # ---- connected components (lsm_cc_*)
+    def cc_create(self, phi, level, side):
+        """returns (result handle, (K, nodes in the set, cross-tile edges, non-finite nodes)); side 0: {ϕ < level}, 1: the
+        complement.  An LsmError raised for a non-finite ϕ carries `nonfinite`, the number of such nodes."""
+        if not self.torch.is_tensor(phi) or not phi.is_cuda:
+            raise TypeError(f"cc_create takes a device buffer of this backend, not {type(phi).__name__}")
+        if self.slab is not None:     # a one-rank group's slab is the whole grid with no communicator: the library could not tell
+            raise L.LsmError("cc_create: this backend holds a slab of a decomposed grid; lsm_cc_create works on the whole grid of one device")
+        out, stats = C.c_void_p(), (C.c_int64 * 4)()
+        code = self.lib.lsm_cc_create(self.h, self.ptr(phi), float(level), int(side), C.byref(out), stats)
+        try:
+            L.check(self.h, code, "lsm_cc_create")
+        except L.LsmError as e:
+            e.nonfinite = int(stats[3]) if code == L.ERR_INVALID else 0
+            raise
+        return out, tuple(int(s) for s in stats)
+
+    def cc_read(self, cc, K):
+        """the result's device arrays: labels int32 (one per node, axis 0 fastest), nodes int64 (K), index sums int64 (K, N),
+        bounding boxes int32 (K, 2, N)"""
+        t, N = self.torch, self.ndim
+        labels = t.empty(int(np.prod(self.local_shape())), dtype=t.int32, device=self.device)
+        nodes = t.empty((K,), dtype=t.int64, device=self.device)
+        sums = t.empty((K, N), dtype=t.int64, device=self.device)
+        bbox = t.empty((K, 2, N), dtype=t.int32, device=self.device)
+        L.check(self.h, self.lib.lsm_cc_read(cc, self.ptr(labels), self.ptr(nodes) if K else None, self.ptr(sums) if K else None,
+                                             self.ptr(bbox) if K else None), "lsm_cc_read")
+        return labels, nodes, sums, bbox
+
+    def cc_flip(self, cc, phi, which):
+        """flip the components flagged in `which` (a uint8 device tensor of K entries) in ϕ; returns the number of nodes written"""
+        n = C.c_int64(0)
+        L.check(self.h, self.lib.lsm_cc_flip(cc, self.ptr(phi), self.ptr(which), C.byref(n)), "lsm_cc_flip")
+        return int(n.value)
+
+    def cc_destroy(self, cc):
+        self.lib.lsm_cc_destroy(cc)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""

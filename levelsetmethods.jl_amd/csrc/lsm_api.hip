@@ -138,6 +138,7 @@ LsmHandle::~LsmHandle() {
     i2oe_workspace_free(i2oe_ws);
     mdist_workspace_free(mdist_ws);
     eikonal_workspace_free(eikonal_ws);
+    cc_workspace_free(cc_ws);
 }
 
 extern "C" {
@@ -1828,6 +1829,53 @@ int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, doub
     if (r == 3) return fail(h, LSM_ERR_NOT_CONVERGED, err ? err : "lsm_eikonal");
     if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_eikonal");
     return LSM_OK;
+}
+
+// components: the connected pieces of {phi < level} (side 0) or of its complement (side 1) over the Kuhn edges (lsm_cc.hip)
+struct LsmCc { LsmHandle* h; CcObject* o; };
+int lsm_cc_create(LsmHandle* h, const void* phi, double level, int side, LsmCc** out, int64_t stats[4]) {
+    if (!h || !phi || !out) return h ? fail(h, LSM_ERR_INVALID, "lsm_cc_create: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_cc_create: a 1-dimensional grid is not supported (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_cc_create: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    for (int d = 0; d < N; ++d)
+        if (h->bc[d][0].kind == LSM_BC_PERIODIC || h->bc[d][1].kind == LSM_BC_PERIODIC)
+            return fail(h, LSM_ERR_INVALID, "lsm_cc_create: a periodic dimension is not supported (components are not joined across the wrap)");
+    if (!std::isfinite(level)) return fail(h, LSM_ERR_INVALID, "lsm_cc_create: level must be finite");
+    if (side != 0 && side != 1) return fail(h, LSM_ERR_INVALID, "lsm_cc_create: side must be 0 (phi < level) or 1 (the complement)");
+    const char* err = nullptr;
+    CcObject* o = nullptr;
+    long long c[4] = {0, 0, 0, 0};
+    const int r = cc_build(h, &h->cc_ws, level, side, phi, &o, c, &err);
+    if (stats)
+        for (int i = 0; i < 4; ++i) stats[i] = c[i];
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_cc_create");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_cc_create");
+    *out = new LsmCc{h, o};
+    return LSM_OK;
+}
+int lsm_cc_read(LsmCc* s, void* labels, void* nodes, void* index_sums, void* bbox) {
+    if (!s) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (cc_read(s->o, (int*)labels, (long long*)nodes, (long long*)index_sums, (int*)bbox, &err)) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_cc_read");
+    return LSM_OK;
+}
+int lsm_cc_flip(LsmCc* s, void* phi, const void* which, int64_t* flipped) {
+    if (!s) return LSM_ERR_INVALID;
+    if (!phi || !which || !flipped) return fail(s->h, LSM_ERR_INVALID, "lsm_cc_flip: null argument");
+    const char* err = nullptr;
+    long long n = 0;
+    const int r = cc_flip(s->o, s->h->cc_ws, phi, (const unsigned char*)which, &n, &err);
+    *flipped = n;
+    if (r == 1) return fail(s->h, LSM_ERR_INVALID, err ? err : "lsm_cc_flip");
+    if (r) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_cc_flip");
+    return LSM_OK;
+}
+void lsm_cc_destroy(LsmCc* s) {
+    if (!s) return;
+    cc_free(s->o);
+    delete s;
 }
 
 // volume_mesh (ext/MMGVolumeExt.jl up to the remesher): build once, copy the vertices, the elements and the interface elements out

@@ -56,6 +56,7 @@ struct PinnedBuf {
 struct I2oeWorkspace;   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
 struct MdistWorkspace;  // lsm_mdist.hip: mesh_distance's scratch arrays
 struct EikonalWorkspace;   // lsm_eikonal.hip: eikonal's arrival times, frozen mask and tile lists
+struct CcWorkspace;     // lsm_cc.hip: components' parent array, chunk counts and counters
 }  // namespace lsm
 struct LsmComm;   // lsm_comm.hip: slab communicator (RCCL or in-process), NULL on a single-device handle
 
@@ -142,6 +143,7 @@ struct LsmHandle {
     lsm::I2oeWorkspace* i2oe_ws = nullptr;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
     lsm::MdistWorkspace* mdist_ws = nullptr;     // lsm_mesh_distance's squared distances and flip counters, kept between calls (grow-only)
     lsm::EikonalWorkspace* eikonal_ws = nullptr; // lsm_eikonal's arrival times, frozen mask, tile flags and lists, kept between calls (grow-only)
+    lsm::CcWorkspace* cc_ws = nullptr;           // lsm_cc_*'s parent array (4 bytes per node), chunk counts and counters, kept between calls (grow-only)
     LsmComm* comm = nullptr;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
     bool yredirect = false;        // ... and those of dimension 2 (3-D)
     bool mredirect = false;        // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
@@ -203,4 +205,12 @@ namespace lsm {   // lsm_eikonal.hip: |∇T| = 1/F over the whole grid by the bl
 int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double h[3], void* phi, int f32, const double* speed,
                 double width, double cutoff, long long max_iters, hipStream_t stream, long long stats[4], const char** err, EikonalWorkspace** workspace);
 void eikonal_workspace_free(EikonalWorkspace* w);   // delete, where the type is complete
+}
+namespace lsm {   // lsm_cc.hip: connected components of {ϕ < level} or of its complement over the Kuhn edges, by block-based union–find
+struct CcObject;
+int cc_build(const LsmHandle* h, CcWorkspace** workspace, double level, int side, const void* phi, CcObject** out, long long stats[4], const char** err);
+int cc_read(CcObject* o, int* labels, long long* nodes, long long* sums, int* bbox, const char** err);
+int cc_flip(CcObject* o, CcWorkspace* w, void* phi, const unsigned char* which, long long* flipped, const char** err);
+void cc_free(CcObject* o);
+void cc_workspace_free(CcWorkspace* w);   // delete, where the type is complete
 }
