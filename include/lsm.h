@@ -494,6 +494,64 @@ int lsm_cc_read(LsmCc* s, void* labels, void* nodes, void* index_sums, void* bbo
 int lsm_cc_flip(LsmCc* s, void* phi, const void* which, int64_t* flipped);
 void lsm_cc_destroy(LsmCc* s);
 
+/* ---- elliptic_solve: −∇·(a∇u) + c·u = f on the box of a dense 2-D or 3-D grid, the state equation of a shape optimisation with
+ *      an ersatz material outside the level set, and with constant coefficients the H¹ regularisation (I − α²Δ)V = g; solved on
+ *      the device by conjugate gradients preconditioned by one geometric multigrid V-cycle (csrc/lsm_elliptic.hip, DESIGN.md
+ *      §7.17; tests/_elliptic_ref.py restates every operation).  Unknowns at the nodes; natural (zero-flux) conditions on every
+ *      face; a caller-given set of fixed (Dirichlet) nodes.  Node arrays are n-shaped fp64 on the device, axis 0 fastest, no
+ *      ghosts; the cell array has n−1 entries per axis.  All arithmetic is fp64, without contraction.
+ *      Cell coefficient, for a cell with 2^N corners: mean = (sum of the corner values of phi in ascending linear index)·2^−N;
+ *      theta = min(max(1/2 − (mean − level)/min_d h_d, 0), 1); a = a_out + (a_in − a_out)·theta.  Or a_cells != NULL: the cell
+ *      array is the caller's (phi may be NULL then).
+ *      Edge coefficient, along d between I and I+e_d: S = the sum of a over the existing cells that share the edge, in ascending
+ *      linear index; k = S·2^−(N−1) (a boundary edge carries half or a quarter: the faces are natural); kbar = S/(number of
+ *      those cells); w = k·ih2_d with ih2_d = 1/(h_d·h_d).  Node mass m_I = (existing cells around I)/2^N.
+ *      Operator, scaled by 1/prod h: (A u)_I = sum_d [ w_minus·(u_I − u_{I−e_d}) + w_plus·(u_I − u_{I+e_d}) ] + (c_I·m_I)·u_I,
+ *      accumulated from +0 in this order: d ascending, the minus side before the plus side, sides that do not exist skipped,
+ *      the c term last.  The right-hand side is b_I = m_I·f_I.  A is symmetric.  c: c_nodes (n-shaped) or c_const.
+ *      Fixed nodes (fixed: one byte per node, non-zero = fixed; NULL: none) keep u_I exactly; their rows and columns are
+ *      eliminated: r0 = b − A u0 on the free nodes with u0 = u as passed (the Dirichlet values on the fixed nodes, the guess
+ *      elsewhere); search directions are zero on fixed nodes.
+ *      Solver: PCG on the free nodes until the recursive ||r||_2 <= rtol·||b_free||_2 (||r0||_2 where b_free is zero).  The
+ *      scalars and the status live on the device; iterations are enqueued in chunks.  precond LSM_PRECOND_JACOBI: D^−1.
+ *      LSM_PRECOND_MG: one V-cycle from zero.  Coarsening per dimension: axis d coarsens while n_d > 5, to (n_d+1)/2 nodes;
+ *      coarse node J sits on fine node 2J and h_d doubles; an axis that stopped is carried unchanged; the hierarchy ends when
+ *      no axis coarsens (the coarsest level has at most 5 nodes per axis).  For an even n_d the last fine node has no coarse
+ *      partner.  Prolongation, a tensor product of: fine 2J <- J; fine 2J+1 <- (J + (J+1))/2, or J alone where J+1 does not
+ *      exist.  Restriction = P^T/2^(coarsened axes); fine residuals are zero on fixed nodes; a coarse node is fixed iff fine
+ *      node 2J is; corrections are zero on fixed nodes.  Coarse operator: the same discretisation with the coarse cell's a the
+ *      arithmetic mean of the fine cells {2J, 2J+1} per coarsened axis, c injected.  Smoother: damped Jacobi, omega = 0.8,
+ *      x <- x + omega·(r − A x)/D, 2 sweeps before and 2 after; the first sweep from zero is omega·r/D; the coarsest level
+ *      runs 16 such sweeps from zero.
+ *      lsm_elliptic_create builds the hierarchy (owned by the caller: lsm_elliptic_destroy frees it with its scratch, about
+ *      10 doubles per node).  stats[4] (may be NULL) := {levels, free nodes, fixed nodes, 0}.  LSM_ERR_INVALID without running
+ *      anything: a 1-D grid, a slab handle or one with a communicator, a periodic dimension, fewer than 3 nodes in a dimension,
+ *      a_in / a_out not finite and positive, c_const negative or not finite, an unknown precond.  (There is no mask parameter:
+ *      the values array of a band field is not a dense field, and the caller must not pass one.)  LSM_ERR_INVALID after the
+ *      setup kernel, with stats := {−reason, offending entries, 0, 0}: a non-finite phi (1), a cell coefficient not finite and
+ *      positive (2), a c not finite or negative (3), no fixed node and c = 0 everywhere: singular (4), every node fixed (5).
+ *      lsm_elliptic_apply: y = A x on all nodes, no elimination (so that tests can see the operator).
+ *      lsm_elliptic_solve: f n-shaped fp64; u a dense field of the handle: in, the guess and the Dirichlet values; out, the
+ *      solution on the free nodes, rounded once to the storage type; fixed nodes and ghosts are left as they are.
+ *      LSM_ERR_INVALID: a non-finite f or u.  LSM_ERR_NOT_CONVERGED: breakdown or max_iters.  In every failure u is untouched.
+ *      *iters, *relres (may be NULL) := the iterations and the recursive ||r||/||b_free||.  stream: NULL = the handle's.
+ *      lsm_elliptic_energy: e_I = sum_d ( sum over the sides that exist, minus first, of kbar·(g·g), g = (u_J − u_I)/h_d )
+ *      / (number of existing edges along d at I), d ascending, into a dense field of the handle (rounded once).
+ *      lsm_elliptic_compliance: *out := prod h · sum_I (m_I·f_I)·u_I, reduced on the device.
+ *      lsm_elliptic_cells copies the level-0 cell array into a device buffer.  All but solve run on the handle's stream;
+ *      solve, compliance and create are synchronous. */
+#define LSM_PRECOND_MG 0
+#define LSM_PRECOND_JACOBI 1
+typedef struct LsmElliptic LsmElliptic;
+int lsm_elliptic_create(LsmHandle* h, const void* phi, double level, double a_in, double a_out, const double* a_cells, double c_const,
+                        const double* c_nodes, const void* fixed, int precond, LsmElliptic** out, int64_t stats[4]);
+int lsm_elliptic_apply(LsmElliptic* s, const double* x, double* y);
+int lsm_elliptic_solve(LsmElliptic* s, const double* f, void* u, double rtol, int max_iters, int* iters, double* relres, void* stream);
+int lsm_elliptic_energy(LsmElliptic* s, const void* u, void* e_out);
+int lsm_elliptic_compliance(LsmElliptic* s, const double* f, const void* u, double* out);
+int lsm_elliptic_cells(LsmElliptic* s, double* a_out_cells);
+void lsm_elliptic_destroy(LsmElliptic* s);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

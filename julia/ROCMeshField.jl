@@ -572,6 +572,47 @@ end
 
 destroy_components(c) = ccall((:lsm_cc_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), c.cc)
 
+# elliptic_operator: the discrete −∇·(a∇u) + c·u of ϕ's grid with its multigrid hierarchy (include/lsm.h, lsm_elliptic_*).  The cell
+# coefficient is a_out + (a_in − a_out)·θ(ϕ), or `a` (a ROCArray{Float64} of size n .- 1); c: a number or a ROCArray{Float64} of
+# the grid's size; fixed: nothing or a ROCArray{UInt8} of the grid's size (non-zero = Dirichlet node); precond :mg or :jacobi.
+# Release it with destroy_elliptic.
+function elliptic_operator(ϕ::ROCMeshField; level = 0.0, a_in = 1.0, a_out = 1e-3, a = nothing, c = 0.0, fixed = nothing, precond = :mg)
+    out, stats = Ref{Ptr{Cvoid}}(), zeros(Int64, 4)
+    cnodes = c isa Number ? C_NULL : pointer(c)
+    _check(ϕ.h.ptr, ccall((:lsm_elliptic_create, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), level, a_in, a_out, a === nothing ? C_NULL : pointer(a), c isa Number ? Float64(c) : 0.0, cnodes,
+        fixed === nothing ? C_NULL : pointer(fixed), precond === :jacobi ? 1 : 0, out, stats), "lsm_elliptic_create")
+    return (; op = out[], h = ϕ.h, levels = stats[1], free = stats[2], fixed = stats[3])
+end
+
+# elliptic_solve!: u (a field of the same handle) holds the guess and, on the fixed nodes, the Dirichlet values; on return the
+# solution.  f: a ROCArray{Float64} of the grid's size.  Returns (iterations, relres); a failure leaves u untouched.
+function elliptic_solve!(u::ROCMeshField, E, f; rtol = 1e-8, max_iters = 500)
+    iters, relres = Ref{Cint}(0), Ref{Float64}(0.0)
+    _check(E.h.ptr, ccall((:lsm_elliptic_solve, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Float64, Cint, Ref{Cint}, Ref{Float64}, Ptr{Cvoid}),
+        E.op, pointer(f), pointer(u.buf), rtol, max_iters, iters, relres, C_NULL), "lsm_elliptic_solve")
+    return (; iterations = iters[], relres = relres[])
+end
+
+# y = A x on all nodes, no elimination (x, y: ROCArray{Float64} of the grid's size)
+elliptic_apply!(y, E, x) = _check(E.h.ptr, ccall((:lsm_elliptic_apply, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), E.op, pointer(x), pointer(y)), "lsm_elliptic_apply")
+
+# the energy density a|∇u|² at the nodes into the field e: the normal speed of a compliance descent (NormalMotionTerm takes e.buf's values)
+elliptic_energy!(e::ROCMeshField, E, u::ROCMeshField) =
+    _check(E.h.ptr, ccall((:lsm_elliptic_energy, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), E.op, pointer(u.buf), pointer(e.buf)), "lsm_elliptic_energy")
+
+function elliptic_compliance(E, f, u::ROCMeshField)
+    out = Ref{Float64}(0.0)
+    _check(E.h.ptr, ccall((:lsm_elliptic_compliance, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ref{Float64}), E.op, pointer(f), pointer(u.buf), out), "lsm_elliptic_compliance")
+    return out[]
+end
+
+# the level-0 cell coefficients into a ROCArray{Float64} of size n .- 1
+elliptic_cells!(a, E) = _check(E.h.ptr, ccall((:lsm_elliptic_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), E.op, pointer(a)), "lsm_elliptic_cells")
+
+destroy_elliptic(E) = ccall((:lsm_elliptic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), E.op)
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

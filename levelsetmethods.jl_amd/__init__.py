@@ -16,7 +16,8 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   vortex_deformation, show, LocalGroup, nodeindices, cellindices, getnode, getcell, active_nodeindices, active_cellindices,
                   update_band_, quadrature, integrate, Quadrature, CellQuadratures, isosurface, export_surface_mesh, InterfaceMesh, Camera, Renderer, render, record_, Image,
                   volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
-                  components, remove_components_, prune_, Components)
+                  components, remove_components_, prune_, Components,
+                  elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution)
 
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
@@ -30,4 +31,5 @@ __all__ = [
     "quadrature", "integrate", "Quadrature", "CellQuadratures", "isosurface", "export_surface_mesh", "InterfaceMesh", "Camera", "Renderer", "render", "record_", "Image",
     "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
     "components", "remove_components_", "prune_", "Components",
+    "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
 ]

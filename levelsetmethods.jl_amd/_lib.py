@@ -28,6 +28,7 @@ GEOM_CURVATURE, GEOM_GRADIENT, GEOM_NORMAL = 0, 1, 2
 FAST_MAX_ABS = 2.5e34
 COMM_ID_BYTES = 128
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
+PRECOND_MG, PRECOND_JACOBI = 0, 1
 
 
 class LsmGrid(C.Structure):
@@ -150,6 +151,14 @@ _SIGS = [
     ("lsm_cc_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_cc_flip", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ("lsm_cc_destroy", None, [C.c_void_p]),
+    ("lsm_elliptic_create", C.c_int, [_H, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    ("lsm_elliptic_apply", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p]),
+    ("lsm_elliptic_energy", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_compliance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("lsm_elliptic_cells", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_destroy", None, [C.c_void_p]),
     ("lsm_extend_along_normals", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_double, C.c_double, C.c_double]),
     ("lsm_band_tile_count", C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),

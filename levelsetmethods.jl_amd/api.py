@@ -2508,6 +2508,243 @@ def prune_(phi_or_eq, min_nodes=None, keep_largest=None, level=0.0, side="inside
     return comps, remove_components_(phi, comps, which)
 
 
+# ----------------------------------------------------------------------------- elliptic solves (the state equation of a shape optimisation)
+
+_PRECONDS = {"mg": L.PRECOND_MG, "jacobi": L.PRECOND_JACOBI}
+_ELLIPTIC_REFUSALS = {1: "phi must be finite", 2: "the cell coefficients `a` must be finite and positive", 3: "c must be finite and not negative",
+                      4: "no fixed node and c = 0 everywhere: the problem is singular", 5: "every node is fixed"}
+
+
+def face_mask(grid, d, side):
+    """The boolean node mask (shape grid.n) of a face of the box: dimension d (0-based), side 0 (lower) or 1 (upper); for `dirichlet=`."""
+    n = tuple(int(m) for m in grid.n)
+    if not 0 <= int(d) < len(n) or side not in (0, 1):
+        raise ValueError("face_mask: d must be a dimension of the grid and side 0 or 1")
+    m = np.zeros(n, dtype=np.bool_, order="F")
+    m[tuple(slice(None) if e != d else (0 if side == 0 else n[d] - 1) for e in range(len(n)))] = True
+    return m
+
+
+def _finite_positive(x):
+    return bool(np.all(np.isfinite(x)) and np.all(np.asarray(x) > 0))
+
+
+def _elliptic_field(phi, what):
+    """the dense single-device 2-D / 3-D field behind an elliptic solve, or the refusal"""
+    if isinstance(phi, LevelSetEquation):
+        phi = phi.current_state()
+    if not isinstance(phi, ROCMeshField):
+        raise TypeError(f"{what} takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
+    if isinstance(phi, ROCNarrowBandMeshField):
+        raise ValueError(f"{what} is not supported on NarrowBandMeshField: the equation is solved over the whole box. Use a full MeshField.")
+    if phi.mesh.ndim == 1:
+        raise ValueError(f"{what} of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    if getattr(phi.backend, "slab", None) is not None:
+        raise ValueError(f"{what} of a slab-decomposed field (a field with a comm) is not supported")
+    if phi.bcs is not None and any(bc.kind == L.BC_PERIODIC for pair in phi.bcs for bc in pair):
+        raise ValueError(f"{what} with a PeriodicBC dimension is not supported: the faces of the box are natural (zero-flux)")
+    if any(int(m) < 3 for m in phi.mesh.n):
+        raise ValueError(f"{what} needs at least 3 nodes in every dimension")
+    return phi
+
+
+def _host_values(v):
+    """the host array behind a scalar / array / MeshField argument, or None for a device field"""
+    if isinstance(v, ROCMeshField):
+        return None
+    return np.asarray(v.vals if isinstance(v, MeshField) else v, dtype=np.float64)
+
+
+class EllipticSolution:
+    """elliptic_solve's result: `u` (a ROCMeshField on ϕ's backend: coeff.set_values takes it device to device), `iterations`,
+    `relres` (the recursive ‖r‖₂/‖b_free‖₂), `levels` of the hierarchy; energy_density(): the ROCMeshField of
+    e_I = Σ_d mean over the existing sides of k̄·((u_J − u_I)/h_d)² — a|∇u|² at the nodes, the normal speed of a compliance
+    descent; compliance() = ∏h·Σ m f u, reduced on the device."""
+
+    def __init__(self, op, u, f, iterations, relres):
+        self.operator, self.u, self._f, self.iterations, self.relres, self.levels = op, u, f, int(iterations), float(relres), op.levels
+
+    def energy_density(self):
+        op = self.operator
+        e = ROCMeshField(op.backend, self.u.mesh, self.u.bcs)
+        op.backend.elliptic_energy(op._handle(), self.u.buf, e.buf)
+        return e
+
+    def compliance(self):
+        op = self.operator
+        return op.backend.elliptic_compliance(op._handle(), self._f, self.u.buf)
+
+
+class EllipticOperator:
+    """The discrete operator of −∇·(a∇u) + c·u on ϕ's grid and its multigrid hierarchy, kept on the device for repeated solves
+    with new right-hand sides and guesses: solve(f, u0=None, rtol=1e-8, max_iters=500) → EllipticSolution.  The arguments are
+    elliptic_solve's.  ϕ is read once, here: after ϕ has moved, build a new operator.  close() releases the device memory."""
+
+    def __init__(self, phi_or_eq, *, a_in=1.0, a_out=1e-3, a=None, c=0.0, dirichlet=None, level=0.0, precond="mg"):
+        what = "elliptic_solve"
+        self._h = None
+        if precond not in _PRECONDS:
+            raise ValueError(f'{what}: precond must be "mg" or "jacobi", not {precond!r}')
+        a_host = None if a is None or (hasattr(a, "is_cuda")) else np.asarray(a, dtype=np.float64)
+        if a is None:
+            if not (_finite_positive(float(a_in)) and _finite_positive(float(a_out))):
+                raise ValueError(f"{what}: a_in and a_out must be finite and positive")
+            if not math.isfinite(float(level)):
+                raise ValueError(f"{what}: level must be finite")
+        elif a_host is not None and not _finite_positive(a_host):
+            raise ValueError(f"{what}: the cell coefficients `a` must be finite and positive")
+        c_host = _host_values(c)
+        if c_host is not None and not (np.all(np.isfinite(c_host)) and np.all(c_host >= 0)):
+            raise ValueError(f"{what}: c must be finite and not negative")
+        mask = values = None
+        if dirichlet is not None:
+            if not (isinstance(dirichlet, (tuple, list)) and len(dirichlet) == 2):
+                raise TypeError(f"{what}: dirichlet must be a pair (mask, values)")
+            mask = np.asarray(dirichlet[0])
+            if mask.dtype != np.bool_:
+                raise TypeError(f"{what}: the Dirichlet mask must be a boolean array")
+            values = np.asarray(dirichlet[1], dtype=np.float64)
+            if not np.all(np.isfinite(values)):
+                raise ValueError(f"{what}: the Dirichlet values must be finite")
+        if c_host is not None and not np.any(c_host > 0) and (mask is None or not mask.any()):
+            raise ValueError(f"{what}: no fixed node and c = 0 everywhere: the problem is singular")
+        phi = _elliptic_field(phi_or_eq, what)
+        n = tuple(int(m) for m in phi.mesh.n)
+        if mask is not None and mask.shape != n:
+            raise ValueError(f"{what}: the Dirichlet mask has shape {mask.shape}, the grid has {n} nodes")
+        if values is not None and values.ndim and values.shape != n:
+            raise ValueError(f"{what}: the Dirichlet values have shape {values.shape}, the grid has {n} nodes")
+        if mask is not None and mask.all():
+            raise ValueError(f"{what}: every node is fixed")
+        cells = tuple(m - 1 for m in n)
+        if a_host is not None and a_host.ndim and a_host.shape != cells:
+            raise ValueError(f"{what}: `a` has shape {a_host.shape}, the grid has {cells} cells")
+        if c_host is not None and c_host.ndim and c_host.shape != n:
+            raise ValueError(f"{what}: c has shape {c_host.shape}, the grid has {n} nodes")
+        b = self.backend = phi.backend
+        self.mesh, self.bcs, self.precond = phi.mesh, phi.bcs, precond
+        t = b.torch
+        a_dev = None if a is None else b.node_array(a if a_host is None else a_host, "a", cells)
+        c_dev = None
+        if c_host is None:
+            c_dev = b.interior(c.buf).to(t.float64).contiguous().reshape(-1)
+        elif c_host.ndim:
+            c_dev = b.node_array(c_host, "c")
+        self._mask = self._values = fixed = None
+        if mask is not None and mask.any():
+            self._mask = t.from_numpy(np.ascontiguousarray(mask.T)).to(b.device)                      # the interior view's axis order
+            self._values = t.from_numpy(np.ascontiguousarray(np.broadcast_to(values, n).T)).to(b.device)
+            fixed = self._mask.to(t.uint8).contiguous().reshape(-1)
+        try:
+            self._h, stats = b.elliptic_create(None if a is not None else phi.buf, level, a_in, a_out, a_dev, 0.0 if c_dev is not None else float(c_host),
+                                               c_dev, fixed, _PRECONDS[precond])
+        except L.LsmError as e:
+            why = _ELLIPTIC_REFUSALS.get(getattr(e, "reason", 0))
+            if why is None:
+                raise
+            raise ValueError(f"{what}: {why}") from None
+        self.levels, self.free_nodes, self.fixed_nodes = stats[0], stats[1], stats[2]
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the EllipticOperator is closed")
+        return self._h
+
+    def _field(self, u0):
+        """a new field holding the guess (zero without one) and the Dirichlet values"""
+        b = self.backend
+        u = ROCMeshField(b, self.mesh, self.bcs)
+        if isinstance(u0, ROCMeshField):
+            if u0.backend is not b:
+                raise ValueError("elliptic_solve: u0 belongs to another field's backend")
+            u.copy_(u0)
+        elif u0 is not None:
+            v = _host_values(u0)
+            u.copy_(np.broadcast_to(v, tuple(int(m) for m in self.mesh.n)))
+        if self._mask is not None:
+            iv = b.interior(u.buf)
+            iv.copy_(b.torch.where(self._mask, self._values.to(iv.dtype), iv))
+        return u
+
+    def solve(self, f, u0=None, rtol=1e-8, max_iters=500):
+        b = self.backend
+        h = self._handle()
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("elliptic_solve: rtol must be positive and finite, max_iters at least 1")
+        if isinstance(f, ROCMeshField):
+            fd = b.interior(f.buf).to(b.torch.float64).contiguous().reshape(-1)
+        else:
+            fd = b.node_array(f if b.torch.is_tensor(f) else _host_values(f), "f")       # a flat float64 device tensor is taken as it is
+        u = self._field(u0)
+        try:
+            it, rel = b.elliptic_solve(h, fd, u.buf, rtol, int(max_iters))
+        except L.LsmNotConvergedError:
+            raise
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                raise ValueError("elliptic_solve: f, u0 and the Dirichlet values must be finite") from None
+            raise
+        return EllipticSolution(self, u, fd, it, rel)
+
+    def apply(self, x):
+        """A x on all nodes, no elimination: x a host array of the grid's shape; returns one (for tests and diagnostics)"""
+        b = self.backend
+        n = tuple(int(m) for m in self.mesh.n)
+        y = b.elliptic_apply(self._handle(), b.node_array(np.asarray(x, dtype=np.float64), "x"))
+        return y.cpu().numpy().reshape(n, order="F")
+
+    def cells(self):
+        """the level-0 cell coefficients, a host array of shape n − 1"""
+        n = tuple(int(m) - 1 for m in self.mesh.n)
+        return self.backend.elliptic_cells(self._handle()).cpu().numpy().reshape(n, order="F")
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.elliptic_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def elliptic_solve(phi_or_eq, f, *, a_in=1.0, a_out=1e-3, a=None, c=0.0, dirichlet=None, u0=None, level=0.0, rtol=1e-8, max_iters=500, precond="mg"):
+    """Solve −∇·(a∇u) + c·u = f on the box of ϕ's grid, on the device: the state equation of a level-set shape optimisation with
+    an ersatz material.  Unknowns at the nodes, zero-flux conditions on every face, u fixed on the nodes of
+    `dirichlet=(mask, values)` (a boolean array of the grid's shape — face_mask builds a face's — and a scalar or an array).
+    The coefficient of a cell is a_out + (a_in − a_out)·θ, θ = clamp(½ − (mean of ϕ's corner values − level)/min h, 0, 1): a_in
+    where ϕ < level, a_out outside, the exact fill fraction in between for a distance function with an axis-aligned interface.
+    `a` (a scalar or an array of shape n − 1) gives the cell coefficients directly and ϕ is not read.  `f` and `c` (≥ 0): a
+    scalar, a host array or MeshField, or a ROCMeshField.  Conjugate gradients from `u0` (zero without one) until
+    ‖r‖₂ ≤ rtol·‖b_free‖₂, preconditioned by one multigrid V-cycle (precond="mg") or by the diagonal ("jacobi").  Returns an
+    EllipticSolution.  Raises ValueError / TypeError for what is refused (1-D, a band field, a slab or a field with a comm, a
+    PeriodicBC dimension, fewer than 3 nodes in a dimension, coefficients that are not finite and positive, c < 0, no fixed node
+    with c ≡ 0, non-finite data) and LsmNotConvergedError when max_iters does not suffice.  For repeated solves keep an
+    EllipticOperator."""
+    op = EllipticOperator(phi_or_eq, a_in=a_in, a_out=a_out, a=a, c=c, dirichlet=dirichlet, level=level, precond=precond)
+    try:
+        return op.solve(f, u0=u0, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        op.close()
+        raise
+
+
+def regularize_(g, alpha, rtol=1e-8, max_iters=500):
+    """Replace the device field g by the solution V of (I − α²Δ)V = g with zero-flux faces, in place: the H¹ regularisation of a
+    shape gradient (a velocity that is smooth over the length α).  One elliptic_solve with a = α², c = 1, f = g, from the guess
+    g.  Returns the EllipticSolution (its u is a new field; g holds the same values)."""
+    alpha = float(alpha)
+    if not (alpha > 0 and math.isfinite(alpha)):
+        raise ValueError("regularize_: alpha must be positive and finite")
+    g = _elliptic_field(g, "regularize_")
+    sol = elliptic_solve(g, g, a=alpha * alpha, c=1.0, u0=g, rtol=rtol, max_iters=max_iters)
+    g.copy_(sol.u)
+    sol.operator.close()
+    return sol
+
+
 # ----------------------------------------------------------------------------- meshes of the interior (ext/MMGVolumeExt.jl)
 
 _BAND_MESH_MSG = ("volume_mesh is not supported on NarrowBandMeshField: a band does not hold the interior. "

@@ -405,6 +405,72 @@ class HipBackend:
     def cc_destroy(self, cc):
         self.lib.lsm_cc_destroy(cc)
 
+    # ---- elliptic solves (lsm_elliptic_*)
+    def interior(self, t):
+        """the interior of a padded field as a strided view, the grid's axes reversed (its C order is the grid's axis-0-fastest order)"""
+        N = self.ndim
+        return t.as_strided([int(self.lay.n[d]) for d in reversed(range(N))], [int(self.lay.stride[d]) for d in reversed(range(N))], int(self.lay.origin))
+
+    def node_array(self, v, what, shape=None):
+        """a flat float64 device array, axis 0 fastest, of the grid's shape (or `shape`): from a scalar, a host array or a device tensor"""
+        t = self.torch
+        shape = tuple(self.local_shape()) if shape is None else tuple(shape)
+        count = int(np.prod(shape))
+        if t.is_tensor(v):
+            out = v.to(device=self.device, dtype=t.float64).contiguous().reshape(-1)
+        elif np.ndim(v) == 0:
+            out = t.full((count,), float(v), dtype=t.float64, device=self.device)
+        else:
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError(f"{what} has shape {a.shape}, expected {shape}")
+            out = t.from_numpy(np.array(a.reshape(-1, order="F"))).to(self.device)
+        if out.numel() != count:
+            raise ValueError(f"{what} has {out.numel()} values, expected {count}")
+        return out
+
+    def elliptic_create(self, phi, level, a_in, a_out, a_cells, c_const, c_nodes, fixed, precond):
+        """returns (object, (levels, free nodes, fixed nodes, 0)).  An LsmError raised for the data carries `reason` (include/lsm.h)."""
+        if self.slab is not None:
+            raise L.LsmError("elliptic_create: this backend holds a slab of a decomposed grid; lsm_elliptic_create works on the whole grid of one device")
+        out, stats = C.c_void_p(), (C.c_int64 * 4)()
+        code = self.lib.lsm_elliptic_create(self.h, self.ptr(phi), float(level), float(a_in), float(a_out), self.ptr(a_cells), float(c_const),
+                                            self.ptr(c_nodes), self.ptr(fixed), int(precond), C.byref(out), stats)
+        try:
+            L.check(self.h, code, "lsm_elliptic_create")
+        except L.LsmError as e:
+            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0
+            raise
+        return out, tuple(int(v) for v in stats)
+
+    def elliptic_apply(self, obj, x):
+        y = self.torch.empty_like(x)
+        L.check(self.h, self.lib.lsm_elliptic_apply(obj, self.ptr(x), self.ptr(y)), "lsm_elliptic_apply")
+        return y
+
+    def elliptic_solve(self, obj, f, u, rtol, max_iters):
+        it, rel = C.c_int(0), C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_elliptic_solve(obj, self.ptr(f), self.ptr(u), float(rtol), int(max_iters), C.byref(it), C.byref(rel), None),
+                "lsm_elliptic_solve")
+        return it.value, rel.value
+
+    def elliptic_energy(self, obj, u, e):
+        L.check(self.h, self.lib.lsm_elliptic_energy(obj, self.ptr(u), self.ptr(e)), "lsm_elliptic_energy")
+
+    def elliptic_compliance(self, obj, f, u):
+        out = C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_elliptic_compliance(obj, self.ptr(f), self.ptr(u), C.byref(out)), "lsm_elliptic_compliance")
+        return out.value
+
+    def elliptic_cells(self, obj):
+        n = self.local_shape()
+        out = self.torch.empty(int(np.prod([m - 1 for m in n])), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elliptic_cells(obj, self.ptr(out)), "lsm_elliptic_cells")
+        return out
+
+    def elliptic_destroy(self, obj):
+        self.lib.lsm_elliptic_destroy(obj)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""
