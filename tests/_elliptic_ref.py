@@ -3,7 +3,8 @@
 The problem: −∇·(a∇u) + c·u = f on the box of a dense 2-D or 3-D grid, unknowns at the nodes, natural (zero-flux) faces, a set of
 fixed (Dirichlet) nodes.  Arrays are n-shaped (cells: n−1), axis 0 fastest (Fortran order).  Every function that the device is
 compared with bit for bit (cell_coefficients, Operator.apply, Operator.energy) spells its operation order out; the assembled
-matrix, the V-cycle and PCG are compared to rounding / by iteration counts.
+matrix, the V-cycle and PCG are compared to rounding / by iteration counts; the first PCG iterate, which shows one V-cycle at
+every node, to the rounding of a long-double restatement (first_iterate_ld).
 
   cell      ϕ̄ = (Σ corners, ascending linear index)·2^−N;  θ = min(max(½ − (ϕ̄ − level)/min(h), 0), 1);  a = a_out + (a_in − a_out)·θ
   edge      along d between I and I+e_d: S = Σ a over the existing cells that share it, ascending linear index; k = S·2^−(N−1);
@@ -354,9 +355,9 @@ def build_case(cs):
     """(Hierarchy, f, u0) of a case; an f32 case's ϕ and u0 are rounded to float32 first, as the handle stores them"""
     n, h = cs["n"], cs["h"]
     phi = cs["phi"].astype(cs["dtype"]).astype(np.float64)
-    a = cs["a"] if cs["a"] is not None else cell_coefficients(phi, h, 0.0, cs["a_in"], cs["a_out"])
+    a = cs["a"] if cs["a"] is not None else cell_coefficients(phi, h, cs.get("level", 0.0), cs["a_in"], cs["a_out"])
     hier = Hierarchy(Operator(a, h, cs["c"], cs["fixed"]))
-    u0 = np.zeros(n, order="F")
+    u0 = np.zeros(n, order="F") if cs.get("u0") is None else np.array(cs["u0"], dtype=np.float64, order="F")
     if cs["fixed"] is not None:
         u0[cs["fixed"]] = cs["g"]
     u0 = u0.astype(cs["dtype"]).astype(np.float64)
@@ -380,3 +381,176 @@ def solved(name):
             res[pc] = (u.astype(cs["dtype"]).astype(np.float64), it, rel, ok)
         _SOLVED[name] = res
     return _SOLVED[name]
+
+
+# ---- the first PCG iterate in long double: with u0 = 0 and zero Dirichlet values r₀ = b, so u₁ = α·M b, α = (b·Mb)/(Mb·A Mb) —
+# a solve that stops after one iteration shows M b at every node (tests/test_gpu_elliptic_edges.py).  scipy.sparse has no long
+# double: the operator is applied in the stated order from the float64 coefficients, P and Pᵀ axis by axis from _p1.
+
+LD = np.longdouble
+
+
+def _apply_free_ld(op, x):
+    acc = np.zeros(op.n, dtype=LD)
+    for d in range(op.N):
+        lo, hi = op._sl(d, 1, None), op._sl(d, None, -1)
+        w = op.w[d].astype(LD)
+        acc[lo] = acc[lo] + w * (x[lo] - x[hi])
+        acc[hi] = acc[hi] + w * (x[hi] - x[lo])
+    return np.where(op.free, acc + op.cm.astype(LD) * x, LD(0))
+
+
+def _transfer_ld(x, nf, co, transpose):
+    """P x (coarse → fine, the fine shape nf) or Pᵀ x, one axis at a time"""
+    for d in range(len(nf)):
+        if co[d]:
+            P = _p1(nf[d]).toarray().astype(LD)
+            x = np.moveaxis(np.tensordot(P.T if transpose else P, x, axes=(1, d)), 0, d)
+    return x
+
+
+def _vcycle_ld(hier, r, lev=0):
+    op = hier.ops[lev]
+    D, om = op.D.astype(LD), LD(OMEGA)
+    coarsest = lev == hier.levels - 1
+    x = np.where(op.free, om * r / D, LD(0))
+    for _ in range((NCOARSE if coarsest else NPRE) - 1):
+        x = np.where(op.free, x + om * (r - _apply_free_ld(op, x)) / D, LD(0))
+    if coarsest:
+        return x
+    cop = hier.ops[lev + 1]
+    co = tuple(a != b for a, b in zip(op.n, cop.n))
+    res = np.where(op.free, r - _apply_free_ld(op, x), LD(0))
+    rc = np.where(cop.free, _transfer_ld(res, op.n, co, True) * LD(hier.P[lev][1]), LD(0))
+    x = np.where(op.free, x + _transfer_ld(_vcycle_ld(hier, rc, lev + 1), op.n, co, False), LD(0))
+    for _ in range(NPOST):
+        x = np.where(op.free, x + om * (r - _apply_free_ld(op, x)) / D, LD(0))
+    return x
+
+
+def first_iterate_ld(hier, f, precond="mg"):
+    """u₁ of PCG from u0 = 0 with zero Dirichlet values, every operation in np.longdouble (the coefficients are the float64 ones)"""
+    op = hier.ops[0]
+    b = np.where(op.free, rhs(op, f).astype(LD), LD(0))
+    z = _vcycle_ld(hier, b) if precond == "mg" else np.where(op.free, b / op.D.astype(LD), LD(0))
+    return (np.sum(b * z) / np.sum(z * _apply_free_ld(op, z))) * z
+
+
+def first_iterate_rhs(op):
+    """name → f: a standard normal field and the impulses f = e_j/m_j (so b = e_j: u₁ is a multiple of column j of M) at the upper
+    corner n − 1 (the unpaired last node of every even axis), at n − 2 and at the odd interior node (n//2)|1; a fixed j is left out"""
+    out = {"normal": np.asfortranarray(np.random.default_rng(13).standard_normal(op.n))}
+    for name, j in (("corner", tuple(m - 1 for m in op.n)), ("corner-1", tuple(m - 2 for m in op.n)), ("odd", tuple((m // 2) | 1 for m in op.n))):
+        if op.free[j]:
+            f = np.zeros(op.n, order="F")
+            f[j] = 1.0 / op.m[j]
+            out[name] = f
+    return out
+
+
+# ---- the cases of tests/test_gpu_elliptic_edges.py: what tests/test_gpu_elliptic.py's ten shapes leave out
+
+_EDGE_CASES = {}
+
+
+def edge_cases():
+    """name → the dict of cases() with the optional keys u0 (the guess, n-shaped; the fixed nodes take g), level, max_iters,
+    solve ("both" | "mg"), direct (False: no sparse direct solve — 3-D fill — and the restatement's distance to its own solve at
+    rtol/100 in its place), big (the two shapes beyond EL_MAXB workgroups: one mg solve, no comparison of u), devfield (c and f are
+    given as device fields)"""
+    if _EDGE_CASES:
+        return _EDGE_CASES
+    rng = np.random.default_rng(19)
+    base = cases()
+    out = _EDGE_CASES
+
+    def add(name, n, hc=None, contrast=1e-3, c=0.0, fixed=None, g=0.0, f=1.0, dtype=np.float64, a_in=1.0, **extra):
+        hc = tuple((nd - 1.0) / (max(n) - 1.0) for nd in n) if hc is None else hc
+        h = tuple(x / (nd - 1) for x, nd in zip(hc, n))
+        out[name] = dict(n=n, hc=hc, h=h, phi=two_holes(n, h), a=None, a_in=a_in, a_out=contrast, c=c, fixed=fixed, g=g, f=f, dtype=dtype, **extra)
+
+    def free_guess(n, fixed):
+        u0 = np.asfortranarray(rng.standard_normal(n))
+        if fixed is not None:
+            u0[fixed] = 0.0
+        return u0
+
+    # node-wise c, on every level
+    n = (24, 33, 10)
+    fixed = _patch(n, 0, 1 / 3, 2 / 3)
+    add("24x33x10_cn", n, c=np.asfortranarray(rng.random(n)), f=rng.standard_normal(n), fixed=fixed, u0=free_guess(n, fixed))
+    n = (6, 6, 6)
+    add("6x6x6_cn_sparse", n, c=np.asfortranarray(rng.random(n) * (rng.random(n) > 0.5)), f=rng.standard_normal(n))
+    n = (64, 48)
+    blob = np.zeros(n, dtype=bool)
+    blob[20:25, 30:34] = True
+    c, f = np.asfortranarray(rng.random(n)), np.asfortranarray(rng.standard_normal(n))
+    add("64x48_cn_devicefield", n, c=c, f=f, fixed=blob, g=1.0, devfield=True)
+    add("64x48_cn_devicefield_f32", n, c=c.astype(np.float32).astype(np.float64), f=f.astype(np.float32).astype(np.float64), fixed=blob, g=1.0,
+        dtype=np.float32, devfield=True)
+    # one-level and minimal hierarchies (a device handle needs at least 4 nodes per dimension: 4x4 is the smallest grid there is)
+    add("5x5_face", (5, 5), fixed=face_mask((5, 5), 0, 0))
+    add("4x4_c", (4, 4), c=1.0, f=rng.standard_normal((4, 4)))
+    add("5x5x5_laplace", (5, 5, 5), fixed=face_mask((5, 5, 5), 2, 1), g=1.0, f=0.0)
+    add("4x5x4_cn", (4, 5, 4), c=np.asfortranarray(rng.random((4, 5, 4))), f=rng.standard_normal((4, 5, 4)))
+    add("6x5_face", (6, 5), fixed=face_mask((6, 5), 0, 0))
+    add("4x40_face", (4, 40), fixed=face_mask((4, 40), 1, 0))
+    add("4x40_side", (4, 40), fixed=face_mask((4, 40), 0, 0))       # the first-iterate test's 4x40: the V-cycle is good enough on it
+    # launch shapes: more than 256 workgroups (the reduction's second pass strides), more than EL_MAXB (a second grid-stride trip)
+    add("300x230", (300, 230), fixed=face_mask((300, 230), 0, 0), max_iters=3000)
+    add("45x41x37", (45, 41, 37), fixed=face_mask((45, 41, 37), 2, 0), direct=False)
+    add("1000x530", (1000, 530), fixed=face_mask((1000, 530), 0, 0), big=True, solve="mg", direct=False)
+    add("83x81x79", (83, 81, 79), fixed=face_mask((83, 81, 79), 2, 0), big=True, solve="mg", direct=False)
+    # a guess that is not zero on the free nodes
+    for name in ("33x33_face", "65x20_aniso_h", "17c_face", "17c_f32"):
+        out[name + "_guess"] = dict(base[name], u0=free_guess(base[name]["n"], base[name]["fixed"]))
+    # a level other than zero, and the stiff material outside
+    n = (64, 48)
+    add("64x48_level", n, fixed=face_mask(n, 0, 0), level=0.03, solve="mg")
+    add("64x48_level_neg", n, fixed=face_mask(n, 0, 0), level=-0.02, a_in=1e-3, contrast=1.0, solve="mg")
+    # a float32 handle in 2-D
+    out["33x33_f32_2d"] = dict(base["33x33_face"], g=0.25, dtype=np.float32)
+    return out
+
+
+_EDGE = {}
+
+
+def edge_case_names(big=None):
+    """the names of the big cases (big=True), of the others (False) or of all"""
+    return sorted(k for k, v in edge_cases().items() if big is None or bool(v.get("big")) == big)
+
+
+def edge_solved(name):
+    """solved() for an edge case: direct is None where the case has no direct solve, and then `tight` holds
+    |u(rtol) − u(rtol/100)|∞ of the restatement per preconditioner (not for a big case); a preconditioner the case does not run is None"""
+    if name not in _EDGE:
+        cs = edge_cases()[name]
+        hier, f, u0 = build_case(cs)
+        want_direct = cs.get("direct", True)
+        res = dict(case=cs, hier=hier, f=f, u0=u0, direct=direct(hier.ops[0], f, u0) if want_direct else None, tight={})
+        mi = cs.get("max_iters", 2000)
+        for pc in ("mg", "jacobi"):
+            if pc == "jacobi" and cs.get("solve", "both") == "mg":
+                res[pc] = None
+                continue
+            u, it, rel, ok = pcg(hier, f, u0, 1e-8, mi, pc)
+            if not want_direct and not cs.get("big"):
+                res["tight"][pc] = float(np.abs(u - pcg(hier, f, u0, 1e-10, mi, pc)[0]).max())
+            res[pc] = (u.astype(cs["dtype"]).astype(np.float64), it, rel, ok)
+        _EDGE[name] = res
+    return _EDGE[name]
+
+
+def any_solved(name):
+    return solved(name) if name in cases() else edge_solved(name)
+
+
+# the first-iterate test's shapes: the float64 cases of cases(), the smallest multi-level hierarchies (4x40_side stands for
+# 4x40_face, whose V-cycle leaves 1.32 of the residual after one iteration for one impulse: tests/test_elliptic_host.py), c per
+# node on four levels, and the one-level shapes, where M is the coarsest kernel alone; Jacobi, where u₁ = α·D⁻¹b, on two of them as
+# the trivial control
+FIRST_ITERATE = (sorted(k for k, v in cases().items() if v["dtype"] == np.float64)
+                 + ["6x5_face", "4x40_side", "6x6x6_cn_sparse", "24x33x10_cn", "4x5x4_cn", "5x5x5_laplace", "5x5_face"])
+FIRST_ITERATE_JACOBI = ["64x48_upper_patch", "6x6x6_cn_sparse"]
+FIRST_ITERATE_PAIRS = [(k, "mg") for k in FIRST_ITERATE] + [(k, "jacobi") for k in FIRST_ITERATE_JACOBI]

@@ -1,7 +1,8 @@
 """elliptic_solve without a device: the restatement (tests/_elliptic_ref.py) has the properties the device tests rely on — a
 symmetric operator whose rows sum to c·m, positive definite on the free nodes, exact fill fractions, second-order convergence, a
-symmetric positive V-cycle, fewer V-cycle than Jacobi iterations on every case of tests/test_gpu_elliptic.py — and the Python API
-refuses what needs no device to refuse."""
+symmetric positive V-cycle, fewer V-cycle than Jacobi iterations on every case of tests/test_gpu_elliptic.py and of
+tests/test_gpu_elliptic_edges.py, a first iterate that shows the preconditioner — and the Python API refuses what needs no device
+to refuse."""
 import types
 
 import numpy as np
@@ -104,6 +105,86 @@ def test_the_v_cycle_needs_fewer_iterations_than_jacobi(name):
             print(f"{name} {pc}: {it} iterations, recursive {rel:.6e}, true {tr / bn:.6e}, |u - direct| {np.abs(u - s['direct']).max():.3e}")
             assert tr <= 1.01 * max(rel, 1e-12) * bn + 1e-12 * bn
     assert s["mg"][1] < s["jacobi"][1]
+
+
+# ---- what tests/test_gpu_elliptic_edges.py relies on
+@pytest.mark.parametrize("name,precond", R.FIRST_ITERATE_PAIRS)
+def test_the_first_iterate_shows_the_preconditioner(name, precond):
+    """From u0 = 0 with zero Dirichlet values a solve at rtol = 0.95 stops after exactly one iteration, for every right-hand side
+    of first_iterate_rhs: the relative residual after iteration 1 is ≤ 0.9 (0.95 would do; the margin is for the device's
+    rounding).  Measured, mg: 0.031 … 0.894 over the 63 pairs, the largest 64x48_upper_patch with the corner impulse; jacobi:
+    0.407 … 0.707.  4x40_face fails it (1.317 for the impulse at n − 2; 0.442 … 0.633 for the others: point Jacobi smooths a
+    strip four nodes wide badly), so the same shape with the lower face of axis 0 fixed, 4x40_side, takes its place (0.071 … 0.243).
+    The long-double u₁ (first_iterate_ld, its own apply and transfers) and the float64 one (pcg, scipy's P) agree to
+    0.4e-16 … 6.4e-16 of max|u| (jacobi: 0 … 3.0e-16; each pair's figure is printed): that spread is the device test's yardstick, and 64 ε bounds it here —
+    two statements of the V-cycle that differed in a weight would differ by 1e-3 of max|u| or more."""
+    s = R.any_solved(name)
+    hier = s["hier"]
+    op = hier.ops[0]
+    rhs = R.first_iterate_rhs(op)
+    assert "normal" in rhs and len(rhs) >= 3              # an impulse at a fixed node is left out
+    for fname, f in rhs.items():
+        b = R.rhs(op, f)
+        if fname != "normal":
+            assert np.count_nonzero(b) == 1 and b.max() == 1.0 and op.free[np.unravel_index(np.argmax(b), op.n)]
+        u, it, rel, ok = R.pcg(hier, f, np.zeros(op.n), 0.95, 1, precond)
+        uld = R.first_iterate_ld(hier, f, precond)
+        assert uld.dtype == np.longdouble and np.finfo(np.longdouble).eps < EPS
+        spread = float(np.abs(u - uld).max() / np.abs(uld).max())
+        print(f"{name} {precond} {fname}: relative residual after iteration 1: {rel:.3f}, float64 against long double: {spread:.2e}·max|u|")
+        assert ok and it == 1
+        assert rel <= 0.9
+        assert spread <= 64 * EPS
+
+
+_EDGE_LEVELS = {"24x33x10_cn": [(24, 33, 10), (12, 17, 5), (6, 9, 5), (3, 5, 5)], "6x6x6_cn_sparse": [(6, 6, 6), (3, 3, 3)], "5x5_face": [(5, 5)],
+                "4x4_c": [(4, 4)], "5x5x5_laplace": [(5, 5, 5)], "4x5x4_cn": [(4, 5, 4)], "6x5_face": [(6, 5), (3, 5)],
+                "4x40_face": [(4, 40), (4, 20), (4, 10), (4, 5)], "4x40_side": [(4, 40), (4, 20), (4, 10), (4, 5)]}
+
+
+@pytest.mark.parametrize("name", R.edge_case_names())
+def test_the_edge_cases_converge_and_the_v_cycle_needs_fewer_iterations(name):
+    """the restatement on the cases of tests/test_gpu_elliptic_edges.py, rtol 1e-8: iterations mg / jacobi
+      24x33x10_cn 23/227, 6x6x6_cn_sparse 13/49, 64x48_cn_devicefield 19/361 (float32 handle: the same),
+      5x5_face 5/19, 4x4_c 5/15, 5x5x5_laplace 6/29, 4x5x4_cn 7/33, 6x5_face 7/22, 4x40_face 17/74, 4x40_side 8/41,
+      300x230 25/1529, 45x41x37 18/339 (|u(rtol) − u(rtol/100)|∞ 1.9e-9 / 6.2e-10), 1000x530 28/–, 83x81x79 24/–,
+      33x33_face_guess 14/197, 65x20_aniso_h_guess 23/235, 17c_face_guess 12/159, 17c_f32_guess 12/158,
+      64x48_level 18/–, 64x48_level_neg 33/–, 33x33_f32_2d 13/189
+    so mg < jacobi wherever both run.  A device handle needs at least 4 nodes per dimension (lsm_create), so 4x4 is the smallest
+    grid and 4x40 the strip whose short axis never coarsens; axes of 3 nodes occur on the coarse levels.  The one-level shapes have one level, c per node is positive somewhere and zero somewhere in
+    6x6x6_cn_sparse, and the two big shapes need a second grid-stride trip of 2048·256 threads."""
+    s = R.edge_solved(name)
+    cs, hier = s["case"], s["hier"]
+    if name in _EDGE_LEVELS:
+        assert [o.n for o in hier.ops] == _EDGE_LEVELS[name]
+    for lev, op in enumerate(hier.ops[1:], 1):         # c and the fixed mask are injected: coarse J sits on fine 2J of a coarsened axis
+        fine = hier.ops[lev - 1]
+        sl = tuple(slice(None, None, 2) if a != b else slice(None) for a, b in zip(fine.n, op.n))
+        assert np.array_equal(op.c, fine.c[sl]) and np.array_equal(op.fixed, fine.fixed[sl])
+    for pc in ("mg", "jacobi"):
+        if s[pc] is None:
+            assert pc == "jacobi" and cs["solve"] == "mg"
+            continue
+        u, it, rel, ok = s[pc]
+        print(f"{name} {pc}: {it} iterations, relres {rel:.3e}, levels {[o.n for o in hier.ops]}")
+        assert ok and it < cs.get("max_iters", 2000)
+    if s["jacobi"] is not None:
+        assert s["mg"][1] < s["jacobi"][1]
+    if name == "6x6x6_cn_sparse":
+        assert 0.25 < float((cs["c"] == 0).mean()) < 0.75 and cs["fixed"] is None
+    if cs.get("big"):
+        assert hier.ops[0].free.size > 2048 * 256
+    elif name in ("300x230", "45x41x37"):
+        assert 256 * 256 < hier.ops[0].free.size <= 2048 * 256
+    if cs.get("u0") is not None:
+        assert np.count_nonzero(s["u0"][hier.ops[0].free]) == int(hier.ops[0].free.sum())
+
+
+def test_the_budget_cases_need_at_least_eight_iterations():
+    """test_an_exact_iteration_budget_converges_and_one_less_does_not solves with max_iters = it − 1 ≥ 1"""
+    for name in ("24x33x10_patch", "64x48_blob"):
+        for pc in ("mg", "jacobi"):
+            assert R.solved(name)[pc][1] >= 8
 
 
 # ---- the refusals that need no device
