@@ -15,6 +15,7 @@
 #include <initializer_list>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -128,12 +129,7 @@ __device__ __forceinline__ void kuhn_chunk_sums(unsigned x0, unsigned x1, unsign
     __shared__ unsigned tot[3];
     if (threadIdx.x < 3) tot[threadIdx.x] = 0;
     __syncthreads();
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        x0 += __shfl_xor(x0, d, 64);
-        x1 += __shfl_xor(x1, d, 64);
-        x2 += __shfl_xor(x2, d, 64);
-    }
+    x0 = wave_sum(x0); x1 = wave_sum(x1); x2 = wave_sum(x2);
     if ((threadIdx.x & 63) == 0) { atomicAdd(&tot[0], x0); atomicAdd(&tot[1], x1); atomicAdd(&tot[2], x2); }
     __syncthreads();
     if (threadIdx.x < 3) sums[threadIdx.x * nchunk + blockIdx.x] = tot[threadIdx.x];

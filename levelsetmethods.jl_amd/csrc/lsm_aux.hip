@@ -2,6 +2,7 @@
 // extrema, Eikonal sign map.  Built with -ffp-contract=off: ghost values and the CFL minimum are
 // bit-for-bit those of the reference arithmetic (they cost nothing next to a stage).
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -269,26 +270,9 @@ void launch_ghost_fill_all(int ndim, const GhostAllArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// NaN-propagating min reduction helpers (Julia's min(x, NaN) = NaN, src/levelsetterms.jl:31-38).
-// The minimum over non-NaN values and an "any NaN" flag are reduced separately.
+// NaN-propagating min reduction (Julia's min(x, NaN) = NaN, src/levelsetterms.jl:31-38).
+// The minimum over non-NaN values (wave_min, wave_max) and an "any NaN" flag are reduced separately.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 #define CFL_MAX_CHUNK 512   // planes per march chunk staged in LDS (launcher keeps chunk <= this)
 
 // Per-node CFL of one term (src/levelsetterms.jl:90-96,123-127,172-178).  The node formulas are
@@ -702,11 +686,6 @@ void launch_extrema(int /*ndim*/, const int n[3], long long s1, long long s2, lo
 // times prod(h).  One partial sum per workgroup (wave shuffles + LDS, fixed order), summed by a
 // second tiny kernel: deterministic, and equal to the reference's pairwise sum up to rounding.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 __device__ __forceinline__ double smooth_heaviside(double x, double alpha) {   // src/levelsetops.jl:171-179
     if (x > alpha) return 1.0;
     if (x < -alpha) return 0.0;
@@ -1016,7 +995,3 @@ void launch_eikonal_sign(int /*ndim*/, const int n[3], long long s1, long long s
 }
 
 }  // namespace lsm
-
-// SemiImplicitI2OE (lsm_advance_i2oe) is compiled in this translation unit.  make does not track the include: touch this
-// file after editing lsm_i2oe.hip.
-#include "lsm_i2oe.hip"

@@ -21,6 +21,7 @@
 // Built with -ffp-contract=off.
 #include <cstdlib>
 #include "lsm_internal.h"
+#include "wave.h"
 
 #define LSM_BAND_LDS 40960   // bytes of LDS for a tile + apron of byte flags
 
@@ -264,7 +265,7 @@ __global__ void __launch_bounds__(256) band_status_kernel(const unsigned* halo_c
     for (int s = 0; s < pf.n; ++s) {
         double best = 0.0;
         for (int i = threadIdx.x; i < pf.npartials; i += 256) { const double v = pf.partial[s * pf.npartials + i]; best = v > best ? v : best; }
-        for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(best, off, 64); best = o > best ? o : best; }
+        best = wave_max(best);
         if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = best;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -306,11 +307,7 @@ __device__ __forceinline__ void finish_node(const BandArgs& a, long long q, cons
     const long long qp = a.origin + P[0] + P[1] * a.s1 + P[2] * a.s2;
     if (list) {
         // one atomic per wave: the lanes that reach this point together take consecutive slots
-        const unsigned long long bal = __ballot(1);
-        const int lane = threadIdx.x & 63, leader = __ffsll((long long)bal) - 1;
-        unsigned base = 0;
-        if (lane == leader) base = atomicAdd(list_count, (unsigned)__popcll(bal));
-        const unsigned k = __shfl(base, leader, 64) + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+        const unsigned k = wave_append(true, list_count);
         if (k < list_cap) {
             BandEntry e;
             e.q = q; e.rel = (int)(qp - q);
@@ -708,7 +705,7 @@ __global__ void __launch_bounds__(256) band_search3_kernel(BandArgs a, const uns
     // The (node, nearest band node) pairs of the tile are appended with ONE global atomic per block and
     // J·npg planes: lanes take tile-local slots through an LDS counter first.
     __shared__ unsigned s_cnt, s_base;
-    const int lx = tx_ + RL, ly = ty_ + RL, lane = threadIdx.x & 63;
+    const int lx = tx_ + RL, ly = ty_ + RL;
     for (int i0 = 0; i0 < a.tm; i0 += J * npg) {
         if (threadIdx.x == 0) s_cnt = 0;
         __syncthreads();
@@ -756,15 +753,7 @@ __global__ void __launch_bounds__(256) band_search3_kernel(BandArgs a, const uns
                 finish_node(a, q, I, P, found, src_mask, src, dst, miss, nullptr, nullptr, 0);
                 if (found) rec[j] = 0x8000u | (unsigned)(I[0] - P[0] + 8) | ((unsigned)(I[1] - P[1] + 8) << 4) | ((unsigned)(I[2] - P[2] + 8) << 8);
             }
-            if (list) {
-                const u64 bal = __ballot(rec[j] != 0);
-                if (bal) {
-                    const int leader = __ffsll((long long)bal) - 1;
-                    unsigned base = 0;
-                    if (lane == leader) base = atomicAdd(&s_cnt, (unsigned)__popcll(bal));
-                    slot[j] = __shfl(base, leader, 64) + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-                }
-            }
+            if (list) slot[j] = wave_append(rec[j] != 0, &s_cnt);
         }
         if (list) {
             __syncthreads();
@@ -1175,8 +1164,7 @@ __global__ void __launch_bounds__(256) band_halo_bits_kernel(BandArgs a, const u
     if (threadIdx.x < 64) {
         const int l = (int)threadIdx.x;
         const unsigned c0 = 2 * l < wpt ? (unsigned)__builtin_popcount(cnt[2 * l]) : 0u, c1 = 2 * l + 1 < wpt ? (unsigned)__builtin_popcount(cnt[2 * l + 1]) : 0u;
-        unsigned inc = c0 + c1;
-        for (int o = 1; o < 64; o <<= 1) { const unsigned vv = __shfl_up(inc, o, 64); if (l >= o) inc += vv; }
+        const unsigned inc = wave_incl_scan(c0 + c1);
         const unsigned ex = inc - (c0 + c1);
         if (2 * l < wpt) offs[2 * l] = ex;
         if (2 * l + 1 < wpt) offs[2 * l + 1] = ex + c0;
@@ -1392,10 +1380,6 @@ __global__ void __launch_bounds__(1024) band_lists_kernel(BandArgs a, const unsi
         return r;
     };
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto wave_sum = [&](unsigned v) {
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        return v;
-    };
     // offset of this chunk = set flags in the chunks before it
     unsigned pa = 0, pw = 0;
     for (unsigned cb = 0; cb < blockIdx.x; ++cb) {
@@ -1409,11 +1393,7 @@ __global__ void __launch_bounds__(1024) band_lists_kernel(BandArgs a, const unsi
     const unsigned t0 = blockIdx.x * LISTS_CHUNK + threadIdx.x * 8;
     const unsigned long long fa = flags8(active, t0), fw = flags8(work, t0);
     const unsigned na = nz_bytes(fa), nw = nz_bytes(fw);
-    unsigned ia = na, iw = nw;                                    // inclusive wave scans
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned va = __shfl_up(ia, off, 64), vw = __shfl_up(iw, off, 64);
-        if ((int)lane >= off) { ia += va; iw += vw; }
-    }
+    unsigned ia = wave_incl_scan(na), iw = wave_incl_scan(nw);
     if (lane == 63) { wsum[0][wave] = ia; wsum[1][wave] = iw; }
     __syncthreads();
     unsigned offa = 0, offw = 0, tota = 0, totw = 0;
@@ -1450,7 +1430,7 @@ __global__ void __launch_bounds__(256) band_count_kernel(BandArgs a, const unsig
     LSM_TILE_PROLOGUE(a)
     unsigned long long c = 0;
     LSM_TILE_FOR(a, x, y, m, q) c += mask[q] ? 1 : 0;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 

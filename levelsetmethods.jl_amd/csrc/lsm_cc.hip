@@ -88,8 +88,7 @@ __device__ __forceinline__ void cc_union(unsigned* parent, unsigned a, unsigned 
 
 // the workgroup's sum of x added to *dst by one atomic.  Every thread calls this.
 __device__ __forceinline__ void cc_block_add(unsigned x, unsigned* s_tot, unsigned long long* dst) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
+    x = wave_sum(x);
     if ((threadIdx.x & 63) == 0 && x) atomicAdd(s_tot, x);
     __syncthreads();
     if (threadIdx.x == 0 && *s_tot) atomicAdd(dst, (unsigned long long)*s_tot);
@@ -202,8 +201,7 @@ __global__ void __launch_bounds__(256) cc_flatten_kernel(CcArgs a, unsigned* par
         parent[i] = r;
         roots += r == (unsigned)i;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) roots += __shfl_xor(roots, d, 64);
+    roots = wave_sum(roots);
     if ((threadIdx.x & 63) == 0 && roots) atomicAdd(&s_tot, roots);
     __syncthreads();
     if (threadIdx.x == 0) sums[blockIdx.x] = s_tot;

@@ -35,6 +35,7 @@
 #include <thread>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace {
 
@@ -453,7 +454,7 @@ __device__ __forceinline__ unsigned nz_bytes16(const unsigned char* p, size_t of
     return (unsigned)__builtin_popcount(bits);
 }
 __device__ __forceinline__ unsigned block_sum256(unsigned v, unsigned* sh) {      // sum over a 256-thread block; sh: 4 words
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = lsm::wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     const unsigned t = sh[0] + sh[1] + sh[2] + sh[3];
@@ -490,14 +491,8 @@ __global__ void __launch_bounds__(256) nz_write_kernel(const unsigned char* p, s
     unsigned bits;
     const size_t off = (size_t)blockIdx.x * NZ_CHUNK + threadIdx.x * 16;
     const unsigned c = nz_bytes16(p, off, n, bits);
-    unsigned inc = c;                                   // inclusive scan over the wave, then over the 4 waves
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(inc, o, 64); if ((int)lane >= o) inc += v; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned base = offsets[blockIdx.x];
-    for (unsigned w = 0; w < wave; ++w) base += wsum[w];
-    unsigned k = base + inc - c;
+    unsigned total;
+    unsigned k = offsets[blockIdx.x] + lsm::block_excl_scan<4>(c, wsum, total);
     for (int j = 0; j < 16; ++j)
         if ((bits >> j) & 1u) { if (k < cap) out[k] = (unsigned)(off + j); ++k; }
 }

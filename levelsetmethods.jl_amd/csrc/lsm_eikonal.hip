@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -185,13 +186,8 @@ __global__ void __launch_bounds__(256) ek_compact_kernel(unsigned char* next, lo
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool on = i < ntile && next[i];
     if (on) next[i] = 0;
-    const unsigned long long m = __ballot(on);
-    if (!m) return;
-    const int lane = threadIdx.x & 63;
-    unsigned base = 0;
-    if (lane == 0) base = atomicAdd(count, (unsigned)__popcll(m));
-    base = __shfl(base, 0, 64);
-    if (on) list[base + __popcll(m & ((1ULL << lane) - 1ULL))] = (int)i;
+    const unsigned k = wave_append(on, count);
+    if (on) list[k] = (int)i;
 }
 
 // one workgroup per listed tile, one thread per node of the tile.  Every global index is checked against the grid: a partial

@@ -13,7 +13,7 @@
 //   [z = M r, ρ' = r·z, β = ρ'/ρ]   the V-cycle, whose last sweep carries the dot product — or, for M = D⁻¹, part of K2
 //   K1  p' = z + β p (p double-buffered: neighbours read the old one),  q = A p',  σ = p'·q   → α = ρ/σ
 //   K2  x += α p',  r −= α q,  r·r → converged?  (Jacobi: z = r/D, ρ' = r·z as well)
-// Reductions as in lsm_i2oe.hip: one partial per workgroup, the last workgroup to draw a ticket sums them in workgroup order and
+// Reductions by wave.h's block_reduce_ordered: one partial per workgroup, the last workgroup to draw a ticket sums them in workgroup order and
 // updates the scalars; every kernel returns at once when the device status is set, the host enqueues iterations in chunks and
 // reads the status once per chunk.
 //
@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -133,58 +134,7 @@ __device__ __forceinline__ double el_apply_free(const ElLevel& L, int id, const 
     return el_apply<N>(L, id, I, x[id], [&](int q) { return el_fixed(L, q) ? 0.0 : x[q]; });
 }
 
-__device__ __forceinline__ double el_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ bool el_finite(double x) { return x - x == 0.0; }
-
-// block sum of K values, one partial per workgroup, and the last workgroup's total (true in that workgroup only): lsm_i2oe.hip's
-template <int K>
-__device__ bool el_reduce(double (&v)[K], double* partial, unsigned* ticket) {
-    __shared__ double red[K][EL_THREADS / 64];
-    __shared__ int last;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = el_wave_sum(v[k]);
-        if (lane == 0) red[k][wave] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) partial[k * gridDim.x + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = tk == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!last) return false;
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        acc[k] = 0.0;
-        for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) acc[k] += partial[k * gridDim.x + b];
-    }
-    __syncthreads();   // red is reused
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = el_wave_sum(acc[k]);
-        if (lane == 0) red[k][wave] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
 
 #define EL_LOOP(id, nn) for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < (nn); id += gridDim.x * blockDim.x)
 
@@ -228,9 +178,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_setup_kernel(ElLevel L, ElField
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        unsigned v = cnt[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const unsigned v = wave_sum(cnt[k]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&st[k], (unsigned long long)v);
     }
 }
@@ -348,7 +296,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_compliance_kernel(ElLevel L, El
         el_coords<N>(L, id, I);
         red[0] += (el_mass<N>(L, I) * f[id]) * ld_val(u, el_padded(F, I), F.f32);
     }
-    if (!el_reduce<1>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<1, EL_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
     st->out = red[0];
 }
 
@@ -393,7 +341,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_init_kernel(ElLevel L, ElField 
         V.p[0][id] = 0.0;
         if (jac) V.z[id] = z;
     }
-    if (!el_reduce<4>(red, V.partial, &V.st->ticket[0]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<4, EL_THREADS>(red, V.partial, &V.st->ticket[0]) || threadIdx.x != 0) return;
     ElState& S = *V.st;
     S.bb = red[0] > 0.0 ? red[0] : red[1];      // f ≡ 0 on the free nodes: the norm of the eliminated right-hand side
     S.rr = red[1];
@@ -430,7 +378,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_k1_kernel(ElLevel L, ElVec V, i
         pn[id] = pp;
         V.q[id] = q;
     }
-    if (!el_reduce<1>(red, V.partial, &V.st->ticket[1]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<1, EL_THREADS>(red, V.partial, &V.st->ticket[1]) || threadIdx.x != 0) return;
     ElState& S = *V.st;
     const double alpha = S.rho / red[0];
     if (!(red[0] > 0.0) || !el_finite(alpha)) { S.status = EL_BREAK_SIGMA; return; }
@@ -455,7 +403,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_k2_kernel(ElLevel L, ElVec V, i
             red[1] += r * z;
         }
     }
-    if (!el_reduce<2>(red, V.partial, &V.st->ticket[2]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<2, EL_THREADS>(red, V.partial, &V.st->ticket[2]) || threadIdx.x != 0) return;
     ElState& S = *V.st;
     S.iters += 1;
     S.rr = red[0];
@@ -500,7 +448,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_smooth_kernel(ElLevel L, const 
         xn[id] = v;
     }
     if (DOT) {
-        if (!el_reduce<1>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
+        if (!block_reduce_ordered<1, EL_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
         el_rho_update(*st, red[0]);
     }
 }
@@ -649,7 +597,7 @@ __global__ void __launch_bounds__(128) el_coarsest_kernel(ElLevel L, const doubl
     }
     if (id < L.nn) x[id] = v;
     if (DOT) {
-        const double s = el_wave_sum(ri * v);
+        const double s = wave_sum(ri * v);
         if ((id & 63) == 0) red[id >> 6] = s;
         __syncthreads();
         if (id == 0) el_rho_update(*st, red[0] + red[1]);

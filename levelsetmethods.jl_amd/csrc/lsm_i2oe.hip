@@ -1,8 +1,6 @@
 // lsm_i2oe.hip — SemiImplicitI2OE (src/timestepping.jl:204-426): one semi-implicit advection step, the global linear
 // system solved on the device by unpreconditioned BiCGSTAB, matrix-free.
 //
-// Compiled as part of lsm_aux.hip (#include at its end); make does not track this file, touch lsm_aux.hip after editing it.
-//
 // The system.  With fac = Δt/(2·Πh), the face measure Π_{e≠d} h_e (1 in 1-D) and the face velocity v_f (½(v_p + v_q) for an
 // ordinary neighbour q, v_p for a LinearExtrapolationBC ghost), every face f of dimension d carries ONE signed coefficient
 //     c_f = fac · (area_d · v_f)
@@ -32,6 +30,7 @@
 #include <cstring>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -137,53 +136,6 @@ __device__ __forceinline__ double i2_matvec(const I2Args& a, unsigned id, const 
     return y;
 }
 
-// block sum of K values, one partial per workgroup, and the last workgroup's total (true in that workgroup only)
-template <int K>
-__device__ bool i2_reduce(double (&v)[K], double* partial, unsigned* ticket) {
-    __shared__ double red[K][I2_THREADS / 64];
-    __shared__ int last;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) red[k][wave] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) partial[k * gridDim.x + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-        // publish the partials, then take a ticket (agent-scope release before the relaxed add; acquire in the last one)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = tk == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!last) return false;
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        acc[k] = 0.0;
-        for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) acc[k] += partial[k * gridDim.x + b];
-    }
-    __syncthreads();   // red is reused
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(acc[k]);
-        if (lane == 0) red[k][wave] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
-
 __device__ __forceinline__ bool i2_finite(double x) { return x - x == 0.0; }
 
 // ---- assembly: the face coefficients of dimension d (one thread per face)
@@ -245,7 +197,7 @@ __global__ void __launch_bounds__(I2_THREADS) i2oe_init_kernel(const I2Args a) {
         red[0] += rhs * rhs;
         red[1] += r * r;
     }
-    if (!i2_reduce<2>(red, a.partial, &a.st->ticket[0]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<2, I2_THREADS>(red, a.partial, &a.st->ticket[0]) || threadIdx.x != 0) return;
     I2State& S = *a.st;
     S.bb = red[0];
     S.rr = red[1];
@@ -277,7 +229,7 @@ __global__ void __launch_bounds__(I2_THREADS) i2oe_k1_kernel(const I2Args a, int
         vn[id] = y;
         red[0] += a.rh[id] * y;
     }
-    if (!i2_reduce<1>(red, a.partial, &a.st->ticket[1]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<1, I2_THREADS>(red, a.partial, &a.st->ticket[1]) || threadIdx.x != 0) return;
     I2State& S = *a.st;
     const double alpha = S.rho / red[0];
     if (red[0] == 0.0 || !i2_finite(alpha)) { S.status = I2_BREAK_SIGMA; return; }
@@ -303,7 +255,7 @@ __global__ void __launch_bounds__(I2_THREADS) i2oe_k2_kernel(const I2Args a, int
         red[1] += t * t;
         red[2] += s * s;
     }
-    if (!i2_reduce<3>(red, a.partial, &a.st->ticket[2]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<3, I2_THREADS>(red, a.partial, &a.st->ticket[2]) || threadIdx.x != 0) return;
     I2State& S = *a.st;
     if (red[2] <= S.rtol2 * S.bb) { S.omega = 0.0; return; }   // x += α p solves it: K3 finds r = s converged
     const double omega = red[0] / red[1];
@@ -325,7 +277,7 @@ __global__ void __launch_bounds__(I2_THREADS) i2oe_k3_kernel(const I2Args a, int
         red[0] += a.rh[id] * r;
         red[1] += r * r;
     }
-    if (!i2_reduce<2>(red, a.partial, &a.st->ticket[3]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<2, I2_THREADS>(red, a.partial, &a.st->ticket[3]) || threadIdx.x != 0) return;
     I2State& S = *a.st;
     S.iters += 1;
     S.rr = red[1];

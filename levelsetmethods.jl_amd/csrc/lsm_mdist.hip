@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -318,12 +319,7 @@ __global__ void __launch_bounds__(256) md_final_kernel(MdArgs a, const unsigned 
     unsigned near = 0;
     for (int i0 = 0; i0 < a.n[0]; i0 += 64) {
         const int i = i0 + lane;
-        int s = i < a.n[0] ? flips[bf + i] : 0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(s, d, 64);
-            if (lane >= d) s += t;
-        }
+        const int s = wave_incl_scan(i < a.n[0] ? flips[bf + i] : 0);
         if (i < a.n[0]) {
             const unsigned long long bits = d2[bd + i];
             near += bits < a.c2bits;
@@ -333,8 +329,7 @@ __global__ void __launch_bounds__(256) md_final_kernel(MdArgs a, const unsigned 
         carry += __shfl(s, 63, 64);
     }
     const int total = carry + flips[bf + a.n[0]];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) near += __shfl_xor(near, d, 64);
+    near = wave_sum(near);
     if (lane == 0) {
         if (near) atomicAdd(&st[MD_NEAR], (unsigned long long)near);
         if (total != 0) atomicAdd(&st[MD_UNBALANCED], 1ULL);

@@ -395,13 +395,7 @@ __device__ __forceinline__ void qd_line1(const QuadArgs& qa, QLine<NP, NC>& l, i
 }
 
 __device__ __forceinline__ int qd_wave_excl(int v, int& total) {
-    const int lane = threadIdx.x & 63;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
+    const int x = wave_incl_scan(v);
     total = __shfl(x, 63, 64);
     return x - v;
 }
@@ -675,9 +669,7 @@ __global__ void __launch_bounds__(64) quad_cells_kernel(QuadArgs qa, const long 
             qd_run_level<N, N, NC>(qa, S, topmode, o, EMIT, cursor, nfb);
         }
         if (!EMIT) {
-            int c = o.cnt;
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+            const int c = wave_sum(o.cnt);
             if (lane == 0) counts[ci] = (unsigned)c;
         } else if (lane == 0) {
             out_cells[pos[ci]] = cell;

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -321,7 +322,6 @@ __device__ void bernstein_extrema_reg(const ReinitArgs& a, long long q0, double&
 // cand_id has been set to -1 by the caller.
 __global__ void __launch_bounds__(256) reinit_cells_kernel(ReinitArgs a, int* cand_id, long long* maybe, unsigned* maybe_count,
                                                            const long long* node_list, DevCount nlist) {
-    __shared__ unsigned blk_n, blk_base;
     const long long nc = node_list ? count_of(nlist) : ncells(a);
     const long long span = (nc + 255) / 256 * 256;      // whole workgroups reach the barriers
     for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < span; w += (long long)gridDim.x * blockDim.x) {
@@ -360,25 +360,14 @@ __global__ void __launch_bounds__(256) reinit_cells_kernel(ReinitArgs a, int* ca
             if (!node_list) cand_id[c] = -1;
         }
         // one append per workgroup (every thread of it reaches this point: `span` is a multiple of 256)
-        const unsigned long long bal = __ballot(keep);
-        const int lane = threadIdx.x & 63;
-        if (threadIdx.x == 0) blk_n = 0;
-        __syncthreads();
-        unsigned wbase = 0;
-        if (bal && lane == 0) wbase = atomicAdd(&blk_n, (unsigned)__popcll(bal));
-        wbase = __shfl(wbase, 0, 64);
-        __syncthreads();
-        if (threadIdx.x == 0 && blk_n) blk_base = atomicAdd(maybe_count, blk_n);
-        __syncthreads();
-        if (keep) maybe[blk_base + wbase + __popcll(bal & ((1ull << lane) - 1ull))] = c;
+        const unsigned k = block_append<256>(keep, maybe_count);
+        if (keep) maybe[k] = c;
     }
 }
 template <int NV, int NC, int NDIM>   // NV = 0: the general version
 __global__ void __launch_bounds__(256) reinit_cells2_kernel(ReinitArgs a, const long long* maybe, const unsigned* maybe_count, int* cand_id,
                                                             long long* cand_cell, unsigned* cand_count, unsigned cand_cap) {
     const unsigned nmaybe = *maybe_count;          // stays on the device: the launch does not wait for it
-    __shared__ unsigned blk_n, blk_base;
-    const int lane = threadIdx.x & 63;
     for (unsigned base = blockIdx.x * blockDim.x; base < nmaybe; base += gridDim.x * blockDim.x) {     // uniform per workgroup
         const unsigned i = base + threadIdx.x;
         bool keep = false;
@@ -394,19 +383,10 @@ __global__ void __launch_bounds__(256) reinit_cells2_kernel(ReinitArgs a, const 
             keep = !(clo * chi > 0.0);
         }
         // candidate ids: one append to the counter per workgroup
-        const unsigned long long bal = __ballot(keep);
-        if (threadIdx.x == 0) blk_n = 0;
-        __syncthreads();
-        unsigned wbase = 0;
-        if (bal && lane == 0) wbase = atomicAdd(&blk_n, (unsigned)__popcll(bal));
-        wbase = __shfl(wbase, 0, 64);
-        __syncthreads();
-        if (threadIdx.x == 0 && blk_n) blk_base = atomicAdd(cand_count, blk_n);
-        __syncthreads();
+        const unsigned id = block_append<256>(keep, cand_count);
         if (keep) {
             // a candidate beyond what the per-candidate buffers (samples, counts) hold is counted — the host repeats the round with larger
             // buffers — and otherwise left alone: no id may point outside them
-            const unsigned id = blk_base + wbase + __popcll(bal & ((1ull << lane) - 1ull));
             if (id < cand_cap) {
                 cand_id[c] = (int)id;
                 cand_cell[id] = c;
@@ -449,7 +429,6 @@ __global__ void __launch_bounds__(256) reinit_starts_kernel(ReinitArgs a, const 
     const long long total = (long long)ncand * S;
     const int up = a.upsample, up1 = up + 1;
     const int nc_[3] = {a.n[0] - 1, a.ndim > 1 ? a.n[1] - 1 : 1, a.ndim > 2 ? a.n[2] - 1 : 1};
-    const int lane = threadIdx.x & 63;
     for (long long sc = blockIdx.x; sc * (256 * CHUNK) < total; sc += gridDim.x) {
         if (threadIdx.x == 0) nbuf = 0;
         __syncthreads();
@@ -485,14 +464,8 @@ __global__ void __launch_bounds__(256) reinit_starts_kernel(ReinitArgs a, const 
                         }
                 rec = (unsigned long long)id | ((unsigned long long)s << 32);
             }
-            const unsigned long long bal = __ballot(own);
-            if (bal) {
-                const int leader = __ffsll((long long)bal) - 1;
-                unsigned base = 0;
-                if (lane == leader) base = atomicAdd(&nbuf, (unsigned)__popcll(bal));
-                base = __shfl(base, leader, 64);
-                if (own) buf[base + __popcll(bal & ((1ull << lane) - 1ull))] = rec;
-            }
+            const unsigned k = wave_append(own, &nbuf);
+            if (own) buf[k] = rec;
         }
         __syncthreads();
         if (threadIdx.x == 0) gbase = atomicAdd(nstarts, nbuf);
@@ -768,13 +741,8 @@ __global__ void __launch_bounds__(256) reinit_nodes_kernel(ReinitArgs a, long lo
             const long long q = a.origin + (t % a.n[0]) + ((t / a.n[0]) % a.n[1]) * a.s1 + (t / ((long long)a.n[0] * a.n[1])) * a.s2;
             on = a.mask[q] != 0;
         }
-        const unsigned long long bal = __ballot(on);
-        if (!bal) continue;
-        const int lane = threadIdx.x & 63, leader = __ffsll((long long)bal) - 1;
-        unsigned base = 0;
-        if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(bal));
-        base = __shfl(base, leader, 64);
-        if (on && list) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = t;   // list == NULL: count only
+        const unsigned k = wave_append(on, count);
+        if (on && list) list[k] = t;   // list == NULL: count only
     }
 }
 
@@ -1892,8 +1860,7 @@ int sdf_samples(SdfObject* o, double* out, const char** err) {
 }
 void sdf_free(SdfObject* o) { delete o; }
 
-// quadrature (lsm_quad_*) is compiled in this translation unit, on the patch set-up above.  make does not track the include: touch
-// this file after editing lsm_quad.hip.
+// quadrature (lsm_quad_*) is compiled in this translation unit, on the patch set-up above
 #include "lsm_quad.hip"
 
 }  // namespace lsm

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "lsm_handle.h"
+#include "wave.h"
 
 namespace lsm {
 
@@ -305,8 +306,7 @@ __global__ void __launch_bounds__(256) render_brick_kernel(RenderArgs a, unsigne
             pmn = mn; pmx = mx; pbad = bad; pon = on;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) seen |= __shfl_xor(seen, d, 64);
+    seen = wave_or(seen);
     if (lane == 0) raw[((long long)bz * a.nb[1] + by) * a.nb[0] + bx] = (unsigned char)(__popc(seen) == 1 ? __ffs(seen) - 1 : R_MIXED);
 }
 

@@ -97,23 +97,15 @@ __global__ void __launch_bounds__(256) vol_classify_kernel(KuhnArgs a, unsigned 
 // takes KUHN_PER consecutive nodes; the arrays cover whole chunks.
 __global__ void __launch_bounds__(256) vol_offset_kernel(const unsigned char* emask, const long long* off, unsigned* vbase) {
     __shared__ unsigned wsum[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const long long c0 = (long long)blockIdx.x * KUHN_CHUNK + (long long)t * KUHN_PER;
     const uint4 em4 = *reinterpret_cast<const uint4*>(emask + c0);
     const unsigned emw[4] = {em4.x, em4.y, em4.z, em4.w};
     unsigned m = 0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) m += __popc(emw[w]);
-    unsigned incl = m;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    unsigned p = (unsigned)off[blockIdx.x] + incl - m;
-    for (int w = 0; w < wave; ++w) p += wsum[w];
+    unsigned total;
+    unsigned p = (unsigned)off[blockIdx.x] + block_excl_scan<4>(m, wsum, total);
     unsigned o[KUHN_PER];
 #pragma unroll
     for (int e = 0; e < KUHN_PER; ++e) {
@@ -158,28 +150,15 @@ __global__ void __launch_bounds__(256) vol_element_kernel(KuhnArgs a, const unsi
     constexpr int W = N + 1;
     __shared__ __attribute__((aligned(16))) unsigned stage[VOL_CAP * W];
     __shared__ unsigned wsum[2][4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const long long c0 = (long long)blockIdx.x * KUHN_CHUNK;
     long long ebase = off[nchunk + blockIdx.x], ibase = off[2 * nchunk + blockIdx.x];
     for (int k = 0; k < KUHN_PER; ++k) {
         const long long lin = c0 + t + 256 * k;          // the count arrays cover whole chunks, zero past the last node
         const unsigned ec = ecnt[lin], ic = icnt[lin];
         const unsigned x = ec | (ic << 16);              // at most 256·18 and 256·12 per pass: two 16-bit sums in one word
-        unsigned incl = x;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned y = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += y;
-        }
-        if (lane == 63) wsum[k & 1][wave] = incl;
-        __syncthreads();
-        unsigned excl = incl - x, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const unsigned s = wsum[k & 1][w];
-            if (w < wave) excl += s;
-            total += s;
-        }
+        unsigned total;
+        const unsigned excl = block_excl_scan<4>(x, wsum[k & 1], total);    // two buffers: a pass has no barrier after the scan
         const unsigned eoff = excl & 0xffffu, ioff = excl >> 16, etot = total & 0xffffu, itot = total >> 16;
         if (!etot) continue;                             // uniform; no elements, no interface
         const bool full = ec == (unsigned)kuhn_nsimplex(N) && ic == 0;      // no simplex is cut and all are kept: every corner inside

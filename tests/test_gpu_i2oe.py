@@ -81,6 +81,8 @@ CASES = [
     ((33, 29), ("PP", "PP"), "rotation", 2.0), ((33, 29), ("NN", "NN"), "rotation", 4.0), ((33, 29), ("LL", "LL"), "rotation", 0.5),
     ((33, 29), ("PP", "LL"), "separable", 2.0), ((33, 29), ("NN", "PP"), "field", 4.0), ((33, 29), ("LN", "NL"), "callable", 2.0),
     ((33, 29), ("LL", "NN"), "const", 4.0),
+    # 66 563 nodes, 261 workgroups: the last workgroup's sum over the partials takes a second trip, the grid-stride loop one
+    ((259, 257), ("PP", "LL"), "rotation", 2.0),
     ((17, 15, 13), ("PP", "NN", "LL"), "separable", 2.0), ((17, 15, 13), ("LL", "LL", "LL"), "field", 4.0),
     ((17, 15, 13), ("NN", "NN", "NN"), "rotation", 2.0), ((17, 15, 13), ("PP", "PP", "PP"), "const", 0.5),
     ((17, 15, 13), ("NL", "PP", "LN"), "callable", 4.0),
