@@ -552,6 +552,76 @@ int lsm_elliptic_compliance(LsmElliptic* s, const double* f, const void* u, doub
 int lsm_elliptic_cells(LsmElliptic* s, double* a_out_cells);
 void lsm_elliptic_destroy(LsmElliptic* s);
 
+/* ---- elasticity_solve: −∇·σ(u) = f on the box of a dense 2-D or 3-D grid, σ = E(x)·C0(ν):ε(u), the state equation of a
+ *      structural (compliance) shape optimisation with an ersatz material outside the level set; Q1 elements, the N displacement
+ *      components at the nodes, traction-free faces, a caller-given set of fixed displacement components; solved on the device by
+ *      conjugate gradients preconditioned by one geometric multigrid V-cycle (csrc/lsm_elastic.hip, DESIGN.md §7.18;
+ *      tests/_elastic_ref.py restates every operation).  Shapes, ownership, streams and failures are lsm_elliptic_*'s.
+ *      Cell modulus: exactly lsm_elliptic's cell formula with (e_in, e_out) for (a_in, a_out) — the same code, the same bits —
+ *      or e_cells != NULL: the caller's cell array (phi may be NULL then).
+ *      Material at E = 1: mu = 1/(2(1+nu)); lambda = nu/((1+nu)(1−2nu)) in 3-D and for LSM_PLANE_STRAIN, lambda = nu/(1−nu²) for
+ *      LSM_PLANE_STRESS (plane is ignored in 3-D, but must be one of the two).  nu finite with −1 < nu < 0.5.
+ *      Unit element matrix of a level, for a box cell with sides h, scaled by 1/prod h as the scalar operator is:
+ *        K0[(a,i),(b,j)] = (1/prod h)·∫_cell lambda·d_i N_a·d_j N_b + mu·d_j N_a·d_i N_b + delta_ij·mu·grad N_a·grad N_b,
+ *      exact for the multilinear shape functions N_a; corner a has bit d set when it sits on the cell's upper side along d; the row
+ *      index is a·N + i; (2^N·N)² doubles, row-major.  It is computed on the host in fp64, once per level (h doubles on the axes
+ *      that coarsen): G[a,b,i,j] = ∫ d_i N_a d_j N_b is the product over the axes d, ascending from 1.0, of the 1-D factors
+ *      stiffness ((a_d == b_d ? 1 : −1)/h_d: i == j == d), mixed (+1/2 when the differentiated corner has bit d set, else −1/2:
+ *      i != j and d == i takes a's bit, d == j takes b's) and mass (h_d/3 when a_d == b_d, else h_d/6: every other axis);
+ *      K0 = ((lambda·G[a,b,i,j] + mu·G[a,b,j,i]) + [i == j]·mu·(sum_k G[a,b,k,k], k ascending from 0))/(1·h_0·h_1·…).
+ *      lsm_elastic_stiffness copies a level's K0, as the device holds it, into a host array.
+ *      Unknowns: solver vectors are component-major fp64 on the device, x[i·nn + id], id = i0 + n0·(i1 + n1·i2), no ghosts.
+ *      Operator: (A u)_{I,i} = sum over the cells C around I of E_C·(sum_b sum_j K0[(a,i),(b,j)]·u_{b,j}), a = I's corner in C.  The
+ *      cells in ascending order m = 0 … 2^N−1 (bit d of m set: cell index I_d along d, clear: I_d − 1; a = ~m); the inner sum is
+ *      accumulated from +0, corner b ascending, component j fastest; it is then multiplied by E_C; the cell terms are accumulated
+ *      from +0.  A cell that does not exist counts as E = 0 with u = 0 on its missing nodes, which adds a zero.  No contraction.
+ *      Diagonal D_{I,i} = sum_C E_C·K0[(a,i),(a,i)].  Right-hand side b_{I,i} = m_I·f_{I,i} with lsm_elliptic's node mass: a uniform
+ *      traction t on a face normal to d is f = 2t/h_d on that face's nodes, the consistent load.
+ *      Fixed components (fixed: one byte per node, bit i set = component i keeps u as passed; NULL: none, which is refused): clamped
+ *      faces, rollers, symmetry planes.  Elimination as in lsm_elliptic: r0 = b − A u0 on the free components, search directions
+ *      zero on the fixed ones.  A component without a fixed bit anywhere leaves its translation in the null space: refused.  A set
+ *      that still leaves a rotation free (a single roller face, say) is the caller's to avoid: the solve then breaks down or does
+ *      not converge, and says so.
+ *      Hierarchy: lsm_elliptic's, per component (axis d coarsens while n_d > 5, to (n_d+1)/2 nodes; the same prolongation;
+ *      restriction P^T/2^k; coarse cell moduli arithmetic means; the coarse operator the same discretisation with that level's K0;
+ *      a coarse node's bits are fine node 2J's; residuals and corrections zero on fixed components on every level; the coarsest
+ *      level, at most 125 nodes, runs 16 sweeps from zero).  Smoother: point Jacobi, 2 + 2 sweeps, the first from zero, with
+ *      omega_l = min(0.6, 1.9/lambda_l) on level l — 0.6, not the scalar solve's 0.8, which is no convergent smoother for Q1
+ *      elasticity in 3-D; lambda_l bounds lambda_max(D^−1 A) of the level on a uniform grid: the largest eigenvalue, over the 2^N
+ *      corner frequencies theta in {0, pi}^N, of the N×N symbol D^−1/2·Ahat(theta)·D^−1/2 with Ahat_ij = sum_a sum_b s·K0[(a,i),(b,j)]
+ *      (s = −1 where a and b differ on an odd number of the axes with theta_d = pi, else +1) and D_i = sum_a K0[(a,i),(a,i)]; it is
+ *      2.86 on cubes and 2.22 on squares at nu = 0.3, where omega_l = 0.6.  Stretched cells — an axis that stopped coarsening while
+ *      the others go on — push it past 2/0.6, where 0.6 would amplify and the V-cycle would be indefinite.  Point Jacobi still
+ *      bounds the cell aspect ratio the V-cycle copes with: in 3-D its iteration count grows from max h/min h of about 1.5 on
+ *      (DESIGN.md §7.18 has the counts), and from about 3 on the Jacobi preconditioner is the better choice.
+ *      stats[4] (may be NULL) := {levels, free components, fixed components, 0}.  LSM_ERR_INVALID without running anything: a 1-D
+ *      grid, a slab handle or one with a communicator, a periodic dimension, fewer than 3 nodes in a dimension, e_in / e_out not
+ *      finite and positive, a bad nu, an unknown plane or precond.  LSM_ERR_INVALID after the setup kernel, with stats :=
+ *      {−reason, offending entries, 0, 0}: a non-finite phi (1), a cell modulus not finite and positive (2), a component with no
+ *      fixed bit (4; stats[1] := the component), everything fixed (5).
+ *      lsm_elastic_apply: y = A x on all components, no elimination.  lsm_elastic_solve: f is N·nn fp64, component-major; u0, u1
+ *      (, u2: NULL in 2-D) are N distinct dense fields of the handle: in, the guess and the prescribed values; out, the solution
+ *      on the free components, rounded once to the storage type.  LSM_ERR_INVALID: a non-finite f or u.  LSM_ERR_NOT_CONVERGED:
+ *      breakdown or max_iters.  In every failure u is untouched.
+ *      lsm_elastic_energy: e_I = (sum over the existing cells C around I, ascending, of E_C·q_C)/(number of those cells),
+ *      q_C = sum_r u_r·(sum_s K0[r,s]·u_s), both sums from +0 ascending over the cell's 2^N·N corner values: the cell mean of
+ *      E·C0 ε:ε, the integrand of the compliance shape derivative; into a dense field of the handle, rounded once.
+ *      lsm_elastic_compliance: *out := prod h · sum b·u, reduced on the device in workgroup order.
+ *      lsm_elastic_cells copies the level-0 cell moduli into a device buffer. */
+#define LSM_PLANE_STRESS 0
+#define LSM_PLANE_STRAIN 1
+typedef struct LsmElastic LsmElastic;
+int lsm_elastic_create(LsmHandle* h, const void* phi, double level, double e_in, double e_out, const double* e_cells, double nu, int plane,
+                       const void* fixed, int precond, LsmElastic** out, int64_t stats[4]);
+int lsm_elastic_stiffness(LsmElastic* s, int level, double* k0_host);
+int lsm_elastic_apply(LsmElastic* s, const double* x, double* y);
+int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* u2, double rtol, int max_iters, int* iters, double* relres,
+                      void* stream);
+int lsm_elastic_energy(LsmElastic* s, const void* u0, const void* u1, const void* u2, void* e_out);
+int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const void* u1, const void* u2, double* out);
+int lsm_elastic_cells(LsmElastic* s, double* e_out_cells);
+void lsm_elastic_destroy(LsmElastic* s);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

@@ -613,6 +613,62 @@ elliptic_cells!(a, E) = _check(E.h.ptr, ccall((:lsm_elliptic_cells, libhiplsm), 
 
 destroy_elliptic(E) = ccall((:lsm_elliptic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), E.op)
 
+# elasticity_operator: the discrete Q1 operator of −∇·σ(u), σ = E(x)·C₀(ν):ε(u), on ϕ's grid with its multigrid hierarchy
+# (include/lsm.h, lsm_elastic_*).  The cell modulus is E_out + (E_in − E_out)·θ(ϕ), or `E` (a ROCArray{Float64} of size n .- 1);
+# plane :stress or :strain (2-D only); fixed: a ROCArray{UInt8} of the grid's size, bit i-1 set = component i keeps its value (every
+# component needs one somewhere); precond :mg or :jacobi.  Release it with destroy_elasticity.
+function elasticity_operator(ϕ::ROCMeshField, fixed; level = 0.0, E_in = 1.0, E_out = 1e-3, E = nothing, nu = 0.3, plane = :stress, precond = :mg)
+    out, stats = Ref{Ptr{Cvoid}}(), zeros(Int64, 4)
+    _check(ϕ.h.ptr, ccall((:lsm_elastic_create, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Float64}, Float64, Cint, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), level, E_in, E_out, E === nothing ? C_NULL : pointer(E), nu, plane === :strain ? 1 : 0,
+        pointer(fixed), precond === :jacobi ? 1 : 0, out, stats), "lsm_elastic_create")
+    return (; op = out[], h = ϕ.h, levels = stats[1], free = stats[2], fixed = stats[3])
+end
+
+_u3(u) = (pointer(u[1].buf), pointer(u[2].buf), length(u) > 2 ? pointer(u[3].buf) : C_NULL)
+
+# elasticity_solve!: u, a tuple of N fields of the same handle, holds the guess and, on the fixed components, the prescribed values;
+# on return the solution.  f: a ROCArray{Float64} of N·nn values, component-major.  Returns (iterations, relres); a failure leaves u
+# untouched.
+function elasticity_solve!(u, K, f; rtol = 1e-8, max_iters = 500)
+    iters, relres = Ref{Cint}(0), Ref{Float64}(0.0)
+    p = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_solve, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Cint, Ref{Cint}, Ref{Float64}, Ptr{Cvoid}),
+        K.op, pointer(f), p[1], p[2], p[3], rtol, max_iters, iters, relres, C_NULL), "lsm_elastic_solve")
+    return (; iterations = iters[], relres = relres[])
+end
+
+# y = A x on all components, no elimination (x, y: ROCArray{Float64} of N·nn values, component-major)
+elasticity_apply!(y, K, x) = _check(K.h.ptr, ccall((:lsm_elastic_apply, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), K.op, pointer(x), pointer(y)), "lsm_elastic_apply")
+
+# the unit element matrix of a level as the device holds it: a (2^N·N)² host matrix (row-major in C: the matrix is symmetric)
+function elasticity_stiffness(K, level, N)
+    R = (1 << N) * N
+    k0 = zeros(Float64, R, R)
+    _check(K.h.ptr, ccall((:lsm_elastic_stiffness, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), K.op, level, k0), "lsm_elastic_stiffness")
+    return k0
+end
+
+# the energy density E·C₀ε:ε at the nodes into the field e: the normal speed of a compliance descent
+function elasticity_energy!(e::ROCMeshField, K, u)
+    p = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_energy, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), K.op, p[1], p[2], p[3], pointer(e.buf)), "lsm_elastic_energy")
+end
+
+function elasticity_compliance(K, f, u)
+    out = Ref{Float64}(0.0)
+    p = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_compliance, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}), K.op, pointer(f), p[1], p[2], p[3], out), "lsm_elastic_compliance")
+    return out[]
+end
+
+# the level-0 cell moduli into a ROCArray{Float64} of size n .- 1
+elasticity_cells!(a, K) = _check(K.h.ptr, ccall((:lsm_elastic_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), K.op, pointer(a)), "lsm_elastic_cells")
+
+destroy_elasticity(K) = ccall((:lsm_elastic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), K.op)
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

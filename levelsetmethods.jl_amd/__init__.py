@@ -17,7 +17,8 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   update_band_, quadrature, integrate, Quadrature, CellQuadratures, isosurface, export_surface_mesh, InterfaceMesh, Camera, Renderer, render, record_, Image,
                   volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
                   components, remove_components_, prune_, Components,
-                  elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution)
+                  elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
+                  elasticity_solve, ElasticityOperator, ElasticitySolution)
 
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
@@ -32,4 +33,5 @@ __all__ = [
     "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
     "components", "remove_components_", "prune_", "Components",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
+    "elasticity_solve", "ElasticityOperator", "ElasticitySolution",
 ]

@@ -29,6 +29,7 @@ FAST_MAX_ABS = 2.5e34
 COMM_ID_BYTES = 128
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 PRECOND_MG, PRECOND_JACOBI = 0, 1
+PLANE_STRESS, PLANE_STRAIN = 0, 1
 
 
 class LsmGrid(C.Structure):
@@ -159,6 +160,16 @@ _SIGS = [
     ("lsm_elliptic_compliance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("lsm_elliptic_cells", C.c_int, [C.c_void_p, C.c_void_p]),
     ("lsm_elliptic_destroy", None, [C.c_void_p]),
+    ("lsm_elastic_create", C.c_int, [_H, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    ("lsm_elastic_stiffness", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    ("lsm_elastic_apply", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                    C.c_void_p]),
+    ("lsm_elastic_energy", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_compliance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("lsm_elastic_cells", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_destroy", None, [C.c_void_p]),
     ("lsm_extend_along_normals", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_double, C.c_double, C.c_double]),
     ("lsm_band_tile_count", C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),

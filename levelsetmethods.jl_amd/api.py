@@ -2745,6 +2745,222 @@ def regularize_(g, alpha, rtol=1e-8, max_iters=500):
     return sol
 
 
+# ----------------------------------------------------------------------------- elasticity solves (the state equation of a structural optimisation)
+
+_PLANES = {"stress": L.PLANE_STRESS, "strain": L.PLANE_STRAIN}
+_ELASTIC_REFUSALS = {1: "phi must be finite", 2: "the cell moduli must be finite and positive",
+                     4: "component {detail} has no fixed bit anywhere (its translation is in the null space)", 5: "every component of every node is fixed"}
+
+
+def _component_values(v, N, n, what):
+    """the (N,)+n host array behind a scalar, an N-tuple of scalars / arrays, or an array of shape (N,)+n"""
+    if isinstance(v, (tuple, list)):
+        if len(v) != N:
+            raise ValueError(f"{what} has {len(v)} components, the grid has {N} dimensions")
+        return np.stack([np.broadcast_to(np.asarray(c.vals if isinstance(c, MeshField) else c, dtype=np.float64), n) for c in v])
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        return np.broadcast_to(a, (N,) + n)
+    if a.shape != (N,) + n:
+        raise ValueError(f"{what} has shape {a.shape}, expected {(N,) + n} (or {N} components)")
+    return a
+
+
+class ElasticitySolution:
+    """elasticity_solve's result: `u` (a tuple of N ROCMeshFields on ϕ's backend), `iterations`, `relres` (the recursive
+    ‖r‖₂/‖b_free‖₂), `levels` of the hierarchy; energy_density(): the ROCMeshField of e_I = the mean over the cells around I of
+    E_C·(C₀ε:ε averaged over the cell) — the integrand of the compliance shape derivative, the normal speed of a compliance
+    descent (coeff.set_values takes it device to device); compliance() = ∏h·Σ b·u, reduced on the device."""
+
+    def __init__(self, op, u, f, iterations, relres):
+        self.operator, self.u, self._f, self.iterations, self.relres, self.levels = op, tuple(u), f, int(iterations), float(relres), op.levels
+
+    def energy_density(self):
+        op = self.operator
+        e = ROCMeshField(op.backend, self.u[0].mesh, self.u[0].bcs)
+        op.backend.elastic_energy(op._handle(), [c.buf for c in self.u], e.buf)
+        return e
+
+    def compliance(self):
+        op = self.operator
+        return op.backend.elastic_compliance(op._handle(), self._f, [c.buf for c in self.u])
+
+
+class ElasticityOperator:
+    """The discrete Q1 elasticity operator of ϕ's grid and its multigrid hierarchy, kept on the device for repeated solves with
+    new loads and guesses: solve(f, u0=None, rtol=1e-8, max_iters=500) → ElasticitySolution.  The arguments are
+    elasticity_solve's.  ϕ is read once, here: after ϕ has moved, build a new operator.  `levels`, `free_dofs`, `fixed_dofs`;
+    apply(x), cells(), stiffness(level) show the operator; close() releases the device memory."""
+
+    def __init__(self, phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", dirichlet=None, level=0.0, precond="mg"):
+        what = "elasticity_solve"
+        self._h = None
+        if precond not in _PRECONDS:
+            raise ValueError(f'{what}: precond must be "mg" or "jacobi", not {precond!r}')
+        if plane not in _PLANES:
+            raise ValueError(f'{what}: plane must be "stress" or "strain", not {plane!r}')
+        nu = float(nu)
+        if not (math.isfinite(nu) and -1.0 < nu < 0.5):
+            raise ValueError(f"{what}: nu must be finite with -1 < nu < 0.5")
+        E_host = None if E is None or hasattr(E, "is_cuda") else np.asarray(E, dtype=np.float64)
+        if E is None:
+            if not (_finite_positive(float(E_in)) and _finite_positive(float(E_out))):
+                raise ValueError(f"{what}: E_in and E_out must be finite and positive")
+            if not math.isfinite(float(level)):
+                raise ValueError(f"{what}: level must be finite")
+        elif E_host is not None and not _finite_positive(E_host):
+            raise ValueError(f"{what}: the cell moduli `E` must be finite and positive")
+        mask = values = None
+        if dirichlet is not None:
+            if not (isinstance(dirichlet, (tuple, list)) and len(dirichlet) == 2):
+                raise TypeError(f"{what}: dirichlet must be a pair (mask, values)")
+            mask = np.asarray(dirichlet[0])
+            if mask.dtype != np.bool_:
+                raise TypeError(f"{what}: the Dirichlet mask must be a boolean array")
+        phi = _elliptic_field(phi_or_eq, what)
+        n = tuple(int(m) for m in phi.mesh.n)
+        N = len(n)
+        if mask is not None:
+            if mask.shape == n:
+                mask = np.broadcast_to(mask[..., None], n + (N,))
+            elif mask.shape != n + (N,):
+                raise ValueError(f"{what}: the Dirichlet mask has shape {mask.shape}, expected {n} or {n + (N,)}")
+            values = _component_values(dirichlet[1], N, n, f"{what}: the Dirichlet values")
+            if not np.all(np.isfinite(values)):
+                raise ValueError(f"{what}: the Dirichlet values must be finite")
+        for i in range(N):
+            if mask is None or not mask[..., i].any():
+                raise ValueError(f"{what}: component {i} has no fixed bit anywhere: its translation is in the null space")
+        if mask.all():
+            raise ValueError(f"{what}: every component of every node is fixed")
+        cells = tuple(m - 1 for m in n)
+        if E_host is not None and E_host.ndim and E_host.shape != cells:
+            raise ValueError(f"{what}: `E` has shape {E_host.shape}, the grid has {cells} cells")
+        b = self.backend = phi.backend
+        self.mesh, self.bcs, self.precond, self.ndim = phi.mesh, phi.bcs, precond, N
+        t = b.torch
+        E_dev = None if E is None else b.node_array(E if E_host is None else E_host, "E", cells)
+        bits = np.zeros(n, dtype=np.uint8)
+        for i in range(N):
+            bits |= mask[..., i].astype(np.uint8) << np.uint8(i)
+        self._mask = [t.from_numpy(np.array(mask[..., i].T, order="C")).to(b.device) for i in range(N)]      # the interior view's axis order
+        self._values = [t.from_numpy(np.array(values[i].T, order="C")).to(b.device) for i in range(N)]
+        fixed = t.from_numpy(np.array(bits.reshape(-1, order="F"))).to(b.device)
+        try:
+            self._h, stats = b.elastic_create(None if E is not None else phi.buf, level, E_in, E_out, E_dev, nu, _PLANES[plane], fixed, _PRECONDS[precond])
+        except L.LsmError as e:
+            why = _ELASTIC_REFUSALS.get(getattr(e, "reason", 0))
+            if why is None:
+                raise
+            raise ValueError(f"{what}: " + why.format(detail=getattr(e, "detail", 0))) from None
+        self.levels, self.free_dofs, self.fixed_dofs = stats[0], stats[1], stats[2]
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the ElasticityOperator is closed")
+        return self._h
+
+    def _fields(self, u0):
+        """N new fields holding the guess (zero without one) and the prescribed values"""
+        b, N = self.backend, self.ndim
+        n = tuple(int(m) for m in self.mesh.n)
+        if u0 is not None and not (isinstance(u0, (tuple, list)) and all(isinstance(c, ROCMeshField) for c in u0)):
+            u0 = list(_component_values(u0, N, n, "elasticity_solve: u0"))
+        if u0 is not None and len(u0) != N:
+            raise ValueError(f"elasticity_solve: u0 has {len(u0)} components, the grid has {N} dimensions")
+        out = []
+        for i in range(N):
+            u = ROCMeshField(b, self.mesh, self.bcs)
+            if u0 is not None:
+                if isinstance(u0[i], ROCMeshField) and u0[i].backend is not b:
+                    raise ValueError("elasticity_solve: u0 belongs to another field's backend")
+                u.copy_(u0[i])
+            iv = b.interior(u.buf)
+            iv.copy_(b.torch.where(self._mask[i], self._values[i].to(iv.dtype), iv))
+            out.append(u)
+        return out
+
+    def _load(self, f):
+        """f as one flat float64 device array, component-major"""
+        b, N = self.backend, self.ndim
+        t = b.torch
+        n = tuple(int(m) for m in self.mesh.n)
+        if t.is_tensor(f):
+            return b.node_array(f, "f", (N,) + n)
+        if isinstance(f, (tuple, list)) and len(f) == N and all(isinstance(c, ROCMeshField) for c in f):
+            return t.cat([b.interior(c.buf).to(t.float64).contiguous().reshape(-1) for c in f])
+        v = _component_values(f, N, n, "elasticity_solve: f")
+        return t.from_numpy(np.concatenate([v[i].reshape(-1, order="F") for i in range(N)])).to(b.device)
+
+    def solve(self, f, u0=None, rtol=1e-8, max_iters=500):
+        b = self.backend
+        h = self._handle()
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("elasticity_solve: rtol must be positive and finite, max_iters at least 1")
+        fd = self._load(f)
+        u = self._fields(u0)
+        try:
+            it, rel = b.elastic_solve(h, fd, [c.buf for c in u], rtol, int(max_iters))
+        except L.LsmNotConvergedError:
+            raise
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                raise ValueError("elasticity_solve: f, u0 and the Dirichlet values must be finite") from None
+            raise
+        return ElasticitySolution(self, u, fd, it, rel)
+
+    def apply(self, x):
+        """A x on all components, no elimination: x a host array of shape (N,)+n; returns one (for tests and diagnostics)"""
+        b, N = self.backend, self.ndim
+        n = tuple(int(m) for m in self.mesh.n)
+        nn = int(np.prod(n))
+        y = b.elastic_apply(self._handle(), self._load(np.asarray(x, dtype=np.float64))).cpu().numpy()
+        return np.stack([y[i * nn:(i + 1) * nn].reshape(n, order="F") for i in range(N)])
+
+    def cells(self):
+        """the level-0 cell moduli, a host array of shape n − 1"""
+        n = tuple(int(m) - 1 for m in self.mesh.n)
+        return self.backend.elastic_cells(self._handle()).cpu().numpy().reshape(n, order="F")
+
+    def stiffness(self, level=0):
+        """the unit element matrix K0 of a level as the device holds it: (2^N·N)², row a·N + i"""
+        return self.backend.elastic_stiffness(self._handle(), level)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.elastic_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def elasticity_solve(phi_or_eq, f, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", dirichlet=None, u0=None, level=0.0, rtol=1e-8, max_iters=500,
+                     precond="mg"):
+    """Solve −∇·σ(u) = f, σ = E(x)·C₀(ν):ε(u), on the box of ϕ's grid, on the device: the state equation of a structural level-set
+    shape optimisation with an ersatz material.  Q1 elements, the N displacement components at the nodes,
+    traction-free faces.  The modulus of a cell is E_out + (E_in − E_out)·θ with elliptic_solve's fill fraction θ; `E` (a scalar
+    or an array of shape n − 1) gives the cell moduli directly and ϕ is not read.  `plane` ("stress" or "strain") matters in 2-D
+    only.  `dirichlet=(mask, g)` fixes displacement components: the mask is a boolean array of the grid's shape (all components
+    of those nodes) or of shape n + (N,) (component by component: rollers, symmetry planes); g a scalar, an N-tuple or an array of
+    shape (N,) + n.  Every component needs a fixed bit somewhere, and the set must not leave a rotation free.  `f`: N host arrays
+    (or scalars), an array of shape (N,) + n, or N ROCMeshFields; a uniform traction t on a face normal to d is f = 2t/h_d on that
+    face's nodes.  Conjugate gradients from `u0` (zero without one) until ‖r‖₂ ≤ rtol·‖b_free‖₂, preconditioned by one multigrid
+    V-cycle (precond="mg") or by the diagonal ("jacobi").  Returns an ElasticitySolution.  Raises ValueError / TypeError for
+    what is refused (1-D, a band field, a slab, a PeriodicBC dimension, fewer than 3 nodes in a dimension, moduli that are not
+    finite and positive, ν outside (−1, 0.5), an unknown plane, a component that is fixed nowhere, everything fixed, non-finite
+    data) and LsmNotConvergedError when max_iters does not suffice.  For repeated solves keep an ElasticityOperator."""
+    op = ElasticityOperator(phi_or_eq, E_in=E_in, E_out=E_out, E=E, nu=nu, plane=plane, dirichlet=dirichlet, level=level, precond=precond)
+    try:
+        return op.solve(f, u0=u0, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        op.close()
+        raise
+
+
 # ----------------------------------------------------------------------------- meshes of the interior (ext/MMGVolumeExt.jl)
 
 _BAND_MESH_MSG = ("volume_mesh is not supported on NarrowBandMeshField: a band does not hold the interior. "

@@ -471,6 +471,60 @@ class HipBackend:
     def elliptic_destroy(self, obj):
         self.lib.lsm_elliptic_destroy(obj)
 
+    # ---- elasticity solves (lsm_elastic_*): u is a tuple of N padded fields
+    def _u3(self, u):
+        return [self.ptr(t) for t in u] + [None] * (3 - len(u))
+
+    def elastic_create(self, phi, level, e_in, e_out, e_cells, nu, plane, fixed, precond):
+        """returns (object, (levels, free components, fixed components, 0)).  An LsmError raised for the data carries `reason` and
+        `detail` (include/lsm.h)."""
+        if self.slab is not None:
+            raise L.LsmError("elastic_create: this backend holds a slab of a decomposed grid; lsm_elastic_create works on the whole grid of one device")
+        out, stats = C.c_void_p(), (C.c_int64 * 4)()
+        code = self.lib.lsm_elastic_create(self.h, self.ptr(phi), float(level), float(e_in), float(e_out), self.ptr(e_cells), float(nu), int(plane),
+                                           self.ptr(fixed), int(precond), C.byref(out), stats)
+        try:
+            L.check(self.h, code, "lsm_elastic_create")
+        except L.LsmError as e:
+            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0
+            e.detail = int(stats[1])
+            raise
+        return out, tuple(int(v) for v in stats)
+
+    def elastic_stiffness(self, obj, level):
+        R = (1 << self.ndim) * self.ndim
+        out = np.zeros((R, R), dtype=np.float64)
+        L.check(self.h, self.lib.lsm_elastic_stiffness(obj, int(level), out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_elastic_stiffness")
+        return out
+
+    def elastic_apply(self, obj, x):
+        y = self.torch.empty_like(x)
+        L.check(self.h, self.lib.lsm_elastic_apply(obj, self.ptr(x), self.ptr(y)), "lsm_elastic_apply")
+        return y
+
+    def elastic_solve(self, obj, f, u, rtol, max_iters):
+        it, rel = C.c_int(0), C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_elastic_solve(obj, self.ptr(f), *self._u3(u), float(rtol), int(max_iters), C.byref(it), C.byref(rel), None),
+                "lsm_elastic_solve")
+        return it.value, rel.value
+
+    def elastic_energy(self, obj, u, e):
+        L.check(self.h, self.lib.lsm_elastic_energy(obj, *self._u3(u), self.ptr(e)), "lsm_elastic_energy")
+
+    def elastic_compliance(self, obj, f, u):
+        out = C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_elastic_compliance(obj, self.ptr(f), *self._u3(u), C.byref(out)), "lsm_elastic_compliance")
+        return out.value
+
+    def elastic_cells(self, obj):
+        n = self.local_shape()
+        out = self.torch.empty(int(np.prod([m - 1 for m in n])), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_cells(obj, self.ptr(out)), "lsm_elastic_cells")
+        return out
+
+    def elastic_destroy(self, obj):
+        self.lib.lsm_elastic_destroy(obj)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""

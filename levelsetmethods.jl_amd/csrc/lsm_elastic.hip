@@ -1,0 +1,1086 @@
+// lsm_elastic.hip — elasticity_solve: −∇·σ(u) = f, σ = E(x)·C₀(ν):ε(u), on the box of a dense 2-D / 3-D grid with an ersatz material
+// outside the level set: Q1 elements, the N displacement components at the nodes, traction-free faces, a caller-given set of fixed
+// components; solved on the device by conjugate gradients preconditioned with one geometric multigrid V-cycle (or with the
+// diagonal).  DESIGN.md §7.18; include/lsm.h ("elasticity_solve") states the discretisation, tests/_elastic_ref.py restates it.
+// Built with -ffp-contract=off: the cell array, A x and the energy density round as numpy does.
+//
+// Storage.  Solver vectors are fp64, component-major: x[i·nn + id], id = i0 + n0·(i1 + n1·i2).  The cell moduli of a level have n−1
+// entries per axis (lsm_elliptic.hip's cell array: el_cell.h is shared).  The operator is never stored: a node multiplies the unit
+// element matrix K0 of its level — (2^N·N)² doubles in a small device buffer, read at compile-time offsets from a kernel argument,
+// so through scalar loads — with the 3^N neighbours' components, cell by cell, and scales by the cell's modulus.  The diagonal is
+// stored.  The fixed components hold zero in every vector the operator is applied to (search directions, smoother iterates), so
+// the eliminated operator needs no mask on the neighbours; the rows of fixed components are set to zero.
+//
+// One PCG iteration and the V-cycle are lsm_elliptic.hip's, per component, with ω = 0.6: D⁻¹A of Q1 elasticity has eigenvalues
+// above 2/0.8 in 3-D, where the scalar solve's ω = 0.8 is no convergent smoother.  A level with stretched cells
+// takes ω = 1.9/λ instead, λ its symbol bound on λmax(D⁻¹A), where that is smaller: with 0.6 there the V-cycle is indefinite.
+//   dir p = z + β p (a pass of its own, in place);  K1  q = A p,  σ = p·q   → α = ρ/σ
+//   K2  x += α p,  r −= α q,  r·r → converged?  (Jacobi: z = r/D, ρ' = r·z as well)
+// Reductions by wave.h's block_reduce_ordered; every kernel returns at once when the device status is set, the host enqueues
+// iterations in chunks and reads the status once per chunk.
+//
+// The apply (K1, the residual, the smoother) is one thread per node with all N rows: the 3^N·N neighbour values are loaded once
+// into registers (zero where there is no node), then 2^N cells × N rows × 2^N·N columns of multiply and add in the stated order.
+// -DLSM_ES_PRELOAD=0 loads each value where a cell uses it instead (measured: DESIGN.md §7.18).
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "el_cell.h"
+#include "lsm_handle.h"
+#include "wave.h"
+
+namespace lsm {
+
+#ifndef LSM_ES_PRELOAD
+#define LSM_ES_PRELOAD 1
+#endif
+static const int ES_THREADS = 256;
+static const int ES_MAXB = 2048;
+static const int ES_NCOARSE = 16;
+static const double ES_OMEGA = 0.6;
+static const double ES_SAFE = 1.9;      // ω·λmax(D⁻¹A) stays below 2 with this margin where ES_OMEGA would exceed it
+enum { ES_RUN = 0, ES_CONVERGED = 1, ES_MAXITER = 2, ES_BREAK_INPUT = -1, ES_BREAK_SIGMA = -2, ES_BREAK_RHO = -3 };
+enum { ES_BAD_PHI = 0, ES_BAD_E = 1, ES_NFIX = 2 /* 2, 3, 4: per component */, ES_NSTAT = 8 };
+
+struct EsState {
+    double rho, alpha, beta, bb, rr, rtol2, out;
+    int status, iters, max_iters, first;
+    unsigned long long nonfinite;
+    unsigned ticket[4];
+};
+
+struct EsLevel {
+    int n[3];
+    int nn;
+    double h[3];
+    const double* E;              // cell moduli, n−1 per axis
+    const unsigned char* fixed;   // one byte per node: bit i = component i is fixed
+    const double* D;              // the diagonal, component-major
+    const double* K;              // the level's K0, (2^N·N)² row-major
+    double omega;                 // the level's damping: min(ES_OMEGA, ES_SAFE/λ), λ the level's symbol bound (es_symbol_lambda)
+};
+
+// where the fields of the handle live (padded layout)
+struct EsField { long long s1, s2, origin; int f32; };
+struct EsU { void* p[3]; };
+
+template <int N>
+__device__ __forceinline__ void es_coords(const EsLevel& L, int id, int I[3]) {
+    I[0] = id % L.n[0];
+    const int r = id / L.n[0];
+    I[1] = N > 2 ? r % L.n[1] : r;
+    I[2] = N > 2 ? r / L.n[1] : 0;
+}
+__device__ __forceinline__ long long es_padded(const EsField& F, const int I[3]) { return F.origin + I[0] + I[1] * F.s1 + I[2] * F.s2; }
+__device__ __forceinline__ bool es_fixed(const EsLevel& L, int id, int i) { return (L.fixed[id] >> i) & 1; }
+__device__ __forceinline__ bool es_finite(double x) { return x - x == 0.0; }
+
+// cell m of the 2^N around node I (bit d of m set: cell index I_d along d, clear: I_d − 1): its modulus, or zero where there is none
+template <int N>
+__device__ __forceinline__ double es_cell(const EsLevel& L, const int I[3], int m, bool& in) {
+    int C[3] = {0, 0, 0};
+    in = true;
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        C[d] = I[d] - 1 + ((m >> d) & 1);
+        in = in && C[d] >= 0 && C[d] < L.n[d] - 1;
+    }
+    return in ? L.E[C[0] + (L.n[0] - 1) * (C[1] + (N > 2 ? (L.n[1] - 1) * C[2] : 0))] : 0.0;
+}
+template <int N>
+__device__ __forceinline__ double es_mass(const EsLevel& L, const int I[3]) {
+    double m = 1.0;
+#pragma unroll
+    for (int d = 0; d < N; ++d)
+        if (I[d] == 0 || I[d] == L.n[d] - 1) m = m * 0.5;
+    return m;
+}
+
+// (A x)_{I,·} in the stated order: the cells ascending; per cell and row the columns from +0, corner b ascending, component j
+// fastest; then the cell's modulus; the cell terms from +0.  xat(q, o0, o1, o2, j): component j at the node q = I + o, which exists.
+// A cell that does not exist has E = 0 and its missing nodes the value 0: it adds ±0 to a sum that began at +0.
+template <int N, class X>
+__device__ __forceinline__ void es_apply(const EsLevel& L, int id, const int I[3], X xat, double out[N]) {
+    constexpr int NC = 1 << N, NB = N == 2 ? 9 : 27, R = NC * N;
+    const int s1 = L.n[0], s2 = N > 2 ? L.n[0] * L.n[1] : 0;
+    bool lo[3], hi[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        lo[d] = d < N && I[d] > 0;
+        hi[d] = d < N && I[d] < L.n[d] - 1;
+    }
+#if LSM_ES_PRELOAD
+    double v[NB][N];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const int o0 = k % 3 - 1, o1 = (k / 3) % 3 - 1, o2 = N > 2 ? k / 9 - 1 : 0;
+        const bool ex = (o0 >= 0 || lo[0]) && (o0 <= 0 || hi[0]) && (o1 >= 0 || lo[1]) && (o1 <= 0 || hi[1]) && (o2 >= 0 || lo[2]) && (o2 <= 0 || hi[2]);
+        const int q = id + o0 + o1 * s1 + o2 * s2;
+#pragma unroll
+        for (int j = 0; j < N; ++j) v[k][j] = 0.0;
+        if (ex) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) v[k][j] = xat(q, o0, o1, o2, j);
+        }
+    }
+#endif
+    const double* __restrict__ K = L.K;
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+        bool in;
+        const double E = es_cell<N>(L, I, m, in);
+        const int a = (~m) & (NC - 1);
+        double inner[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) inner[i] = 0.0;
+#pragma unroll
+        for (int b = 0; b < NC; ++b) {
+            const int o0 = (m & 1) + (b & 1) - 1, o1 = ((m >> 1) & 1) + ((b >> 1) & 1) - 1, o2 = N > 2 ? ((m >> 2) & 1) + ((b >> 2) & 1) - 1 : 0;
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+#if LSM_ES_PRELOAD
+                const double val = v[(o0 + 1) + 3 * (o1 + 1) + (N > 2 ? 9 * (o2 + 1) : 0)][j];
+#else
+                const double val = in ? xat(id + o0 + o1 * s1 + o2 * s2, o0, o1, o2, j) : 0.0;
+#endif
+#pragma unroll
+                for (int i = 0; i < N; ++i) inner[i] = inner[i] + K[(a * N + i) * R + b * N + j] * val;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) out[i] = out[i] + E * inner[i];
+    }
+}
+
+#define ES_LOOP(id, nn) for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < (nn); id += gridDim.x * blockDim.x)
+
+// ---- setup of level 0: the cell moduli from ϕ (or the caller's, checked), the fixed bits counted per component
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_setup_kernel(EsLevel L, EsField F, const void* __restrict__ phi, double level, double e_in, double e_out,
+                                                              double hmin, const double* __restrict__ e_given, double* __restrict__ E, unsigned long long* st) {
+    unsigned cnt[5] = {0, 0, 0, 0, 0};
+    ES_LOOP(id, L.nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        if (phi && !es_finite(ld_val(phi, es_padded(F, I), F.f32))) ++cnt[ES_BAD_PHI];
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (es_fixed(L, id, i)) ++cnt[ES_NFIX + i];
+        bool corner = true;
+#pragma unroll
+        for (int d = 0; d < N; ++d) corner = corner && I[d] < L.n[d] - 1;
+        if (!corner) continue;
+        const int ci = I[0] + (L.n[0] - 1) * (I[1] + (N > 2 ? (L.n[1] - 1) * I[2] : 0));
+        double ev;
+        if (e_given) {
+            ev = e_given[ci];
+            if (!(ev > 0.0) || !es_finite(ev)) ++cnt[ES_BAD_E];
+        } else {
+            ev = el_cell_from_phi<N>(phi, es_padded(F, I), F.s1, F.s2, F.f32, level, e_in, e_out, hmin);
+            if (!(ev > 0.0)) ++cnt[ES_BAD_E];
+        }
+        E[ci] = ev;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const unsigned v = wave_sum(cnt[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&st[k], (unsigned long long)v);
+    }
+}
+
+// ---- a coarse level from the fine one: cells averaged, the fixed bits of fine node 2J.  co: the axes that coarsen
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_coarsen_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, double* __restrict__ Ec,
+                                                                unsigned char* __restrict__ fixc) {
+    const int co[3] = {co0, co1, co2};
+    const int k = co0 + co1 + co2;
+    const double scale = k == 1 ? 0.5 : k == 2 ? 0.25 : 0.125;
+    ES_LOOP(id, Lc.nn) {
+        int J[3];
+        es_coords<N>(Lc, id, J);
+        const int fid = (co[0] ? 2 * J[0] : J[0]) + Lf.n[0] * ((co[1] ? 2 * J[1] : J[1]) + (N > 2 ? Lf.n[1] * (co[2] ? 2 * J[2] : J[2]) : 0));
+        fixc[id] = Lf.fixed[fid];
+        bool corner = true;
+#pragma unroll
+        for (int d = 0; d < N; ++d) corner = corner && J[d] < Lc.n[d] - 1;
+        if (!corner) continue;
+        double s = 0.0;
+        bool first = true;
+#pragma unroll
+        for (int m = 0; m < (1 << N); ++m) {    // the fine cells {2J, 2J+1} per coarsened axis, ascending
+            int C[3] = {0, 0, 0};
+            bool use = true;
+#pragma unroll
+            for (int d = 0; d < N; ++d) {
+                const int b = (m >> d) & 1;
+                if (!co[d] && b) use = false;
+                C[d] = co[d] ? 2 * J[d] + b : J[d];
+            }
+            if (!use) continue;
+            const double v = Lf.E[C[0] + (Lf.n[0] - 1) * (C[1] + (N > 2 ? (Lf.n[1] - 1) * C[2] : 0))];
+            s = first ? v : s + v;
+            first = false;
+        }
+        Ec[J[0] + (Lc.n[0] - 1) * (J[1] + (N > 2 ? (Lc.n[1] - 1) * J[2] : 0))] = s * scale;
+    }
+}
+
+// ---- the diagonal of a level: D_{I,i} = Σ_C E_C·K0[(a,i),(a,i)]
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_diag_kernel(EsLevel L, double* __restrict__ D) {
+    constexpr int NC = 1 << N, R = NC * N;
+    ES_LOOP(id, L.nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        double acc[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc[i] = 0.0;
+#pragma unroll
+        for (int m = 0; m < NC; ++m) {
+            bool in;
+            const double E = es_cell<N>(L, I, m, in);
+            const int a = (~m) & (NC - 1);
+#pragma unroll
+            for (int i = 0; i < N; ++i) acc[i] = acc[i] + E * L.K[(a * N + i) * R + a * N + i];
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) D[i * L.nn + id] = acc[i];
+    }
+}
+
+// ---- y = A x on all components, no elimination (lsm_elastic_apply)
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_apply_kernel(EsLevel L, const double* __restrict__ x, double* __restrict__ y) {
+    const int nn = L.nn;
+    ES_LOOP(id, nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        double out[N];
+        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
+#pragma unroll
+        for (int i = 0; i < N; ++i) y[i * nn + id] = out[i];
+    }
+}
+
+// ---- the energy density e_I = (Σ_C E_C·q_C)/(existing cells around I), q_C = Σ_r u_r·(Σ_s K0[r,s]·u_s), into a field of the handle
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_energy_kernel(EsLevel L, EsField F, EsU U, void* __restrict__ e_out) {
+    constexpr int NC = 1 << N, R = NC * N;
+    const double* __restrict__ K = L.K;
+    ES_LOOP(id, L.nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        const long long at = es_padded(F, I);
+        double acc = 0.0, cnt = 0.0;
+#pragma unroll 1
+        for (int m = 0; m < NC; ++m) {
+            bool in;
+            const double E = es_cell<N>(L, I, m, in);
+            if (!in) continue;
+            const long long c0 = at + ((m & 1) - 1) + (((m >> 1) & 1) - 1) * F.s1 + (N > 2 ? (((m >> 2) & 1) - 1) * F.s2 : 0);     // the cell's lowest corner
+            double uc[R];
+#pragma unroll
+            for (int b = 0; b < NC; ++b) {
+                const long long o = (b & 1) + ((b >> 1) & 1) * F.s1 + (N > 2 ? ((b >> 2) & 1) * F.s2 : 0);
+#pragma unroll
+                for (int j = 0; j < N; ++j) uc[b * N + j] = ld_val(U.p[j], c0 + o, F.f32);
+            }
+            double q = 0.0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int s = 0; s < R; ++s) t = t + K[r * R + s] * uc[s];
+                q = q + uc[r] * t;
+            }
+            acc = acc + E * q;
+            cnt = cnt + 1.0;
+        }
+        st_val(e_out, at, F.f32, acc / cnt);
+    }
+}
+
+// ---- Πh·Σ b·u is finished on the host: this reduces Σ (m·f)·u over the components
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_compliance_kernel(EsLevel L, EsField F, const double* __restrict__ f, EsU U, double* partial, EsState* st) {
+    double red[1] = {0.0};
+    ES_LOOP(id, L.nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        const double m = es_mass<N>(L, I);
+        const long long at = es_padded(F, I);
+#pragma unroll
+        for (int i = 0; i < N; ++i) red[0] += (m * f[i * L.nn + id]) * ld_val(U.p[i], at, F.f32);
+    }
+    if (!block_reduce_ordered<1, ES_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
+    st->out = red[0];
+}
+
+// ---- PCG
+struct EsVec {
+    double *x, *r, *q, *p, *z;   // z: where the preconditioner leaves M r
+    double* partial;
+    EsState* st;
+};
+
+// x₀ = u (the guess and the prescribed values) as fp64, p = 0
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_load_kernel(EsLevel L, EsField F, EsVec V, EsU U) {
+    const int nn = L.nn;
+    ES_LOOP(id, nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        const long long at = es_padded(F, I);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            V.x[i * nn + id] = ld_val(U.p[i], at, F.f32);
+            V.p[i * nn + id] = 0.0;
+        }
+    }
+}
+// b = m·f, r₀ = b − A x₀ on the free components, 0 on the fixed ones; ‖b_free‖², ‖r₀‖²; jac: z = r/D and ρ = r·z as well
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_init_kernel(EsLevel L, EsVec V, const double* __restrict__ x, const double* __restrict__ f,
+                                                             double* __restrict__ rv, double* __restrict__ zv, int jac) {
+    double red[4] = {0.0, 0.0, 0.0, 0.0};     // ‖b_free‖², ‖r₀‖², r·z, non-finite entries (a count below 2^53: exact)
+    const int nn = L.nn;
+    ES_LOOP(id, nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        const double m = es_mass<N>(L, I);
+        double out[N];
+        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const double ui = x[i * nn + id], fi = f[i * nn + id];
+            if (!es_finite(ui) || !es_finite(fi)) red[3] += 1.0;
+            double r = 0.0, z = 0.0;
+            if (!es_fixed(L, id, i)) {
+                const double b = m * fi;
+                r = b - out[i];
+                red[0] += b * b;
+                red[1] += r * r;
+                if (jac) {
+                    z = r / L.D[i * nn + id];
+                    red[2] += r * z;
+                }
+            }
+            rv[i * nn + id] = r;
+            if (jac) zv[i * nn + id] = z;
+        }
+    }
+    if (!block_reduce_ordered<4, ES_THREADS>(red, V.partial, &V.st->ticket[0]) || threadIdx.x != 0) return;
+    EsState& S = *V.st;
+    S.bb = red[0] > 0.0 ? red[0] : red[1];      // f ≡ 0 on the free components: the norm of the eliminated right-hand side
+    S.rr = red[1];
+    S.rho = red[2];
+    S.alpha = 0.0; S.beta = 0.0;
+    S.iters = 0;
+    S.first = 1;
+    S.nonfinite = (unsigned long long)red[3];
+    if (red[3] > 0.0 || !es_finite(red[0]) || !es_finite(red[1])) S.status = ES_BREAK_INPUT;
+    else if (red[1] <= S.rtol2 * S.bb) S.status = ES_CONVERGED;
+    else if (jac && !(red[2] > 0.0)) S.status = ES_BREAK_RHO;
+    else S.status = ES_RUN;
+    if (jac) S.first = 0;
+}
+
+// the search direction over the nt = N·nn unknowns, in place: p = z + β p (z and p are zero on the fixed components, so p stays zero there)
+__global__ void __launch_bounds__(ES_THREADS) es_dir_kernel(int nt, EsVec V) {
+    if (V.st->status != ES_RUN) return;
+    const double beta = V.st->beta;
+    const double* __restrict__ z = V.z;
+    double* __restrict__ p = V.p;
+    ES_LOOP(k, nt) p[k] = z[k] + beta * p[k];
+}
+// K1: q = A p, σ = p·q, α = ρ/σ.  The direction has a pass of its own, in place: one vector less than lsm_elliptic.hip's double-buffered
+// p, and the apply loads 3^N·N values, not twice as many.  The vectors are __restrict__ parameters, not fields of V: read through
+// the struct, this kernel and es_init_kernel compiled to 3.2 KB of scratch per lane in 3-D.
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_k1_kernel(EsLevel L, const double* __restrict__ p, double* __restrict__ qv, double* partial, EsState* st) {
+    if (st->status != ES_RUN) return;
+    const int nn = L.nn;
+    double red[1] = {0.0};
+    ES_LOOP(id, nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        double out[N];
+        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return p[j * nn + q]; }, out);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double q = 0.0;
+            if (!es_fixed(L, id, i)) {
+                q = out[i];
+                red[0] += p[i * nn + id] * q;
+            }
+            qv[i * nn + id] = q;
+        }
+    }
+    if (!block_reduce_ordered<1, ES_THREADS>(red, partial, &st->ticket[1]) || threadIdx.x != 0) return;
+    EsState& S = *st;
+    const double alpha = S.rho / red[0];
+    if (!(red[0] > 0.0) || !es_finite(alpha)) { S.status = ES_BREAK_SIGMA; return; }
+    S.alpha = alpha;
+}
+
+// K2 over the nt = N·nn unknowns: x += α p, r −= α q, r·r → converged?; JAC: z = r/D, ρ' = r·z, β = ρ'/ρ
+template <int JAC>
+__global__ void __launch_bounds__(ES_THREADS) es_k2_kernel(const double* __restrict__ D, int nt, EsVec V) {
+    if (V.st->status != ES_RUN) return;
+    const double alpha = V.st->alpha;
+    const double* __restrict__ p = V.p;
+    double red[2] = {0.0, 0.0};
+    ES_LOOP(k, nt) {
+        V.x[k] = V.x[k] + alpha * p[k];
+        const double r = V.r[k] - alpha * V.q[k];
+        V.r[k] = r;
+        red[0] += r * r;
+        if (JAC) {
+            const double z = r / D[k];      // r is zero on the fixed components
+            V.z[k] = z;
+            red[1] += r * z;
+        }
+    }
+    if (!block_reduce_ordered<2, ES_THREADS>(red, V.partial, &V.st->ticket[2]) || threadIdx.x != 0) return;
+    EsState& S = *V.st;
+    S.iters += 1;
+    S.rr = red[0];
+    if (red[0] <= S.rtol2 * S.bb) { S.status = ES_CONVERGED; return; }
+    if (!es_finite(red[0])) { S.status = ES_BREAK_RHO; return; }
+    if (JAC) {
+        if (!(red[1] > 0.0) || !es_finite(red[1])) { S.status = ES_BREAK_RHO; return; }
+        S.beta = red[1] / S.rho;
+        S.rho = red[1];
+    }
+    if (S.iters >= S.max_iters) S.status = ES_MAXITER;
+}
+
+// the scalars after z = M r of the V-cycle: ρ' = r·z, β = ρ'/ρ (0 the first time)
+__device__ __forceinline__ void es_rho_update(EsState& S, double rz) {
+    if (!(rz > 0.0) || !es_finite(rz)) { S.status = ES_BREAK_RHO; return; }
+    S.beta = S.first ? 0.0 : rz / S.rho;
+    S.rho = rz;
+    S.first = 0;
+}
+
+// ---- the V-cycle's kernels (any level)
+// first sweep from zero: x = ω r/D, over the N·nn unknowns
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_smooth0_kernel(EsLevel L, const double* __restrict__ r, double* __restrict__ x, const EsState* st) {
+    if (st->status != ES_RUN) return;
+    const int nn = L.nn;
+    ES_LOOP(id, nn) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i * nn + id] = es_fixed(L, id, i) ? 0.0 : (L.omega * r[i * nn + id]) / L.D[i * nn + id];
+    }
+}
+// xn = x + ω (r − A x)/D; DOT (the cycle's last sweep on level 0): r·xn and the scalars
+template <int N, int DOT>
+__global__ void __launch_bounds__(ES_THREADS) es_smooth_kernel(EsLevel L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ xn,
+                                                               double* partial, EsState* st) {
+    if (st->status != ES_RUN) return;
+    const int nn = L.nn;
+    double red[1] = {0.0};
+    ES_LOOP(id, nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        double out[N];
+        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double v = 0.0;
+            if (!es_fixed(L, id, i)) {
+                const double ri = r[i * nn + id];
+                v = x[i * nn + id] + (L.omega * (ri - out[i])) / L.D[i * nn + id];
+                if (DOT) red[0] += ri * v;
+            }
+            xn[i * nn + id] = v;
+        }
+    }
+    if (DOT) {
+        if (!block_reduce_ordered<1, ES_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
+        es_rho_update(*st, red[0]);
+    }
+}
+// the fine residual, zero on the fixed components, written once (into the level's free smoother buffer), then gathered
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_resid_kernel(EsLevel L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ res,
+                                                              const EsState* st) {
+    if (st->status != ES_RUN) return;
+    const int nn = L.nn;
+    ES_LOOP(id, nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        double out[N];
+        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
+#pragma unroll
+        for (int i = 0; i < N; ++i) res[i * nn + id] = es_fixed(L, id, i) ? 0.0 : r[i * nn + id] - out[i];
+    }
+}
+// r_c = Pᵀ res / 2^k per component (blockIdx.y): a coarse node gathers from the fine nodes 2J + o, o ∈ {−1, 0, 1} per coarsened axis
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_gather_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, const double* __restrict__ res,
+                                                               double* __restrict__ rc, const EsState* st) {
+    if (st->status != ES_RUN) return;
+    const int co[3] = {co0, co1, co2};
+    const int k = co0 + co1 + co2;
+    const double scale = k == 1 ? 0.5 : k == 2 ? 0.25 : 0.125;
+    const int comp = blockIdx.y;
+    res += (size_t)comp * Lf.nn;
+    rc += (size_t)comp * Lc.nn;
+    ES_LOOP(id, Lc.nn) {
+        double acc = 0.0;
+        if (!es_fixed(Lc, id, comp)) {
+            int J[3];
+            es_coords<N>(Lc, id, J);
+            for (int m = 0; m < (N == 2 ? 9 : 27); ++m) {
+                const int o[3] = {m % 3 - 1, (m / 3) % 3 - 1, N > 2 ? m / 9 - 1 : 0};
+                int I[3] = {0, 0, 0};
+                double w = 1.0;
+                bool use = true;
+#pragma unroll
+                for (int d = 0; d < N; ++d) {
+                    if (!co[d]) {
+                        if (o[d] != 0) use = false;
+                        I[d] = J[d];
+                        continue;
+                    }
+                    I[d] = 2 * J[d] + o[d];
+                    if (I[d] < 0 || I[d] >= Lf.n[d]) use = false;
+                    if (o[d] == -1 || (o[d] == 1 && J[d] + 1 < Lc.n[d])) w = w * 0.5;     // the unpaired last fine node gives all it has
+                }
+                if (use) acc += w * res[I[0] + Lf.n[0] * (I[1] + (N > 2 ? Lf.n[1] * I[2] : 0))];     // zero on fixed fine components
+            }
+        }
+        rc[id] = acc * scale;
+    }
+}
+// x += P x_c on the free fine components, per component (blockIdx.y)
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_prolong_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, const double* __restrict__ xc,
+                                                                double* __restrict__ x, const EsState* st) {
+    if (st->status != ES_RUN) return;
+    const int co[3] = {co0, co1, co2};
+    const int comp = blockIdx.y;
+    xc += (size_t)comp * Lc.nn;
+    x += (size_t)comp * Lf.nn;
+    ES_LOOP(id, Lf.nn) {
+        if (es_fixed(Lf, id, comp)) continue;
+        int I[3];
+        es_coords<N>(Lf, id, I);
+        int J0[3] = {0, 0, 0}, two[3] = {0, 0, 0};
+#pragma unroll
+        for (int d = 0; d < N; ++d) {
+            J0[d] = co[d] ? I[d] >> 1 : I[d];
+            two[d] = co[d] && (I[d] & 1) && J0[d] + 1 < Lc.n[d];
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int m = 0; m < (1 << N); ++m) {
+            double w = 1.0;
+            bool use = true;
+            int J[3] = {0, 0, 0};
+#pragma unroll
+            for (int d = 0; d < N; ++d) {
+                const int b = (m >> d) & 1;
+                if (b && !two[d]) use = false;
+                if (two[d]) w = w * 0.5;
+                J[d] = J0[d] + b;
+            }
+            if (use) acc += w * xc[J[0] + Lc.n[0] * (J[1] + (N > 2 ? Lc.n[1] * J[2] : 0))];
+        }
+        x[id] = x[id] + acc;
+    }
+}
+// the coarsest level (≤ 128 nodes, ≤ 384 unknowns): ES_NCOARSE sweeps from zero in one workgroup, x in LDS, double-buffered
+template <int N, int DOT>
+__global__ void __launch_bounds__(128) es_coarsest_kernel(EsLevel L, const double* __restrict__ r, double* __restrict__ x, EsState* st) {
+    __shared__ double xs[2][N * 128];
+    __shared__ double red[2];
+    if (st->status != ES_RUN) return;
+    const int id = threadIdx.x, nn = L.nn;
+    const bool node = id < nn;
+    int I[3] = {0, 0, 0};
+    if (node) es_coords<N>(L, id, I);
+    bool on[N];
+    double ri[N], Di[N], v[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        on[i] = node && !es_fixed(L, id, i);
+        ri[i] = on[i] ? r[i * nn + id] : 0.0;
+        Di[i] = on[i] ? L.D[i * nn + id] : 1.0;
+        v[i] = on[i] ? (L.omega * ri[i]) / Di[i] : 0.0;
+    }
+    int cur = 0;
+    for (int s = 1; s < ES_NCOARSE; ++s) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) xs[cur][i * 128 + id] = v[i];
+        __syncthreads();
+        if (node) {
+            const double* xb = xs[cur];
+            double out[N];
+            es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return xb[j * 128 + q]; }, out);     // fixed components hold zero
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+                if (on[i]) v[i] = v[i] + (L.omega * (ri[i] - out[i])) / Di[i];
+        }
+        cur ^= 1;
+    }
+    if (node) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i * nn + id] = v[i];
+    }
+    if (DOT) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) t += ri[i] * v[i];
+        const double s = wave_sum(t);
+        if ((id & 63) == 0) red[id >> 6] = s;
+        __syncthreads();
+        if (id == 0) es_rho_update(*st, red[0] + red[1]);
+    }
+}
+
+// ---- x → u on the free components (rounded to the storage type); the fixed components and the ghosts are left as they are
+template <int N>
+__global__ void __launch_bounds__(ES_THREADS) es_store_kernel(EsLevel L, EsField F, const double* __restrict__ x, EsU U) {
+    ES_LOOP(id, L.nn) {
+        int I[3];
+        es_coords<N>(L, id, I);
+        const long long at = es_padded(F, I);
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (!es_fixed(L, id, i)) st_val(U.p[i], at, F.f32, x[i * L.nn + id]);
+    }
+}
+
+// ---- host side
+struct ElasticObject {
+    int N = 0, precond = 0, last_iters = 0;
+    int co[32][3];                       // co[l]: the axes that coarsen from level l to l+1
+    std::vector<EsLevel> lev;
+    std::vector<std::vector<double>> k0; // the levels' K0 as computed (what the device holds)
+    std::vector<double*> rhs, xa, xb;    // per level ≥ 1: right-hand side and the two smoother buffers; level 0: xa, xb only
+    EsVec V;
+    EsField F;
+    long long nfree = 0, nfixed = 0;
+    DevBuf<double> buf, partial;
+    DevBuf<unsigned char> fx;
+    DevBuf<EsState> st;
+    DevBuf<unsigned long long> cnt;
+    PinnedBuf<EsState> h_st;
+};
+
+// the unit element matrix of a box cell with sides h, scaled by 1/∏h (include/lsm.h states the formula): a product over the axes
+// of the 1-D factors mass h/3 | h/6, stiffness ±1/h, mixed ±½ (the sign of the differentiated corner)
+static void es_k0(int N, const double h[3], double lam, double mu, std::vector<double>& K) {
+    const int NC = 1 << N, R = NC * N;
+    std::vector<double> G((size_t)NC * NC * N * N);
+    auto g_at = [&](int a, int b, int i, int j) -> double& { return G[(((size_t)a * NC + b) * N + i) * N + j]; };
+    double vol = 1.0;
+    for (int d = 0; d < N; ++d) vol = vol * h[d];
+    for (int a = 0; a < NC; ++a)
+        for (int b = 0; b < NC; ++b)
+            for (int i = 0; i < N; ++i)
+                for (int j = 0; j < N; ++j) {
+                    double g = 1.0;
+                    for (int d = 0; d < N; ++d) {
+                        const int ad = (a >> d) & 1, bd = (b >> d) & 1;
+                        if (i == j && d == i) g = g * ((ad == bd ? 1.0 : -1.0) / h[d]);
+                        else if (i != j && d == i) g = g * (ad ? 0.5 : -0.5);
+                        else if (i != j && d == j) g = g * (bd ? 0.5 : -0.5);
+                        else g = g * (ad == bd ? h[d] / 3.0 : h[d] / 6.0);
+                    }
+                    g_at(a, b, i, j) = g;
+                }
+    K.assign((size_t)R * R, 0.0);
+    for (int a = 0; a < NC; ++a)
+        for (int b = 0; b < NC; ++b) {
+            double tr = 0.0;
+            for (int k = 0; k < N; ++k) tr = tr + g_at(a, b, k, k);
+            for (int i = 0; i < N; ++i)
+                for (int j = 0; j < N; ++j) {
+                    double v = lam * g_at(a, b, i, j) + mu * g_at(a, b, j, i);
+                    if (i == j) v = v + mu * tr;
+                    K[(size_t)(a * N + i) * R + b * N + j] = v / vol;
+                }
+        }
+}
+
+// λmax(D⁻¹A) of the level's operator on a uniform infinite grid, from K0 alone: the largest eigenvalue over the 2^N corner
+// frequencies θ ∈ {0, π}^N of the N×N symbol D^−½·Â(θ)·D^−½, Â_ij(θ) = Σ_a Σ_b ±K0[(a,i),(b,j)] (minus where a and b differ on an odd
+// number of the axes with θ_d = π), D_i = Σ_a K0[(a,i),(a,i)].  Stretched cells — an axis that stopped coarsening while the others go
+// on — push it past 2/ES_OMEGA, where damped Jacobi amplifies and the V-cycle is no longer positive definite.
+static double es_symbol_lambda(int N, const std::vector<double>& K) {
+    const int NC = 1 << N, R = NC * N;
+    double D[3] = {0, 0, 0}, best = 0.0;
+    for (int i = 0; i < N; ++i)
+        for (int a = 0; a < NC; ++a) D[i] += K[(size_t)(a * N + i) * R + a * N + i];
+    for (int th = 0; th < NC; ++th) {
+        double A[3][3] = {{0}};
+        for (int a = 0; a < NC; ++a)
+            for (int b = 0; b < NC; ++b) {
+                const double sg = (__builtin_popcount((a ^ b) & th) & 1) ? -1.0 : 1.0;
+                for (int i = 0; i < N; ++i)
+                    for (int j = 0; j < N; ++j) A[i][j] += sg * K[(size_t)(a * N + i) * R + b * N + j] / std::sqrt(D[i] * D[j]);
+            }
+        double x[3] = {1.0, 0.9, 0.8}, lam = 0.0;     // power iteration: the symbol is symmetric and not negative
+        for (int it = 0; it < 500; ++it) {
+            double y[3] = {0, 0, 0}, nrm = 0.0;
+            for (int i = 0; i < N; ++i) {
+                for (int j = 0; j < N; ++j) y[i] += A[i][j] * x[j];
+                nrm += y[i] * y[i];
+            }
+            nrm = std::sqrt(nrm);
+            if (!(nrm > 0.0)) break;
+            lam = nrm;
+            for (int i = 0; i < N; ++i) x[i] = y[i] / nrm;
+        }
+        best = std::max(best, lam);
+    }
+    return best;
+}
+
+static unsigned es_blocks(long long n) { return (unsigned)std::min<long long>((n + ES_THREADS - 1) / ES_THREADS, ES_MAXB); }
+
+#define ES_LAUNCH(N, kernel, grid, block, stream, ...)                                              \
+    do {                                                                                            \
+        if ((N) == 2) hipLaunchKernelGGL(kernel<2>, grid, dim3(block), 0, stream, __VA_ARGS__);     \
+        else hipLaunchKernelGGL(kernel<3>, grid, dim3(block), 0, stream, __VA_ARGS__);              \
+    } while (0)
+#define ES_LAUNCH2(N, kernel, flag, grid, block, stream, ...)                                               \
+    do {                                                                                                    \
+        if ((N) == 2) hipLaunchKernelGGL((kernel<2, flag>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel<3, flag>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__);        \
+    } while (0)
+
+// z = M r for M = one V-cycle; the last kernel leaves ρ and β
+static void es_vcycle(ElasticObject& o, hipStream_t s) {
+    const int N = o.N, nl = (int)o.lev.size();
+    EsState* st = o.st;
+    for (int l = 0; l + 1 < nl; ++l) {
+        const EsLevel& L = o.lev[l];
+        const double* r = l == 0 ? o.V.r : o.rhs[l];
+        const unsigned nb = es_blocks(L.nn);
+        ES_LAUNCH(N, es_smooth0_kernel, dim3(nb), ES_THREADS, s, L, r, o.xa[l], (const EsState*)st);
+        ES_LAUNCH2(N, es_smooth_kernel, 0, nb, ES_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
+        ES_LAUNCH(N, es_resid_kernel, dim3(nb), ES_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], (const EsState*)st);      // xa is free until the post-smoothing
+        ES_LAUNCH(N, es_gather_kernel, dim3(es_blocks(o.lev[l + 1].nn), N), ES_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2],
+                  (const double*)o.xa[l], o.rhs[l + 1], (const EsState*)st);
+    }
+    {
+        const int l = nl - 1;
+        const double* r = l == 0 ? o.V.r : o.rhs[l];
+        if (l == 0) ES_LAUNCH2(N, es_coarsest_kernel, 1, 1, 128, s, o.lev[l], r, o.xb[l], st);
+        else ES_LAUNCH2(N, es_coarsest_kernel, 0, 1, 128, s, o.lev[l], r, o.xb[l], st);
+    }
+    for (int l = nl - 2; l >= 0; --l) {
+        const EsLevel& L = o.lev[l];
+        const double* r = l == 0 ? o.V.r : o.rhs[l];
+        const unsigned nb = es_blocks(L.nn);
+        ES_LAUNCH(N, es_prolong_kernel, dim3(nb, N), ES_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2], (const double*)o.xb[l + 1], o.xb[l],
+                  (const EsState*)st);
+        ES_LAUNCH2(N, es_smooth_kernel, 0, nb, ES_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], o.partial.p, st);
+        if (l == 0) ES_LAUNCH2(N, es_smooth_kernel, 1, nb, ES_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
+        else ES_LAUNCH2(N, es_smooth_kernel, 0, nb, ES_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
+    }
+}
+
+}  // namespace lsm
+
+using namespace lsm;
+
+struct LsmElastic { LsmHandle* h; ElasticObject* o; };
+
+#define ES_HIP(h, call)                                                                                       \
+    do {                                                                                                      \
+        hipError_t e_ = (call);                                                                               \
+        if (e_ != hipSuccess) return lsm_fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double level, double e_in, double e_out, const double* e_cells, double lam, double mu,
+                     const unsigned char* fixed, int64_t stats[4]) {
+    const int N = h->grid.ndim;
+    o.N = N;
+    o.F = EsField{h->lay.stride[1], N > 2 ? h->lay.stride[2] : 0, h->lay.origin, h->dtype == LSM_DTYPE_F32 ? 1 : 0};
+    // the hierarchy's shapes: axis d coarsens while n_d > 5, to (n_d+1)/2 nodes; it ends when no axis coarsens
+    std::vector<EsLevel> lev;
+    EsLevel L;
+    memset(&L, 0, sizeof(L));
+    long long nn = 1;
+    double hmin = INFINITY;
+    for (int d = 0; d < 3; ++d) {
+        L.n[d] = d < N ? h->nloc[d] : 1;
+        L.h[d] = d < N ? h->h[d] : 1.0;
+        nn *= L.n[d];
+        if (d < N) hmin = std::min(hmin, L.h[d]);
+    }
+    if (nn >= (1LL << 28)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the grid is too large (2^28 nodes at most)");
+    L.nn = (int)nn;
+    lev.push_back(L);
+    for (;;) {
+        const EsLevel& f = lev.back();
+        EsLevel c = f;
+        bool any = false;
+        const int l = (int)lev.size() - 1;
+        c.nn = 1;
+        for (int d = 0; d < 3; ++d) {
+            o.co[l][d] = d < N && f.n[d] > 5;
+            if (o.co[l][d]) {
+                any = true;
+                c.n[d] = (f.n[d] + 1) / 2;
+                c.h[d] = f.h[d] * 2.0;
+            }
+            c.nn *= c.n[d];
+        }
+        if (!any || lev.size() >= 31) break;
+        lev.push_back(c);
+    }
+    const int nl = (int)lev.size();
+    if (lev[nl - 1].nn > 128) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the coarsest level has more than 128 nodes");
+    const size_t RR = (size_t)((1 << N) * N) * (size_t)((1 << N) * N);
+    // one allocation of doubles: per level K0, cells, D, xa, xb, [rhs]; level 0: x r q p as well
+    auto ncell = [&](const EsLevel& q) { long long m = 1; for (int d = 0; d < N; ++d) m *= q.n[d] - 1; return m; };
+    size_t nd = 0, nb = 0;
+    for (int l = 0; l < nl; ++l) {
+        nd += RR + (size_t)ncell(lev[l]) + (size_t)N * (size_t)lev[l].nn * (size_t)(3 + (l ? 1 : 4));
+        nb += (size_t)lev[l].nn;
+    }
+    ES_HIP(h, o.buf.alloc(nd * sizeof(double)));
+    ES_HIP(h, o.fx.alloc(nb));
+    ES_HIP(h, o.partial.alloc(4 * ES_MAXB * sizeof(double)));
+    ES_HIP(h, o.st.alloc(sizeof(EsState)));
+    ES_HIP(h, o.cnt.alloc(ES_NSTAT * sizeof(unsigned long long)));
+    ES_HIP(h, o.h_st.alloc(sizeof(EsState)));
+    hipStream_t s = h->stream;
+    ES_HIP(h, hipMemsetAsync(o.cnt.p, 0, ES_NSTAT * sizeof(unsigned long long), s));
+    ES_HIP(h, hipMemsetAsync(o.st.p, 0, sizeof(EsState), s));
+    double* b = o.buf;
+    unsigned char* fb = o.fx;
+    std::vector<double*> ecell(nl), dg(nl), kd(nl);
+    std::vector<unsigned char*> fxl(nl, nullptr);
+    o.rhs.assign(nl, nullptr); o.xa.assign(nl, nullptr); o.xb.assign(nl, nullptr);
+    o.k0.resize(nl);
+    for (int l = 0; l < nl; ++l) {
+        const size_t m = (size_t)N * (size_t)lev[l].nn;
+        kd[l] = b; b += RR;
+        ecell[l] = b; b += ncell(lev[l]);
+        dg[l] = b; b += m;
+        o.xa[l] = b; b += m;
+        o.xb[l] = b; b += m;
+        if (l) { o.rhs[l] = b; b += m; }
+        else {
+            o.V.x = b; b += m; o.V.r = b; b += m; o.V.q = b; b += m; o.V.p = b; b += m;
+        }
+        fxl[l] = fb; fb += lev[l].nn;
+        lev[l].E = ecell[l]; lev[l].D = dg[l]; lev[l].K = kd[l]; lev[l].fixed = fxl[l];
+        es_k0(N, lev[l].h, lam, mu, o.k0[l]);       // o.k0 outlives the copy: it belongs to the object
+        lev[l].omega = std::min(ES_OMEGA, ES_SAFE / es_symbol_lambda(N, o.k0[l]));
+        ES_HIP(h, hipMemcpyAsync(kd[l], o.k0[l].data(), RR * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    o.V.partial = o.partial;
+    o.V.st = o.st;
+    if (fixed) ES_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
+    else ES_HIP(h, hipMemsetAsync(fxl[0], 0, (size_t)nn, s));
+    ES_LAUNCH(N, es_setup_kernel, dim3(es_blocks(nn)), ES_THREADS, s, lev[0], o.F, e_cells ? (const void*)nullptr : phi, level, e_in, e_out, hmin, e_cells,
+              ecell[0], o.cnt.p);
+    ES_HIP(h, hipGetLastError());
+    unsigned long long c[ES_NSTAT] = {};
+    ES_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
+    ES_HIP(h, hipStreamSynchronize(s));
+    o.nfixed = 0;
+    int unfixed = -1;
+    for (int i = N - 1; i >= 0; --i) {
+        o.nfixed += (long long)c[ES_NFIX + i];
+        if (!c[ES_NFIX + i]) unfixed = i;
+    }
+    o.nfree = (long long)N * nn - o.nfixed;
+    // what the data is refused for: stats = {-(reason), offending entries (reason 4: the component), 0, 0}
+    const int reason = c[ES_BAD_PHI] ? 1 : c[ES_BAD_E] ? 2 : unfixed >= 0 ? 4 : o.nfree == 0 ? 5 : 0;
+    if (reason) {
+        static const char* why[5] = {"lsm_elastic_create: phi must be finite", "lsm_elastic_create: the cell moduli must be finite and positive", "",
+                                     "lsm_elastic_create: a displacement component has no fixed bit anywhere (its translation is in the null space)",
+                                     "lsm_elastic_create: every component of every node is fixed"};
+        if (stats) { stats[0] = -reason; stats[1] = (int64_t)(reason == 1 ? c[ES_BAD_PHI] : reason == 2 ? c[ES_BAD_E] : reason == 4 ? unfixed : 0); stats[2] = stats[3] = 0; }
+        return lsm_fail(h, LSM_ERR_INVALID, why[reason - 1]);
+    }
+    for (int l = 1; l < nl; ++l)
+        ES_LAUNCH(N, es_coarsen_kernel, dim3(es_blocks(lev[l].nn)), ES_THREADS, s, lev[l - 1], lev[l], o.co[l - 1][0], o.co[l - 1][1], o.co[l - 1][2], ecell[l],
+                  fxl[l]);
+    for (int l = 0; l < nl; ++l) ES_LAUNCH(N, es_diag_kernel, dim3(es_blocks(lev[l].nn)), ES_THREADS, s, lev[l], dg[l]);
+    ES_HIP(h, hipGetLastError());
+    ES_HIP(h, hipStreamSynchronize(s));
+    o.lev = lev;
+    o.V.z = o.precond == LSM_PRECOND_JACOBI ? o.xa[0] : o.xb[0];
+    if (stats) { stats[0] = nl; stats[1] = o.nfree; stats[2] = o.nfixed; stats[3] = 0; }
+    return LSM_OK;
+}
+
+int lsm_elastic_create(LsmHandle* h, const void* phi, double level, double e_in, double e_out, const double* e_cells, double nu, int plane, const void* fixed,
+                       int precond, LsmElastic** out, int64_t stats[4]) {
+    if (!h || !out) return h ? lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: null argument") : LSM_ERR_INVALID;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    if (!phi && !e_cells) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: give phi or the cell moduli");
+    const int N = h->grid.ndim;
+    if (N == 1) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: a 1-dimensional grid is not supported (2-D and 3-D only)");
+    if (h->comm) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the handle has a communicator attached (single device only)");
+    if (h->bc[N - 1][0].kind == LSM_BC_NONE || h->bc[N - 1][1].kind == LSM_BC_NONE)
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the handle is a slab of a multi-GPU grid (whole grids only)");
+    for (int d = 0; d < N; ++d) {
+        if (h->bc[d][0].kind == LSM_BC_PERIODIC || h->bc[d][1].kind == LSM_BC_PERIODIC)
+            return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: a periodic dimension is not supported (the faces are traction-free)");
+        if (h->nloc[d] < 3) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: at least 3 nodes per dimension");
+    }
+    if (!e_cells && (!(e_in > 0) || !std::isfinite(e_in) || !(e_out > 0) || !std::isfinite(e_out)))
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: e_in and e_out must be finite and positive");
+    if (!e_cells && !std::isfinite(level)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: level must be finite");
+    if (!std::isfinite(nu) || !(nu > -1.0) || !(nu < 0.5)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: nu must be finite with -1 < nu < 0.5");
+    if (plane != LSM_PLANE_STRESS && plane != LSM_PLANE_STRAIN) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: unknown plane (LSM_PLANE_STRESS or LSM_PLANE_STRAIN)");
+    if (precond != LSM_PRECOND_MG && precond != LSM_PRECOND_JACOBI) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: unknown preconditioner");
+    const double mu = 1.0 / (2.0 * (1.0 + nu));
+    const double lam = (N == 2 && plane == LSM_PLANE_STRESS) ? nu / (1.0 - nu * nu) : nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
+    (void)hipSetDevice(h->device);
+    ElasticObject* o = new ElasticObject();
+    o->precond = precond;
+    const int r = es_create(h, *o, phi, level, e_in, e_out, e_cells, lam, mu, (const unsigned char*)fixed, stats);
+    if (r != LSM_OK) { delete o; return r; }
+    *out = new LsmElastic{h, o};
+    return LSM_OK;
+}
+
+int lsm_elastic_stiffness(LsmElastic* s, int level, double* k0_host) {
+    if (!s) return LSM_ERR_INVALID;
+    if (!k0_host || level < 0 || level >= (int)s->o->k0.size()) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stiffness: no such level, or a null array");
+    memcpy(k0_host, s->o->k0[level].data(), s->o->k0[level].size() * sizeof(double));
+    return LSM_OK;
+}
+
+int lsm_elastic_apply(LsmElastic* s, const double* x, double* y) {
+    if (!s) return LSM_ERR_INVALID;
+    if (!x || !y || x == y) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_apply: x and y must be two arrays");
+    const EsLevel& L = s->o->lev[0];
+    ES_LAUNCH(s->o->N, es_apply_kernel, dim3(es_blocks(L.nn)), ES_THREADS, s->h->stream, L, x, y);
+    ES_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_cells(LsmElastic* s, double* e_out_cells) {
+    if (!s) return LSM_ERR_INVALID;
+    if (!e_out_cells) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_cells: null argument");
+    const EsLevel& L = s->o->lev[0];
+    size_t m = 1;
+    for (int d = 0; d < s->o->N; ++d) m *= (size_t)(L.n[d] - 1);
+    ES_HIP(s->h, hipMemcpyAsync(e_out_cells, L.E, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
+    return LSM_OK;
+}
+
+// the N fields of u: all given, no two the same
+static bool es_fields(int N, const void* u0, const void* u1, const void* u2, EsU& U) {
+    U.p[0] = (void*)u0; U.p[1] = (void*)u1; U.p[2] = N > 2 ? (void*)u2 : nullptr;
+    if (!u0 || !u1 || u0 == u1) return false;
+    if (N > 2 && (!u2 || u2 == u0 || u2 == u1)) return false;
+    return true;
+}
+
+int lsm_elastic_energy(LsmElastic* s, const void* u0, const void* u1, const void* u2, void* e_out) {
+    if (!s) return LSM_ERR_INVALID;
+    EsU U;
+    if (!es_fields(s->o->N, u0, u1, u2, U) || !e_out || e_out == u0 || e_out == u1 || e_out == u2)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_energy: the components of u and e_out must be distinct fields");
+    const EsLevel& L = s->o->lev[0];
+    ES_LAUNCH(s->o->N, es_energy_kernel, dim3(es_blocks(L.nn)), ES_THREADS, s->h->stream, L, s->o->F, U, e_out);
+    ES_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const void* u1, const void* u2, double* out) {
+    if (!s) return LSM_ERR_INVALID;
+    EsU U;
+    if (!f || !out || !es_fields(s->o->N, u0, u1, u2, U)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_compliance: null argument");
+    ElasticObject& o = *s->o;
+    const EsLevel& L = o.lev[0];
+    hipStream_t st = s->h->stream;
+    ES_LAUNCH(o.N, es_compliance_kernel, dim3(es_blocks(L.nn)), ES_THREADS, st, L, o.F, f, U, o.partial.p, o.st.p);
+    ES_HIP(s->h, hipGetLastError());
+    ES_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(EsState), hipMemcpyDeviceToHost, st));
+    ES_HIP(s->h, hipStreamSynchronize(st));
+    double vol = 1.0;
+    for (int d = 0; d < o.N; ++d) vol *= L.h[d];
+    *out = vol * o.h_st.p->out;
+    return LSM_OK;
+}
+
+int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* u2, double rtol, int max_iters, int* iters_out, double* relres_out, void* stream) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (!f || !es_fields(o.N, u0, u1, u2, U)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_solve: f and the N distinct fields of u must be given");
+    if (!(rtol > 0) || !std::isfinite(rtol) || max_iters < 1) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_solve: rtol must be positive and max_iters at least 1");
+    const int N = o.N;
+    const EsLevel& L = o.lev[0];
+    const int jac = o.precond == LSM_PRECOND_JACOBI;
+    (void)hipSetDevice(h->device);
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    EsState s0;
+    memset(&s0, 0, sizeof(s0));
+    s0.rtol2 = rtol * rtol;
+    s0.max_iters = max_iters;
+    ES_HIP(h, hipMemcpyAsync(o.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+    const unsigned nb = es_blocks(L.nn), nbt = es_blocks((long long)N * L.nn);
+    const int nt = N * L.nn;
+    ES_LAUNCH(N, es_load_kernel, dim3(nb), ES_THREADS, st, L, o.F, o.V, U);
+    ES_LAUNCH(N, es_init_kernel, dim3(nb), ES_THREADS, st, L, o.V, (const double*)o.V.x, f, o.V.r, o.V.z, jac);
+    ES_HIP(h, hipGetLastError());
+    // iterations in chunks: the first as long as the last solve took, then doubling
+    int enq = 0;
+    int chunk = std::max(4, o.last_iters + 1);
+    for (;;) {
+        const int k = std::min(chunk, max_iters - enq);
+        for (int it = 0; it < k; ++it, ++enq) {
+            if (!jac) es_vcycle(o, st);
+            hipLaunchKernelGGL(es_dir_kernel, dim3(nbt), dim3(ES_THREADS), 0, st, nt, o.V);
+            ES_LAUNCH(N, es_k1_kernel, dim3(nb), ES_THREADS, st, L, (const double*)o.V.p, o.V.q, o.partial.p, o.st.p);
+            if (jac) hipLaunchKernelGGL(es_k2_kernel<1>, dim3(nbt), dim3(ES_THREADS), 0, st, L.D, nt, o.V);
+            else hipLaunchKernelGGL(es_k2_kernel<0>, dim3(nbt), dim3(ES_THREADS), 0, st, L.D, nt, o.V);
+        }
+        ES_HIP(h, hipGetLastError());
+        ES_HIP(h, hipMemcpyAsync(o.h_st, o.st, sizeof(EsState), hipMemcpyDeviceToHost, st));
+        ES_HIP(h, hipStreamSynchronize(st));
+        if (o.h_st.p->status != ES_RUN || enq >= max_iters) break;
+        chunk = std::min(2 * chunk, 64);
+    }
+    const EsState S = *o.h_st;
+    const double rel = S.bb > 0 ? std::sqrt(S.rr / S.bb) : (S.rr == 0 ? 0.0 : std::sqrt(S.rr));
+    if (iters_out) *iters_out = S.iters;
+    if (relres_out) *relres_out = rel;
+    if (S.status == ES_BREAK_INPUT) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "lsm_elastic_solve: f and u must be finite (%llu entries are not); u is unchanged", S.nonfinite);
+        return lsm_fail(h, LSM_ERR_INVALID, msg);
+    }
+    if (S.status != ES_CONVERGED) {
+        char msg[320];
+        const char* why = S.status == ES_MAXITER || S.status == ES_RUN ? "no convergence within max_iters"
+                          : S.status == ES_BREAK_SIGMA ? "PCG breakdown (p·Ap not positive)"
+                                                       : "PCG breakdown (r·Mr not positive, or a non-finite residual)";
+        snprintf(msg, sizeof(msg), "lsm_elastic_solve: %s: %d iterations, relative residual %.3e (rtol %.3e); u is unchanged", why, S.iters, rel, rtol);
+        return lsm_fail(h, LSM_ERR_NOT_CONVERGED, msg);
+    }
+    o.last_iters = S.iters;
+    ES_LAUNCH(N, es_store_kernel, dim3(nb), ES_THREADS, st, L, o.F, (const double*)o.V.x, U);
+    ES_HIP(h, hipGetLastError());
+    ES_HIP(h, hipStreamSynchronize(st));
+    return LSM_OK;
+}
+
+void lsm_elastic_destroy(LsmElastic* s) {
+    if (!s) return;
+    delete s->o;
+    delete s;
+}

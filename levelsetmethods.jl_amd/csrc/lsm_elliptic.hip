@@ -30,6 +30,7 @@
 #include <cstring>
 #include <vector>
 
+#include "el_cell.h"
 #include "lsm_handle.h"
 #include "wave.h"
 
@@ -162,17 +163,7 @@ __global__ void __launch_bounds__(EL_THREADS) el_setup_kernel(ElLevel L, ElField
             av = a_given[ci];
             if (!(av > 0.0) || !el_finite(av)) ++cnt[EL_BAD_A];
         } else {
-            const long long at = el_padded(F, I);
-            double s = 0.0;
-#pragma unroll
-            for (int m = 0; m < (1 << N); ++m) {    // the corners in ascending linear index
-                const long long o = (m & 1) + ((m >> 1) & 1) * F.s1 + (N > 2 ? ((m >> 2) & 1) * F.s2 : 0);
-                const double p = ld_val(phi, at + o, F.f32);
-                s = m == 0 ? p : s + p;
-            }
-            const double mean = s * (N == 2 ? 0.25 : 0.125);
-            const double theta = fmin(fmax(0.5 - (mean - level) / hmin, 0.0), 1.0);
-            av = a_out + (a_in - a_out) * theta;
+            av = el_cell_from_phi<N>(phi, el_padded(F, I), F.s1, F.s2, F.f32, level, a_in, a_out, hmin);
         }
         a[ci] = av;
     }
