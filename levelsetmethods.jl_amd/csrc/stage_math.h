@@ -7,11 +7,13 @@
 //          src/levelsetterms.jl:73-265, src/levelsetops.jl:197-244): true IEEE divisions, no
 //          contraction.  Used to prove indexing / ghost / stage logic bit for bit against the oracle.
 //  FAST    same mathematics reorganised for the fp64 vector pipe, which — not HBM — bounds this
-//          kernel (≈230 vector instructions per node-stage of WENO5 advection + Eikonal against 24 bytes):
+//          kernel (≈220 vector instructions per node-stage of WENO5 advection + Eikonal against 24 bytes):
 //            * differences stay undivided (Δ, not Δ/h); WENO5 is homogeneous of degree one, so the
 //              1/h is applied once per dimension and the ε floor becomes 1e-99·h² (raised to 1e-75, see below);
+//            * the smoothness indicators as ¾(S_k+ε), quadratic forms in the second differences and their
+//              differences that need no B_k = first-derivative stencil (10 operations for the three instead of 12);
 //            * the three WENO weights use ONE reciprocal: Σ_k c_k Π_{j≠k}(S_j+ε)² d_k / Σ_k c_k Π_{j≠k}(S_j+ε)²
-//              instead of 6 divisions (src/derivatives.jl:73-78);
+//              instead of 6 divisions (src/derivatives.jl:73-78), with (S₂+ε)² factored out of both sums;
 //            * divisions/sqrt are v_rcp_f64 / v_rsq_f64 seeds + Newton/Goldschmidt FMA steps (≤2 ulp);
 //            * the two minmods of an ENO pair as clamps sharing max(w₃,0), min(w₃,0); Godunov sums without selects;
 //              the ENO pair of a WENO5 line from that line's own differences.
@@ -142,27 +144,28 @@ LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, do
         Q = __builtin_fma(-0.5, __builtin_fmax(__builtin_fmin(w4, hi), lo), e4);
     }
     const double A1 = w2 - w1, A2 = w3 - w2, A3 = w4 - w3;
-    const double B1 = __builtin_fma(2.0, w2, A1);      // e1 - 4e2 + 3e3
-    const double B2 = w2 + w3;                         // -(e2 - e4)
-    const double B3 = __builtin_fma(-2.0, w3, A3);     // 3e3 - 4e4 + e5
     const double m = __builtin_fmax(__builtin_fmax(__builtin_fmax(__builtin_fabs(e1), __builtin_fabs(e2)),
                                                    __builtin_fmax(__builtin_fabs(e3), __builtin_fabs(e4))),
                                     __builtin_fabs(e5));
-    // S_k + ε scaled by 12/13 (the weights only see ratios): A² + (3/13)·B² + (12/13)·ε — one multiply less per k
-    const double eps = __builtin_fma((12.0 / 13) * 1.0e-6 * m, m, __builtin_fmax(eps_floor, 1.0e-75));   // the max is loop-invariant
-    const double r1 = __builtin_fma(A1, A1, __builtin_fma((3.0 / 13) * B1, B1, eps));
-    const double r2 = __builtin_fma(A2, A2, __builtin_fma((3.0 / 13) * B2, B2, eps));
-    const double r3 = __builtin_fma(A3, A3, __builtin_fma((3.0 / 13) * B3, B3, eps));
+    // S_k + ε scaled by 3/4 (the weights only see ratios).  (12/13)(S_k + ε) = A_k² + (3/13)·B_k² + (12/13)·ε with
+    // B₁ = A₁ + 2w₂, B₂ = w₂ + w₃, B₃ = A₃ - 2w₃; B₂² = A₂² + 4w₂w₃ and (4·3/13)/(1 + 3/13) = 3/4 exactly, so dividing by
+    // 16/13 leaves  r₁ = A₁² + ¾w₂(A₁ + w₂),  r₂ = A₂² + ¾w₂w₃,  r₃ = A₃² + ¾w₃(w₃ - A₃)  (+ ¾ε): no B, 10 operations
+    // instead of 12.  The three quadratic forms are positive definite (r₂ >= ⅜(w₂² + w₃²)): no cancellation.
+    const double eps = __builtin_fma(0.75e-6 * m, m, (13.0 / 16) * __builtin_fmax(eps_floor, 1.0e-75));   // the floor is loop-invariant
+    const double t2 = 0.75 * w2, t3 = 0.75 * w3;
+    const double r1 = __builtin_fma(A1, A1, __builtin_fma(t2, A1 + w2, eps));
+    const double r2 = __builtin_fma(A2, A2, __builtin_fma(t2, w3, eps));
+    const double r3 = __builtin_fma(A3, A3, __builtin_fma(t3, w3 - A3, eps));
     const double s1 = r1 * r1, s2 = r2 * r2, s3 = r3 * r3;
-    const double W1 = s2 * s3, W2 = s1 * s3, W3 = s1 * s2;   // ∝ α_k / c_k
-    const double c1W1 = (0.1 / 3) * W1, c3W3 = (0.3 / 6) * W3;
-    // 0.1 W1 + 0.6 W2 + 0.3 W3 > 0: eps_floor >= 1e-75 keeps every r_k >= 1e-75 and the products >= 1e-302
-    // (exactly flat data gives 0·(1/den) = 0, as the reference)
-    const double den = __builtin_fma(3.0, c1W1, __builtin_fma(6.0, c3W3, 0.6 * W2));
-    const double rc = fast_rcp(den);
     const double dphi2 = __builtin_fma(1.0 / 3, w3, __builtin_fma(1.0 / 6, w2, e3));   // (-e2 + 5 e3 + 2 e4)/6 = e3 + w3/3 + w2/6
-    const double X = __builtin_fma(c1W1, A1 - A2, c3W3 * (A2 - A3));
-    return __builtin_fma(rc, X, dphi2);
+    // α_k ∝ c_k/s_k with c = (0.1, 0.6, 0.3); numerator and denominator multiplied by 10·s₁s₂s₃ and s₂ factored out:
+    //   (ω₁/3)(A₁-A₂) + (ω₃/6)(A₂-A₃) = s₂(s₃(A₁-A₂) + 1.5 s₁(A₂-A₃)) / (3(6 s₁s₃ + s₂(3 s₁ + s₃)))
+    // — 11 operations instead of 12, no pair product kept.
+    // Dn > 0: the floor keeps every r_k >= 0.8e-75, every s_k >= 6.6e-151 and Dn >= 10·4.3e-301 > 1e-302
+    // (exactly flat data gives 0·(1/Dn) = 0, as the reference)
+    const double N = s2 * __builtin_fma(1.5, s1 * (A2 - A3), s3 * (A1 - A2));
+    const double Dn = __builtin_fma(6.0, s1 * s3, s2 * __builtin_fma(3.0, s1, s3));
+    return __builtin_fma(fast_rcp(Dn) * (1.0 / 3), N, dphi2);
 }
 LSM_DEV double weno5_undivided(double e1, double e2, double e3, double e4, double e5, double eps_floor) {
     double P, Q;
