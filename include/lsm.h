@@ -622,6 +622,67 @@ int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const
 int lsm_elastic_cells(LsmElastic* s, double* e_out_cells);
 void lsm_elastic_destroy(LsmElastic* s);
 
+/* ---- elasticity_modes: the m smallest eigenpairs of A x = lambda·M x for the ersatz-material structure of an LsmElastic — its
+ *      vibration modes, lambda = omega² — by a locally optimal block preconditioned CG (LOBPCG) whose preconditioner T is the
+ *      object's V-cycle, or 1/D for LSM_PRECOND_JACOBI (csrc/lsm_elastic.hip; tests/_modes_ref.py restates it).
+ *      A is lsm_elastic_apply's operator, scaled by 1/prod h as it is, with the fixed components eliminated: they are zero in
+ *      every mode, whatever values a solve prescribes there.  The fixed set must hold every rigid-body motion.
+ *      Mass: lumped, the same for every component of a node.  Cell density rho_C = lsm_elliptic's cell formula with (rho_in,
+ *      rho_out) for (a_in, a_out) — the code and the fill fraction of the modulus — or rho_cells != NULL: the caller's cell array,
+ *      n−1 per axis, on the device (phi may be NULL then).  M_I = (sum of rho_C over the existing cells around I, ascending
+ *      m = 0 … 2^N−1, from +0)·2^−N: M is scaled by 1/prod h like A, so lambda needs no factor.  rho_out/rho_in must stay far below
+ *      e_out/e_in, or the lowest modes are spurious ones living in the ersatz material.
+ *      Vectors: a block has m columns of N·nn fp64, column-major, a column component-major as lsm_elastic_apply's x.  The object
+ *      holds X, W, P and A·X, A·W, A·P: 6·m·N·nn doubles, plus the node mass and the cell densities.
+ *      Start: x0 (device, m·N·nn doubles), or NULL: entry t = k·N·nn + i·nn + id takes z = t + 0x9E3779B97F4A7C15 (mod 2^64),
+ *      z = (z ^ z>>30)·0xBF58476D1CE4E5B9, z = (z ^ z>>27)·0x94D049BB133111EB, z = z ^ z>>31 (splitmix64), d = (z>>11)·2^−53, the
+ *      value 2d − 1.  Either way the fixed components are set to zero.  A·X = A X once; then one Rayleigh–Ritz step on span X.
+ *      Iteration, with lambda_k the Ritz values:
+ *        1. R_k = A·X_k − lambda_k·(M·X_k) for every k, and ‖R_k‖₂, ‖M·X_k‖₂.  Column k has converged when ‖R_k‖₂ <=
+ *           rtol·lambda_k·‖M·X_k‖₂; relres[k] = ‖R_k‖₂/(lambda_k·‖M·X_k‖₂).  All converged: done.  iters == max_iters: not converged.
+ *        2. W_j = T(R_k), A·W_j = A W_j for the na columns k that have not converged, ascending (soft locking: a converged column
+ *           stays in X and is rotated with it, but gives no W or P column).
+ *        3. Gram matrices G_A = S^T (A·S), G_M = S^T (M·S) over S = [X, W, P], q = m + na + np <= 24 columns (np = the previous
+ *           iteration's na; 0 at first).  Only entries i <= j are formed and mirrored.  Entry (i, j) is a sum over the N·nn rows of
+ *           S_i·(A·S)_j, or of S_i·(M·S_j), multiply then add: each thread over its rows ascending (row = thread + k·threads), then the
+ *           wave butterfly, the workgroup's waves as (0+1)+(2+3), and the workgroups in order; the launch is a function of the grid
+ *           alone, so two solves from the same start return the same bits.
+ *        4. Rayleigh–Ritz on the host, fp64, cyclic Jacobi: s_i = G_M[i,i]^−1/2; G'_M = s G_M s, G'_A = s G_A s; (mu, V) the
+ *           eigen-decomposition of G'_M; directions with mu <= 1e-12·max mu are dropped; B = V·mu^−1/2; (theta, Z) the
+ *           eigen-decomposition of B^T G'_A B, ascending; C = s·B·Z[:, 0…m−1], lambda = theta[0…m−1].
+ *        5. X <- S·C and A·X <- (A·S)·C; P <- [W, P]·C' and A·P <- [A·W, A·P]·C', C' = the W and P rows of C and the columns of the
+ *           na unconverged k.  Row by row, each sum from +0 over the columns of S ascending, multiply then add.  A·X and A·P are
+ *           never recomputed.  X leaves every iteration M-orthonormal.
+ *      lsm_elastic_modes_solve: lambda, relres (host, m doubles each), iters (block iterations) and stats (may be NULL) :=
+ *      {iterations, preconditioner applications, directions dropped, unconverged columns} are written in every return that ran.
+ *      LSM_ERR_INVALID without running anything: m outside 1 … 8, 3·m above the free components, rho_in / rho_out not finite and
+ *      positive, a non-finite level (create); rtol not positive and finite, max_iters < 1 (solve).  LSM_ERR_INVALID after a
+ *      kernel: a non-finite phi or a cell density not finite and positive (create), a non-finite x0 (solve).
+ *      LSM_ERR_NOT_CONVERGED: max_iters did not suffice, or a Gram matrix (or the preconditioner) is not positive; X is the last
+ *      iterate then, and vectors, store and sensitivity work on it.  The second happens where 3·m comes close to the number of free
+ *      components (5 modes of 16 unknowns, say): S then nearly spans the whole space, its Gram matrix loses rank as columns
+ *      converge, and the reduced problem is no longer positive to rounding.  Such problems are a dense solver's.
+ *      lsm_elastic_modes_mass copies the node mass (nn doubles), lsm_elastic_modes_vectors X (m·N·nn doubles) into device buffers.
+ *      lsm_elastic_modes_store: mode k into N distinct dense fields of the handle: X_k·(prod h)^−1/2 rounded once to the storage
+ *      type, so that prod h·sum M·|u|² = 1, the discrete ∫rho·|u|² = 1; exact zeros on the fixed components; ghosts untouched.  The
+ *      sign of a mode is not specified.
+ *      lsm_elastic_modes_sensitivity: g_I = e_I − (lambda_k·rhobar_I)·(sum_i u_{I,i}², from +0, i ascending) into a dense field,
+ *      rounded once: u the stored mode (rounded to the storage type), e_I lsm_elastic_energy's value of u in fp64 before its
+ *      rounding, rhobar_I = (sum of rho_C over the existing cells around I, ascending from +0)/(their number).  It is the integrand
+ *      of the shape derivative of lambda_k, a normal speed.
+ *      The modes object borrows the LsmElastic, which must outlive it, and uses its scratch vectors: a solve of either must not run
+ *      concurrently with the other, and lsm_elastic_solve's results are unaffected by a modes solve in between. */
+typedef struct LsmModes LsmModes;
+int lsm_elastic_modes_create(LsmElastic* s, const void* phi, double level, double rho_in, double rho_out, const double* rho_cells, int m,
+                             LsmModes** out);
+int lsm_elastic_modes_mass(LsmModes* md, double* node_mass);
+int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max_iters, double* lambda, double* relres, int* iters,
+                            int64_t stats[4]);
+int lsm_elastic_modes_vectors(LsmModes* md, double* x_out);
+int lsm_elastic_modes_store(LsmModes* md, int k, void* u0, void* u1, void* u2);
+int lsm_elastic_modes_sensitivity(LsmModes* md, int k, void* g_out);
+void lsm_elastic_modes_destroy(LsmModes* md);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

@@ -669,6 +669,39 @@ elasticity_cells!(a, K) = _check(K.h.ptr, ccall((:lsm_elastic_cells, libhiplsm),
 
 destroy_elasticity(K) = ccall((:lsm_elastic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), K.op)
 
+# elasticity_modes: the m ≤ 8 lowest vibration modes K u = λ M u of an elasticity_operator K (include/lsm.h, lsm_elastic_modes_*).  The
+# density of a cell is rho_out + (rho_in − rho_out)·θ(ϕ), or `rho` (a ROCArray{Float64} of size n .- 1, required when K was built from
+# `E`).  The object borrows K, which must outlive it; release it with destroy_modes.
+function elasticity_modes(K, ϕ::ROCMeshField, m; level = 0.0, rho_in = 1.0, rho_out = 1e-6, rho = nothing)
+    out = Ref{Ptr{Cvoid}}()
+    _check(K.h.ptr, ccall((:lsm_elastic_modes_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+        K.op, rho === nothing ? pointer(ϕ.buf) : C_NULL, level, rho_in, rho_out, rho === nothing ? C_NULL : pointer(rho), m, out), "lsm_elastic_modes_create")
+    return (; md = out[], h = K.h, m = m)
+end
+
+# modes_solve!: LOBPCG from x0 (a ROCArray{Float64} of m·N·nn values, or nothing: the fixed pseudo-random start) until every mode's
+# relative residual is below rtol.  Returns (eigenvalues, relres, iterations); LSM_ERR_NOT_CONVERGED throws, the last iterate stays.
+function modes_solve!(M; x0 = nothing, rtol = 1e-6, max_iters = 300)
+    lam, rel, iters, stats = zeros(Float64, M.m), zeros(Float64, M.m), Ref{Cint}(0), zeros(Int64, 4)
+    _check(M.h.ptr, ccall((:lsm_elastic_modes_solve, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64, Cint, Ptr{Float64}, Ptr{Float64}, Ref{Cint}, Ptr{Int64}),
+        M.md, x0 === nothing ? C_NULL : pointer(x0), rtol, max_iters, lam, rel, iters, stats), "lsm_elastic_modes_solve")
+    return (; eigenvalues = lam, relres = rel, iterations = iters[])
+end
+
+# the node mass into a ROCArray{Float64} of the grid's size; X into one of m·N·nn values (the next design's x0)
+modes_mass!(a, M) = _check(M.h.ptr, ccall((:lsm_elastic_modes_mass, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.md, pointer(a)), "lsm_elastic_modes_mass")
+modes_vectors!(x, M) = _check(M.h.ptr, ccall((:lsm_elastic_modes_vectors, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.md, pointer(x)), "lsm_elastic_modes_vectors")
+
+# mode k (0-based, as in C) into the N fields u, normalised to ∫ρ|u|² = 1; its shape-derivative integrand into the field g
+function modes_store!(u, M, k)
+    p = _u3(u)
+    _check(M.h.ptr, ccall((:lsm_elastic_modes_store, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), M.md, k, p[1], p[2], p[3]), "lsm_elastic_modes_store")
+end
+modes_sensitivity!(g::ROCMeshField, M, k) =
+    _check(M.h.ptr, ccall((:lsm_elastic_modes_sensitivity, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), M.md, k, pointer(g.buf)), "lsm_elastic_modes_sensitivity")
+
+destroy_modes(M) = ccall((:lsm_elastic_modes_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), M.md)
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

@@ -170,6 +170,14 @@ _SIGS = [
     ("lsm_elastic_compliance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("lsm_elastic_cells", C.c_int, [C.c_void_p, C.c_void_p]),
     ("lsm_elastic_destroy", None, [C.c_void_p]),
+    ("lsm_elastic_modes_create", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("lsm_elastic_modes_mass", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_modes_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int64)]),
+    ("lsm_elastic_modes_vectors", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_modes_store", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_modes_sensitivity", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_elastic_modes_destroy", None, [C.c_void_p]),
     ("lsm_extend_along_normals", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_double, C.c_double, C.c_double]),
     ("lsm_band_tile_count", C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),

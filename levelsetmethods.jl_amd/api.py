@@ -2790,7 +2790,8 @@ class ElasticityOperator:
     """The discrete Q1 elasticity operator of ϕ's grid and its multigrid hierarchy, kept on the device for repeated solves with
     new loads and guesses: solve(f, u0=None, rtol=1e-8, max_iters=500) → ElasticitySolution.  The arguments are
     elasticity_solve's.  ϕ is read once, here: after ϕ has moved, build a new operator.  `levels`, `free_dofs`, `fixed_dofs`;
-    apply(x), cells(), stiffness(level) show the operator; close() releases the device memory."""
+    apply(x), cells(), stiffness(level) show the operator; modes(m, …) → ElasticityModes, its lowest vibration modes; close() releases
+    the device memory."""
 
     def __init__(self, phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", dirichlet=None, level=0.0, precond="mg"):
         what = "elasticity_solve"
@@ -2854,6 +2855,11 @@ class ElasticityOperator:
                 raise
             raise ValueError(f"{what}: " + why.format(detail=getattr(e, "detail", 0))) from None
         self.levels, self.free_dofs, self.fixed_dofs = stats[0], stats[1], stats[2]
+        self._phi, self._level = (None if E is not None else phi), float(level)      # the density of modes() is read from the same ϕ
+
+    def modes(self, m, *, rho_in=1.0, rho_out=1e-6, rho=None, x0=None, rtol=1e-6, max_iters=300):
+        """the m smallest eigenpairs of K u = λ M u for this operator (the fixed components zero): an ElasticityModes.  See elasticity_modes."""
+        return ElasticityModes(self, m, rho_in=rho_in, rho_out=rho_out, rho=rho, x0=x0, rtol=rtol, max_iters=max_iters)
 
     def _handle(self):
         if self._h is None:
@@ -2958,6 +2964,170 @@ def elasticity_solve(phi_or_eq, f, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plan
         return op.solve(f, u0=u0, rtol=rtol, max_iters=max_iters)
     except BaseException:
         op.close()
+        raise
+
+
+# ----------------------------------------------------------------------------- vibration modes (the eigenfrequency objective of a structural optimisation)
+
+def _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, from_phi):
+    """elasticity_modes' refusals that need neither a field nor a device; returns ρ as a host array, a device tensor or None"""
+    what = "elasticity_modes"
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+        raise TypeError(f"{what}: m must be an integer, not {type(m).__name__}")
+    if not 1 <= int(m) <= 8:
+        raise ValueError(f"{what}: m must be between 1 and 8, not {m}")
+    rtol = float(rtol)
+    if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+        raise ValueError(f"{what}: rtol must be positive and finite, max_iters at least 1")
+    if rho is None:
+        if not from_phi:
+            raise ValueError(f"{what}: the operator was built from cell moduli `E`, not from ϕ: give the cell densities `rho`")
+        if not (_finite_positive(float(rho_in)) and _finite_positive(float(rho_out))):
+            raise ValueError(f"{what}: rho_in and rho_out must be finite and positive")
+        return None
+    if hasattr(rho, "is_cuda"):
+        return rho
+    rho = np.asarray(rho, dtype=np.float64)
+    if not _finite_positive(rho):
+        raise ValueError(f"{what}: the cell densities `rho` must be finite and positive")
+    return rho
+
+
+class ElasticityModes:
+    """elasticity_modes' result: `eigenvalues` (λ_k = ω_k², ascending), `frequencies` (√λ/2π), `iterations` (block iterations),
+    `relres` (per mode, the recursive ‖A x − λ M x‖₂/(λ‖M x‖₂)), `operator`; mode(k) → N ROCMeshFields normalised to ∫ρ|u|² = 1, exact
+    zeros on the fixed components, the sign unspecified; sensitivity(k) → the ROCMeshField g = e − λ_k·ρ̄·|u|², the integrand of
+    dλ_k/dΩ that a NormalMotionTerm takes as its speed; vectors() → a host array (m, N) + n, the next design's `x0`; mass() → the
+    lumped node mass, n-shaped; solve(x0=None, rtol=…, max_iters=…) runs again; close() releases the device memory.  The object
+    borrows its operator: after operator.close() every use is a ValueError."""
+
+    def __init__(self, op, m, *, rho_in=1.0, rho_out=1e-6, rho=None, x0=None, rtol=1e-6, max_iters=300):
+        self._h = None
+        rho = _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, getattr(op, "_phi", None) is not None)
+        self.operator, self.m = op, int(m)
+        b = self.backend = op.backend
+        n = tuple(int(k) for k in op.mesh.n)
+        if 3 * self.m > op.free_dofs:
+            raise ValueError(f"elasticity_modes: 3·m = {3 * self.m} exceeds the {op.free_dofs} free components")
+        cells = tuple(k - 1 for k in n)
+        if rho is not None and not hasattr(rho, "is_cuda") and rho.ndim and rho.shape != cells:
+            raise ValueError(f"elasticity_modes: `rho` has shape {rho.shape}, the grid has {cells} cells")
+        rho_dev = None if rho is None else b.node_array(rho, "rho", cells)
+        try:
+            self._h = b.modes_create(op._handle(), None if rho is not None else op._phi.buf, op._level, rho_in, rho_out, rho_dev, self.m)
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                raise ValueError("elasticity_modes: " + str(e).split(": ", 2)[-1]) from None
+            raise
+        self.eigenvalues = self.relres = None
+        self.iterations = 0
+        self.solve(x0=x0, rtol=rtol, max_iters=max_iters)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the ElasticityModes object is closed")
+        self.operator._handle()     # ValueError once the operator is closed: the modes object borrows it
+        return self._h
+
+    def solve(self, x0=None, rtol=1e-6, max_iters=300):
+        h = self._handle()
+        b, op, m = self.backend, self.operator, self.m
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("elasticity_modes: rtol must be positive and finite, max_iters at least 1")
+        n = tuple(int(k) for k in op.mesh.n)
+        xd = None
+        if x0 is not None:
+            if b.torch.is_tensor(x0):
+                xd = b.node_array(x0, "x0", (m, op.ndim) + n)
+            else:
+                a = np.asarray(x0, dtype=np.float64)
+                if a.shape != (m, op.ndim) + n:
+                    raise ValueError(f"elasticity_modes: x0 has shape {a.shape}, expected {(m, op.ndim) + n}")
+                if not np.all(np.isfinite(a)):
+                    raise ValueError("elasticity_modes: x0 must be finite")
+                xd = b.torch.from_numpy(np.concatenate([a[k, i].reshape(-1, order="F") for k in range(m) for i in range(op.ndim)])).to(b.device)
+        try:
+            code, lam, rel, it, stats = b.modes_solve(h, m, xd, rtol, int(max_iters))
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                raise ValueError("elasticity_modes: x0 must be finite") from None
+            raise
+        self.eigenvalues, self.relres, self.iterations, self.stats = lam, rel, it, stats
+        if code != L.OK:
+            msg = b.lib.lsm_last_error(b.h)
+            err = L.LsmNotConvergedError(f"lsm_elastic_modes_solve failed ({code}): {msg.decode() if msg else ''}")
+            err.eigenvalues, err.relres, err.iterations, err.modes = lam, rel, it, self
+            raise err
+        return self
+
+    @property
+    def frequencies(self):
+        return np.sqrt(self.eigenvalues) / (2.0 * math.pi)
+
+    def _k(self, k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"elasticity_modes: the mode index must be an integer, not {type(k).__name__}")
+        if not 0 <= int(k) < self.m:
+            raise ValueError(f"elasticity_modes: mode {k} of {self.m}")
+        return int(k)
+
+    def mode(self, k):
+        h, k, op = self._handle(), self._k(k), self.operator
+        u = [ROCMeshField(self.backend, op.mesh, op.bcs) for _ in range(op.ndim)]
+        self.backend.modes_store(h, k, [c.buf for c in u])
+        return tuple(u)
+
+    def sensitivity(self, k):
+        h, k, op = self._handle(), self._k(k), self.operator
+        g = ROCMeshField(self.backend, op.mesh, op.bcs)
+        self.backend.modes_sensitivity(h, k, g.buf)
+        return g
+
+    def vectors(self):
+        h, op, m = self._handle(), self.operator, self.m
+        n = tuple(int(k) for k in op.mesh.n)
+        nn = int(np.prod(n))
+        x = self.backend.modes_vectors(h, m * op.ndim * nn).cpu().numpy()
+        return np.stack([np.stack([x[(k * op.ndim + i) * nn:(k * op.ndim + i + 1) * nn].reshape(n, order="F") for i in range(op.ndim)]) for k in range(m)])
+
+    def mass(self):
+        h = self._handle()
+        n = tuple(int(k) for k in self.operator.mesh.n)
+        return self.backend.modes_mass(h).cpu().numpy().reshape(n, order="F")
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.modes_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def elasticity_modes(phi_or_eq, m, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", dirichlet=None, level=0.0, precond="mg", rho_in=1.0, rho_out=1e-6,
+                     rho=None, x0=None, rtol=1e-6, max_iters=300):
+    """The m (1 … 8) lowest vibration modes of the ersatz-material structure of ϕ: the smallest eigenpairs of K u = λ M u, λ = ω², on
+    the device.  K is elasticity_solve's operator with its arguments (`E_in` … `precond`), the fixed components of
+    `dirichlet` are zero for the modes whatever values it prescribes, and a structure needs enough of them to hold every rigid-body
+    motion.  M is a lumped mass: the density of a cell is rho_out + (rho_in − rho_out)·θ with the modulus' fill fraction θ, or
+    `rho` (a scalar or an array of shape n − 1), which is required when `E` gave the moduli.  Keep rho_out/rho_in far below
+    E_out/E_in (the defaults: 1e-6 against 1e-3): with equal densities the ersatz material is as heavy as the structure and a
+    thousand times softer, and the lowest "modes" are spurious ones that live in the void, below the structure's first frequency.
+    A locally optimal block preconditioned CG (LOBPCG) from `x0` (a host array (m, N) + n, such as the last design's vectors();
+    a fixed pseudo-random start without one) until ‖K x − λ M x‖₂ ≤ rtol·λ·‖M x‖₂ for every mode.  Returns an ElasticityModes, whose
+    `operator` the caller closes.  Raises ValueError / TypeError for what is refused (elasticity_solve's refusals, m outside 1 … 8,
+    3·m above the free components, densities not finite and positive, `E` without `rho`, a non-finite x0) and LsmNotConvergedError,
+    which carries `eigenvalues`, `relres`, `iterations` and `modes`, when max_iters does not suffice."""
+    rho = _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, E is None)
+    op = ElasticityOperator(phi_or_eq, E_in=E_in, E_out=E_out, E=E, nu=nu, plane=plane, dirichlet=dirichlet, level=level, precond=precond)
+    try:
+        return op.modes(m, rho_in=rho_in, rho_out=rho_out, rho=rho, x0=x0, rtol=rtol, max_iters=max_iters)
+    except BaseException as e:
+        if not isinstance(e, L.LsmNotConvergedError):     # the partial results of a failed solve still need their operator
+            op.close()
         raise
 
 

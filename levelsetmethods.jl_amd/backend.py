@@ -525,6 +525,40 @@ class HipBackend:
     def elastic_destroy(self, obj):
         self.lib.lsm_elastic_destroy(obj)
 
+    # ---- vibration modes (lsm_elastic_modes_*): the modes object borrows the elastic object
+    def modes_create(self, obj, phi, level, rho_in, rho_out, rho_cells, m):
+        out = C.c_void_p()
+        L.check(self.h, self.lib.lsm_elastic_modes_create(obj, self.ptr(phi), float(level), float(rho_in), float(rho_out), self.ptr(rho_cells), int(m),
+                                                          C.byref(out)), "lsm_elastic_modes_create")
+        return out
+
+    def modes_mass(self, md):
+        out = self.torch.empty(int(np.prod(self.local_shape())), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_modes_mass(md, self.ptr(out)), "lsm_elastic_modes_mass")
+        return out
+
+    def modes_solve(self, md, m, x0, rtol, max_iters):
+        """returns (status, λ, relres, iterations, stats); status is OK or ERR_NOT_CONVERGED (whose message lsm_last_error keeps), anything else raises"""
+        lam, rel, it, stats = (C.c_double * m)(), (C.c_double * m)(), C.c_int(0), (C.c_int64 * 4)()
+        code = self.lib.lsm_elastic_modes_solve(md, self.ptr(x0), float(rtol), int(max_iters), lam, rel, C.byref(it), stats)
+        if code != L.ERR_NOT_CONVERGED:
+            L.check(self.h, code, "lsm_elastic_modes_solve")
+        return code, np.array(lam[:]), np.array(rel[:]), it.value, tuple(int(v) for v in stats)
+
+    def modes_vectors(self, md, count):
+        out = self.torch.empty(int(count), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_modes_vectors(md, self.ptr(out)), "lsm_elastic_modes_vectors")
+        return out
+
+    def modes_store(self, md, k, u):
+        L.check(self.h, self.lib.lsm_elastic_modes_store(md, int(k), *self._u3(u)), "lsm_elastic_modes_store")
+
+    def modes_sensitivity(self, md, k, g):
+        L.check(self.h, self.lib.lsm_elastic_modes_sensitivity(md, int(k), self.ptr(g)), "lsm_elastic_modes_sensitivity")
+
+    def modes_destroy(self, md):
+        self.lib.lsm_elastic_modes_destroy(md)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""
