@@ -49,7 +49,13 @@ def _mask(cs):
 
 
 def _kwargs(cs):
-    return dict(E_in=cs["E_in"], E_out=cs["E_out"], E=cs["E"], nu=cs["nu"], plane=cs["plane"], dirichlet=(_mask(cs), tuple(cs["g"])))
+    return dict(E_in=cs["E_in"], E_out=cs["E_out"], E=cs["E"], nu=cs["nu"], plane=cs["plane"], dirichlet=(_mask(cs), tuple(cs["g"])),
+                level=cs.get("level", 0.0))
+
+
+def _guess(cs):
+    """the case's guess for u0= (its fixed components are overwritten by the prescribed values), or None"""
+    return None if cs.get("u0") is None else np.asarray(cs["u0"], dtype=np.float64)
 
 
 def _values(u):
@@ -79,10 +85,7 @@ def lsm_error():
     return _lsm().LsmError
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_k0_cells_apply_and_energy_are_the_restatements_bits(name):
-    lsm = _lsm()
-    s = R.solved(name)
+def check_bits(lsm, s):
     cs = s["case"]
     phi = _field(lsm, cs)
     dev = lsm.ElasticityOperator(phi, **_kwargs(cs))
@@ -92,7 +95,7 @@ def test_k0_cells_apply_and_energy_are_the_restatements_bits(name):
     assert dev.fixed_dofs == int(op.fixed.sum()) and dev.free_dofs == int(op.free.sum())
     assert np.array_equal(_bits(dev.cells()), _bits(op.E))
     if cs["E"] is None:
-        scalar = lsm.EllipticOperator(phi, a_in=cs["E_in"], a_out=cs["E_out"], c=1.0)
+        scalar = lsm.EllipticOperator(phi, a_in=cs["E_in"], a_out=cs["E_out"], c=1.0, level=cs.get("level", 0.0))
         assert np.array_equal(_bits(dev.cells()), _bits(scalar.cells()))
         scalar.close()
     x = np.random.default_rng(11).standard_normal((len(cs["n"]),) + tuple(cs["n"]))
@@ -107,11 +110,16 @@ def test_k0_cells_apply_and_energy_are_the_restatements_bits(name):
     dev.close()
 
 
+@pytest.mark.parametrize("name", NAMES)
+def test_k0_cells_apply_and_energy_are_the_restatements_bits(name):
+    check_bits(_lsm(), R.solved(name))
+
+
 def check_solve(lsm, s, name, precond):
     cs, op = s["case"], s["hier"].ops[0]
     uref, itref, _, _ = s[precond]
     phi = _field(lsm, cs)
-    sol = lsm.elasticity_solve(phi, s["f"], rtol=RTOL, max_iters=3000, precond=precond, **_kwargs(cs))
+    sol = lsm.elasticity_solve(phi, s["f"], u0=_guess(cs), rtol=RTOL, max_iters=3000, precond=precond, **_kwargs(cs))
     u = _values(sol.u)
     u64 = u.astype(np.float64)
     g = s["u0"].astype(cs["dtype"])
