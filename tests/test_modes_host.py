@@ -4,7 +4,11 @@ densities, the exported symbols, and the Python API's refusals on fake fields.
 
 The eigenvalue bar (relative error ≤ rtol) is loose by about four decades — the error is second order in the residual, the measured
 largest is 5.4e-10 — and the residual bars are the sharp ones: the recursive relres ≤ rtol and the true residual, with A x in the
-stated order, ≤ 2·rtol·λ·‖M x‖₂ (tests/test_gpu_elliptic.py's bar for a recursive residual)."""
+stated order, ≤ 2·rtol·λ·‖M x‖₂ (tests/test_gpu_elliptic.py's bar for a recursive residual).
+
+For tests/test_gpu_modes_edges.py: the restated Jacobi against eigh and in long double, the trace against solves cut short, the locked
+start, and the conditions under which a single iterate is defined to rounding, per step case (its print-out lists the yardsticks, the
+Gram gaps and every relres)."""
 import numpy as np
 import pytest
 
@@ -40,6 +44,109 @@ def test_a_warm_start_needs_no_iteration():
     s = R.solved("33x33_m4", 1e-6)
     again = R.lobpcg(s["hier"], s["mass"], 4, s["X"], 1e-6, 10)
     assert again["iters"] == 0 and again["converged"]
+
+
+# ---- single iterations: what tests/test_gpu_modes_edges.py relies on
+
+def test_the_restated_jacobi_solves_the_small_problems_as_eigh_does_and_in_long_double_further():
+    rng = np.random.default_rng(3)
+    q, m = 9, 3
+    S = rng.standard_normal((q, 40))
+    GM = S @ S.T
+    GA = S @ np.diag(rng.random(40) + 0.5) @ S.T
+    C0, th0, d0 = R.rayleigh_ritz(GA, GM, m)
+    C1, th1, d1 = R.rayleigh_ritz_jacobi(GA, GM, m)
+    C2, th2, d2 = R.rayleigh_ritz_jacobi(GA, GM, m, dt=R.LD)
+    assert d0 == d1 == d2 == 0 and C2.dtype == R.LD
+    sg = np.sign(np.sum(C0 * C1, axis=0))
+    err64 = max(float(np.abs(C0 * sg - C1).max()), float(np.abs(th0 - th1).max() / th0.max()))
+    # the pencil's residual GA·C − GM·C·θ and the M-orthonormality, both evaluated in long double
+    GAl, GMl = GA.astype(R.LD), GM.astype(R.LD)
+    res = {k: float(np.abs(GAl @ C - (GMl @ C) * th).max() / np.abs(GAl).max()) for k, (C, th) in (("eigh", (C0.astype(R.LD), th0.astype(R.LD))),
+                                                                                                   ("jacobi", (C1.astype(R.LD), th1.astype(R.LD))), ("ld", (C2, th2)))}
+    orth = float(np.abs(C2.T @ GMl @ C2 - np.eye(m)).max())
+    print(f"eigh against jacobi {err64:.1e}; residuals {res}; long-double orthonormality {orth:.1e}")
+    assert err64 <= 1e-11 and res["eigh"] <= 1e-12 and res["jacobi"] <= 1e-12
+    assert res["ld"] <= 1e-16 and orth <= 1e-16             # three decades under float64's rounding: the sweeps ran in long double
+    w, V = R.em_jacobi(GM)
+    assert np.all(np.diff(w) >= 0) and np.abs(V.T @ GM @ V - np.diag(w)).max() <= 1e-13 * w.max()
+    # two equal columns: one direction is dropped, fewer than m are left
+    G2 = np.array([[2.0, 2.0], [2.0, 2.0]])
+    for rr in (R.rayleigh_ritz, R.rayleigh_ritz_jacobi):
+        with pytest.raises(R.NotPositive) as e:
+            rr(3.0 * G2, G2, 2)
+        assert e.value.args == (1,)
+
+
+def test_a_trace_changes_nothing_and_its_record_k_is_the_solve_stopped_after_k_iterations():
+    b = R.base("9x12_m8")
+    hier, Mn = b["hier"], b["mass"]
+    full = R.lobpcg(hier, Mn, 8, None, 1e-6, 600)
+    traced = R.lobpcg(hier, Mn, 8, None, 1e-6, 600, trace=True)
+    assert full["iters"] == traced["iters"] == R.ITERS["9x12_m8"][0] and len(traced["steps"]) == full["iters"] + 1
+    assert np.array_equal(full["X"], traced["X"]) and np.array_equal(full["lam"], traced["lam"])
+    for k in (0, 1, 3):
+        cut, rec = R.lobpcg(hier, Mn, 8, None, 1e-6, k), traced["steps"][k]
+        assert cut["iters"] == k and not cut["converged"]
+        assert np.array_equal(cut["X"], rec["X"]) and np.array_equal(cut["lam"], rec["lam"]) and np.array_equal(cut["relres"], rec["relres"])
+        assert cut["applies"] == rec["applies"] == 8 * k and cut["dropped"] == rec["dropped"]
+    assert traced["steps"][-1]["act"] == () and traced["steps"][0]["act"] == tuple(range(8))
+
+
+def test_the_locked_start_holds_exact_eigenvectors_and_perturbed_ones():
+    r = R.step_ref("9x12_m4_lock02")
+    op, Mn, x0 = r["hier"].ops[0], r["mass"], r["x0"]
+    assert x0.shape == (4, 2, 9, 12) and not np.any(x0[:, op.fixed])
+    lam = R.exact(op, Mn, 8)
+    for k in range(4):
+        rq = float(np.sum(x0[k] * op.apply_free(x0[k])) / np.sum(Mn[None] * x0[k] * x0[k]))
+        tr, mn = R.true_residual(op, Mn, x0[k], rq)
+        print(f"column {k}: Rayleigh quotient {rq:.6g} (λ_k {lam[k]:.6g}), relative residual {tr / (rq * mn):.2e}")
+        if k in (0, 2):
+            assert abs(rq - lam[k]) <= 1e-12 * lam[k] and tr <= 1e-11 * rq * mn
+        else:
+            want = (lam[k] + 0.09 * lam[4 + k] + 0.01 * lam[3 + k]) / 1.1        # the eigenvectors are M-orthonormal
+            assert abs(rq - want) <= 1e-10 * want and tr >= 0.1 * rq * mn
+
+
+@pytest.mark.parametrize("name", list(R.step_cases()))
+def test_the_step_cases_are_well_defined(name):
+    """what makes an iterate comparable to rounding: the three restatements (float64 with eigh, float64 with the device's Jacobi, long
+    double) take the same decisions at every step up to the last observed one, none of them near its threshold, and differ by rounding"""
+    r = R.step_ref(name)
+    cs, rtol = r["case"], R.STEP_RTOL
+    m, locked = cs["m"], cs["locked"] or ()
+    assert len(r["steps"]) == max(cs["ks"]) + 1 and cs["ks"][0] == 0
+    for k, s in enumerate(r["steps"]):
+        ld = s["ld"]
+        rel = ld["relres"].astype(np.float64)
+        gap = ld["mu"][0] / ld["mu"][1]
+        yx, yl = (s["yard_x"] / s["scale"]).astype(np.float64), (s["yard_lam"] / ld["lam"]).astype(np.float64)
+        print(f"{name} k = {k}{'' if k in cs['ks'] else ' (not observed)'}: active {ld['act']}, dropped {ld['dropped']}, V-cycles {ld['applies']}, smallest/largest of the "
+              f"M-Gram {gap:.1e}, relres {np.array2string(rel, precision=1)}, yardstick in max|x| {np.array2string(yx, precision=1)}, in λ {np.array2string(yl, precision=1)}")
+        for v in ("eigh", "jacobi"):
+            assert s[v]["act"] == ld["act"] and s[v]["dropped"] == ld["dropped"] == 0 and s[v]["applies"] == ld["applies"]
+            assert min(s[v]["mu"]) >= 1e-9 * max(s[v]["mu"])
+        assert gap >= 1e-9
+        assert len(ld["act"]) == m - len(locked)
+        assert all(rel[j] >= 10 * rtol if j in ld["act"] else rel[j] <= rtol / 10 for j in range(m))
+        assert np.all(yx <= 1e-10) and np.all(yl <= 1e-10)
+        assert not np.any(ld["X"][:, r["hier"].ops[0].fixed])
+    acts = [s["ld"]["act"] for s in r["steps"]]
+    if name.startswith("9x12_m4_lock02"):
+        assert set(acts) == {(1, 3)}
+    if name == "9x12_m4_lock12":
+        assert set(acts) == {(0, 3)}
+    if name == "6x5x7_m3_lock1":
+        assert acts == [(1, 2)] + [(0, 2)] * 4
+    if name == "5x5_one_level_m2_lock0":
+        assert r["hier"].levels == 1 and set(acts) == {(1,)}
+    if name in ("190x180_m2", "30x29x27_m2"):
+        nt = len(cs["n"]) * int(np.prod(cs["n"]))
+        assert 256 * 256 < nt <= 2048 * 256
+        ref = E.prototype(cs["n"])[0].ops[0]
+        mine = r["hier"].ops[0]
+        assert np.array_equal(ref.E, mine.E) and np.array_equal(ref.bits, mine.bits) and np.array_equal(ref.K0, mine.K0)
 
 
 def test_the_mass_of_a_uniform_field_is_the_integral_of_the_density():
