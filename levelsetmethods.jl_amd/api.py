@@ -1634,7 +1634,13 @@ def perimeter(ls):
         ls.state.prepare(ls.state.buf)      # ϕ[I] off the band (extrapolation) and outside the grid (BCs) for the centred gradient
         return ls.backend.band_perimeter(ls.state.buf, ls.state.mask)
     if ls.comm is not None and ls.world > 1:
-        ls._halo(ls.state.buf)          # slab interfaces: the centred gradient needs the neighbours' planes
+        # slab interfaces: the centred gradient needs the neighbours' planes
+        if ls.lib_comm:                 # the library's own communicator (RCCL or peer copies), as in _advance
+            ls.backend.fill_ghosts(ls.state.buf, 7)
+            ls.backend.halo_exchange(ls.state.buf)
+            ls.state.ghosts_dirty = False
+        else:
+            ls._halo(ls.state.buf)      # torch.distributed fallback
     return _sum_over_ranks(ls, ls.backend.perimeter_local(ls.state.buf))
 
 

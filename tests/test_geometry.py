@@ -40,6 +40,31 @@ def test_oracle_gradient_is_exact_for_linear_fields_and_curvature_vanishes_with_
     assert np.array_equal(orc.geometry(g, bc, flat, "curvature"), np.zeros((9, 11, 13)))   # src/levelsetops.jl:201
 
 
+@pytest.mark.parametrize("shape,bcspec", [((31,), (("neumann", "linear"),)), ((17, 13), (("linear", "symmetry"), (("extrapolation", 2), "neumann"))),
+                                          ((9, 7, 5), (("neumann", "linear"), "periodic", ("symmetry", ("extrapolation", 2))))])
+def test_padded_restatement_of_the_geometry_equals_the_oracle(orc, shape, bcspec):
+    """tests/_measure_ref.geometry_padded (the reference of the float32 fields behind weighted faces in
+    tests/test_gpu_field_ops.py) on the oracle's own ghost fill: gradient and normal bit for bit, curvature to the
+    rounding of pow."""
+    from _measure_ref import geometry_padded
+    nd = len(shape)
+    og = orc.Grid((-1.0, -0.7, -0.4)[:nd], (1.1, 0.9, 0.85)[:nd], shape)
+    X = np.meshgrid(*og.coords(), indexing="ij")
+    phi = np.asfortranarray(sum((1.6, 1.3, -1.4)[d] * x for d, x in enumerate(X)) + 0.05 * np.sin(3 * X[0] + 1) + 0.04 * np.cos(2.5 * X[-1]))
+    bc = orc.make_bc(bcspec, nd)
+    lay = orc.layout(og)
+    full = orc.fill_ghosts_padded(og, bc, lay, orc.to_padded(lay, nd, phi))
+    p = full[(slice(orc.GHOST - 1, -(orc.GHOST - 1)),) * nd]
+    h = og.meshsize()
+    for what in ("gradient", "normal"):
+        for got, want in zip(geometry_padded(p, h, what), orc.geometry(og, bc, phi, what)):
+            assert np.array_equal(got, want), what
+    want = orc.geometry(og, bc, phi, "curvature")
+    assert np.abs(geometry_padded(p, h, "curvature") - want).max() <= 1e-15 * np.abs(want).max()
+    flat = np.full(tuple(n + 2 for n in shape), 0.3)
+    assert np.array_equal(geometry_padded(flat, h, "curvature"), np.zeros(shape))
+
+
 def _device_state(lsm, og, phi, bc, dtype=None):
     lg = lsm.CartesianGrid(og.lc, og.hc, og.n)
     eq = lsm.LevelSetEquation(terms=(lsm.NormalMotionTerm(0.0),), ic=lsm.MeshField(phi, lg, dtype=dtype), bc=bc)

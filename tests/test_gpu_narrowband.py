@@ -7,6 +7,8 @@ import math
 import numpy as np
 import pytest
 
+from _measure_ref import _band_volume_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -429,50 +431,6 @@ def test_field_without_interface(lsm):
         assert any("no interface sample" in str(x.message) for x in w)
         assert np.array_equal(dense.current_state().values(), phi.vals)
 
-
-
-def _band_volume_ref(vals_on_band, n, h, dmin):
-    """volume(nb) restated literally (src/levelsetops.jl:49-113): dict of band values (0-based indices), scanlines along
-    dimension 1, band-free lines by the nearest band node (exact KD-tree query from the line's point n1÷2)."""
-    from scipy.spatial import cKDTree
-    d = vals_on_band
-    if not d:
-        return 0.0
-    N = len(n)
-
-    def heaviside(x, a):
-        return 1.0 if x > a else (0.0 if x < -a else 0.5 * (1.0 + x / a + np.sin(np.pi * x / a) / np.pi))
-    interface = sum(heaviside(-v, dmin) for v in d.values())
-    ks = sorted(d.keys(), key=lambda I: (tuple(I[1:][::-1]), I[0]))     # by line, then along dimension 1 (any line order will do)
-    count, lines = 0, set()
-    i, M = 0, len(ks)
-    while i < M:
-        j = i
-        while j + 1 < M and ks[j + 1][1:] == ks[i][1:]:
-            j += 1
-        lines.add(ks[i][1:])
-        first, last = ks[i], ks[j]
-        if d[first] < 0:
-            count += first[0]                    # 1-based first[1] - 1
-        if d[last] < 0:
-            count += n[0] - 1 - last[0]          # n1 - last[1]
-        for t in range(i, j):
-            gap = ks[t + 1][0] - ks[t][0] - 1
-            if gap > 0 and d[ks[t]] < 0 and d[ks[t + 1]] < 0:
-                count += gap
-        i = j + 1
-    transverse = list(np.ndindex(*n[1:])) if N > 1 else [()]
-    if len(lines) != len(transverse):
-        pts = np.array([[I[k] + 1 for k in range(N)] for I in d.keys()], dtype=float)     # 1-based, as the reference
-        neg = [v < 0 for v in d.values()]
-        tree = cKDTree(pts)
-        for t in transverse:
-            if t in lines:
-                continue
-            _, idx = tree.query(np.array([n[0] // 2] + [c + 1 for c in t], dtype=float))
-            if neg[idx]:
-                count += n[0]
-    return float(np.prod(h)) * (interface + count)
 
 
 def test_reference_band_volume_and_perimeter(lsm, orc):
