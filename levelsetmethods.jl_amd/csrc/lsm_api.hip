@@ -525,6 +525,7 @@ static int stage_impl(LsmHandle* h, const LsmTerm* terms, int nterms, const void
         a.out = (double*)out;
         a.out2 = (double*)out2;
         a.cdt = cdt; a.cdt2 = cdt2;
+        for (int d = 0; d < 3; ++d) { a.inv_h3[d] = a.inv_h[d] / 3.0; a.cdt_inv_h3[d] = cdt * a.inv_h3[d]; }
         a.mb = mb; a.me = me;
         if (first) { a.base_mode = base_mode; a.phin = (const double*)(base_mode == LSM_BASE_PSI ? psi : phin); a.out2_accum = 0; }   // the kernel always loads phin
         else       { a.base_mode = LSM_BASE_OTHER; a.phin = (const double*)out; a.out2_accum = 1; }

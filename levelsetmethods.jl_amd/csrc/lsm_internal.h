@@ -79,6 +79,9 @@ struct StageArgs {
     double base_a, base_b;   // FAST build: base = base_a·ϕⁿ + base_b·ψ (set by the launcher from base_mode)
     int out2_accum;    // 0: out2 starts from psi, 1: out2 accumulates onto itself (multi-pass)
     double cdt, cdt2;
+    // FAST build, factors formed once on the host instead of per node: inv_h/3 (a WENO5 line returns three times its value),
+    // cdt·inv_h/3 (plain WENO5 variants: the advection sum goes straight into the stage base)
+    double inv_h3[3], cdt_inv_h3[3];
     // terms of this pass, in user order: order[k] is a SLOT_*
     int nterms;
     int order[NSLOTS];

@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(NT) brick_kernel(const StageArgs a, const unsi
         const NodeIO io{po, (unsigned)sizeof(ST) * eo, 8u * eo, zb + z + a.goff[2]};
         double pre_adv[3] = {0, 0, 0}, pre_nm[3] = {0, 0, 0}, pre_curv[3] = {0, 0, 0};
         const int gi0 = bx0 + x + a.goff[0], gi1 = by0 + y + a.goff[1];
-        if constexpr (ADV != 0) coeff_prep<NDIM, NDIM, ADV_SCALED, AK>(a.adv, a, gi0, gi1, pre_adv);
+        if constexpr (ADV != 0) coeff_prep<NDIM, NDIM, ADV_SCALED, AK, adv_factor_kind(ADV, true)>(a.adv, a, gi0, gi1, pre_adv);
         if constexpr (NM != 0) coeff_prep<NDIM, 1, false, LSM_COEFF_CONST>(a.nm, a, gi0, gi1, pre_nm);
         if constexpr (CURV != 0) coeff_prep<NDIM, 1, false, LSM_COEFF_CONST>(a.curv, a, gi0, gi1, pre_curv);
         NodeOps op;
@@ -192,7 +192,7 @@ inline bool bricks_applicable(int ADV, int NM, int CURV, const StageArgs& a) {
     if ((NM && a.nm.kind != LSM_COEFF_CONST) || (CURV && a.curv.kind != LSM_COEFF_CONST)) return false;
     const int ak = ADV ? a.adv.kind : (int)LSM_COEFF_CONST;
     if (ak != LSM_COEFF_CONST && ak != LSM_COEFF_ROTATION) return false;
-    if (a.me <= a.mb || a.tune->stage_generic) return false;
+    if (a.me <= a.mb || a.tune->stage_generic || (ADV == 2 && !(a.cdt >= 0.0))) return false;   // cdt: see launch_tiled
     // 16-byte rows: the aligned layout (lsm_create), 16-byte aligned arrays; 32-bit byte offsets inside a pass
     const long long seg = a.f32 ? 4 : 2, lead = a.origin - LSM_GHOST * a.s2 - LSM_GHOST * a.s1;
     if (lead < BrickCfg::XL || lead % seg || a.s1 % 8 || a.s2 % 8 || a.origin % 8) return false;

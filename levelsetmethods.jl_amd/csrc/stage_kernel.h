@@ -35,6 +35,24 @@ constexpr bool ADV_SCALED = false;
 #else
 constexpr bool ADV_SCALED = true;    // the advection velocity is carried as u_d/h_d (see coeff_prep)
 #endif
+// What else rides in that factor (FAST, WENO5 only — the upwind kernels share coeff_prep and keep 1/h_d): bit 0 = the ⅓ of
+// a WENO5 line that returns three times its value (stage_math.h, X3), bit 1 = cdt in the plain variants, whose advection sum
+// goes straight into the stage base (node_update).  cdt >= 0 there (the launchers send other values to the general variant):
+// the sign of the product still is the sign of u_d, which picks the stencil.
+constexpr int adv_factor_kind(int ADV, bool PLAIN) {
+#if LSM_STRICT
+    return 0;
+#else
+    return ADV == 2 ? (LSM_T1 ? 1 : 0) | (LSM_T2 && PLAIN ? 2 : 0) : 0;
+#endif
+}
+template <int FK>
+LSM_DEV double adv_factor(const StageArgs& a, int k) {
+    if constexpr (FK == 3) return a.cdt_inv_h3[k];
+    else if constexpr (FK == 2) return a.cdt * a.inv_h[k];
+    else if constexpr (FK == 1) return a.inv_h3[k];
+    else return a.inv_h[k];
+}
 
 constexpr int halo_of(int ADV, int NM, int CURV, int EIK) {
     int g = 0;
@@ -120,22 +138,23 @@ LSM_DEV unsigned ldg_u8(const unsigned char* base, unsigned boff, int range) {
 // Operation order is exactly ((T1*T2)*T3)*g and lc + i*h, as in the oracle.
 // SCALED (FAST build, advection velocity only): the values produced are u_d/h_d — the factor 1/h_d and
 // the time factor g(t) are folded into the hoisted part, so the per-node remainder is one multiply.
-// KIND >= 0 fixes the coefficient kind at compile time (the "plain" kernel variants), -1 reads it from the arguments
-template <int NDIM, int NCOMP, bool SCALED = false, int KIND = -1>
+// KIND >= 0 fixes the coefficient kind at compile time (the "plain" kernel variants), -1 reads it from the arguments;
+// FK (SCALED only): what the factor holds beside 1/h_d — adv_factor_kind
+template <int NDIM, int NCOMP, bool SCALED = false, int KIND = -1, int FK = 0>
 LSM_DEV void coeff_prep(const CoeffArgs& c, const StageArgs& a, int gi0, int gi1, double pre[3]) {
     pre[0] = pre[1] = pre[2] = 0.0;
     const int kind = KIND >= 0 ? KIND : c.kind;
     if (kind == LSM_COEFF_CONST) {
 #pragma unroll
-        for (int k = 0; k < NCOMP; ++k) pre[k] = SCALED ? c.v[k] * a.inv_h[k] : c.v[k];
+        for (int k = 0; k < NCOMP; ++k) pre[k] = SCALED ? c.v[k] * adv_factor<FK>(a, k) : c.v[k];
     } else if (kind == LSM_COEFF_ROTATION) {
         const double x1 = a.lc[0] + (double)gi0 * a.h[0];
         pre[1] = c.v[0] * (x1 - c.v[1]);
-        if (SCALED) pre[1] = pre[1] * a.inv_h[1];
+        if (SCALED) pre[1] = pre[1] * adv_factor<FK>(a, 1);
         if (NDIM == 3) {
             const double x2 = a.lc[1] + (double)gi1 * a.h[1];
             pre[0] = -(c.v[0] * (x2 - c.v[2]));
-            if (SCALED) pre[0] = pre[0] * a.inv_h[0];
+            if (SCALED) pre[0] = pre[0] * adv_factor<FK>(a, 0);
         }
     } else if (kind == LSM_COEFF_SEPARABLE) {
 #pragma unroll
@@ -143,11 +162,11 @@ LSM_DEV void coeff_prep(const CoeffArgs& c, const StageArgs& a, int gi0, int gi1
             const double* T = c.sep[k];
             double p = T[gi0];
             if (NDIM == 3) p = p * T[a.gn[0] + gi1];
-            pre[k] = SCALED ? p * (c.tfac * a.inv_h[k]) : p;
+            pre[k] = SCALED ? p * (c.tfac * adv_factor<FK>(a, k)) : p;
         }
     }
 }
-template <int NDIM, int NCOMP, bool SCALED = false, int KIND = -1>
+template <int NDIM, int NCOMP, bool SCALED = false, int KIND = -1, int FK = 0>
 LSM_DEV void coeff_eval(const CoeffArgs& c, const StageArgs& a, const double pre[3], const double tz[3], int gim, long long plane_off,
                         unsigned ocol, double out[3]) {
     const int kind = KIND >= 0 ? KIND : c.kind;
@@ -158,7 +177,7 @@ LSM_DEV void coeff_eval(const CoeffArgs& c, const StageArgs& a, const double pre
         if (NDIM == 2) {
             const double x2 = a.lc[1] + (double)gim * a.h[1];
             out[0] = -(c.v[0] * (x2 - c.v[2]));
-            if (SCALED) out[0] = out[0] * a.inv_h[0];
+            if (SCALED) out[0] = out[0] * adv_factor<FK>(a, 0);
         } else {
             out[0] = pre[0];
         }
@@ -175,7 +194,7 @@ LSM_DEV void coeff_eval(const CoeffArgs& c, const StageArgs& a, const double pre
 #pragma unroll
         for (int k = 0; k < NCOMP; ++k) {
             out[k] = ldg(uniform_ptr(c.f[k] + plane_off), ocol);
-            if (SCALED) out[k] = out[k] * a.inv_h[k];
+            if (SCALED) out[k] = out[k] * adv_factor<FK>(a, k);
         }
     }
 }
@@ -232,7 +251,8 @@ LSM_DEV void node_operands(const StageArgs& a, const NodeIO& io, const double pr
     op.u[0] = op.u[1] = op.u[2] = 0.0;
     op.vnm = op.bcurv = op.s0 = op.phin = op.out2 = 0.0;
     op.have_negs = false;
-    if constexpr (ADV != 0) coeff_eval<NDIM, NDIM, ADV_SCALED, AK>(a.adv, a, pre_adv, pt.adv, io.gim, io.plane_off, io.ocold, op.u);   // FAST: u_d/h_d
+    if constexpr (ADV != 0)   // FAST: u_d/h_d (WENO5: u_d/3h_d, plain variants cdt·u_d/3h_d)
+        coeff_eval<NDIM, NDIM, ADV_SCALED, AK, adv_factor_kind(ADV, AK >= 0)>(a.adv, a, pre_adv, pt.adv, io.gim, io.plane_off, io.ocold, op.u);
     if constexpr (NM != 0) {
         double vv[3];
         coeff_eval<NDIM, 1, false, (AK >= 0 ? (int)LSM_COEFF_CONST : -1)>(a.nm, a, pre_nm, pt.nm, io.gim, io.plane_off, io.ocold, vv);
@@ -285,7 +305,7 @@ struct NodeView {
 };
 
 #if !LSM_STRICT
-// FAST: u_d·weno5^{∓}(ϕ) = |u_d|/h_d · W(undivided, upwind-ordered differences) for either sign of u_d
+// FAST: u_d·weno5^{∓}(ϕ) = |u_d|/h_d · W(undivided, upwind-ordered differences) for either sign of u_d; returns W
 // (the flipped stencil negates every difference and W is odd), so neither h nor the result needs a
 // sign select; the stencil itself is chosen with a sign-bit mask and v_bfi_b32 (≈1.9 ns) instead of
 // v_cmp + v_cndmask (≈3 ns each on gfx950).  u_d = +0 takes the left-biased stencil, where the
@@ -308,11 +328,11 @@ LSM_DEV double weno_term(const NV& nv, const StageArgs& a, double v, bool have_n
     auto lds = [&](auto Sc) {            // x / y neighbours, direction Sc::value = ±1 at compile time
         constexpr int ss = (D == 0 ? 1 : W) * decltype(Sc)::value;
         const double q0 = nv.T0[-3 * ss], q1 = nv.T0[-2 * ss], q2 = nv.T0[-ss], q4 = nv.T0[ss], q5 = nv.T0[2 * ss];
-        return weno5_undivided_pq<PQ>(q1 - q0, q2 - q1, nv.c - q2, q4 - nv.c, q5 - q4, epsf, P, Q);
+        return weno5_undivided_pq<PQ, LSM_T1 != 0>(q1 - q0, q2 - q1, nv.c - q2, q4 - nv.c, q5 - q4, epsf, P, Q);
     };
     auto reg = [&](auto Sc) {            // march-axis neighbours from the register line
         constexpr int ss = decltype(Sc)::value;
-        return weno5_undivided_pq<PQ>(nv.z(-2 * ss) - nv.z(-3 * ss), nv.z(-ss) - nv.z(-2 * ss), nv.c - nv.z(-ss),
+        return weno5_undivided_pq<PQ, LSM_T1 != 0>(nv.z(-2 * ss) - nv.z(-3 * ss), nv.z(-ss) - nv.z(-2 * ss), nv.c - nv.z(-ss),
                                       nv.z(ss) - nv.c, nv.z(2 * ss) - nv.z(ss), epsf, P, Q);
     };
     constexpr bool IN_LDS = D == 0 || (D == 1 && NDIM == 3);
@@ -341,9 +361,9 @@ LSM_DEV double weno_term(const NV& nv, const StageArgs& a, double v, bool have_n
             q[4] = sel64(m, nv.z(1), nv.z(-1));
             q[5] = sel64(m, nv.z(2), nv.z(-2));
         }
-        w = weno5_undivided_pq<PQ>(q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] - q[3], q[5] - q[4], epsf, P, Q);
+        w = weno5_undivided_pq<PQ, LSM_T1 != 0>(q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] - q[3], q[5] - q[4], epsf, P, Q);
     }
-    return __builtin_fabs(v) * w;          // v = u_d/h_d
+    return w;          // times |v|, v = u_d/h_d (LSM_T1: u_d/3h_d and three times the line's value): the caller's
 }
 #endif
 
@@ -374,6 +394,17 @@ template <int NDIM, int ADV, int NM, int CURV, int EIK, int G, int W, class ST, 
 LSM_DEV void node_update(const StageArgs& a, const NV& nv, const NodeOps& op, double& r_out, double& r_out2) {
     const double c = nv.c;
     double Ladv = 0.0, Lnm = 0.0, Lcurv = 0.0, Leik = 0.0;
+#if LSM_STRICT
+    constexpr bool ADV_TO_BASE = false;
+#else
+    // plain WENO5 variants: op.u holds cdt·u_d/3h_d, the three lines sum to -cdt·Ladv (the small terms among themselves) and
+    // base_b·ψ, then base_a·ϕⁿ, join by one FMA each — ϕⁿ behind the arithmetic as before.  One instruction less than
+    // Ladv, base and base - cdt·Ladv, and two roundings at the size of ϕ instead of three.
+    constexpr bool ADV_TO_BASE = (adv_factor_kind(ADV, PLAIN) & 2) != 0;
+    // Eikonal with the current sign: on equal spacings the tail takes the undivided Godunov sum (eikonal_tail_raw)
+    constexpr bool EIK_RAW = LSM_T3 && EIK == 2;
+#endif
+    [[maybe_unused]] double adv_base = 0.0;
     double A[3] = {0, 0, 0}, B[3] = {0, 0, 0};   // second-order ENO pairs (NormalMotion, Eikonal)
 #if LSM_STRICT
     constexpr bool ENO_FROM_WENO = false;
@@ -393,7 +424,13 @@ LSM_DEV void node_update(const StageArgs& a, const NV& nv, const NodeOps& op, do
 #if LSM_STRICT
                 der = weno_dim<NDIM, D, G, W>(nv, a, v);
 #else
-                return weno_term<NDIM, D, G, W, ENO_FROM_WENO>(nv, a, v, op.have_negs, op.negs[D], A[D], B[D]);
+                const double w = weno_term<NDIM, D, G, W, ENO_FROM_WENO>(nv, a, v, op.have_negs, op.negs[D], A[D], B[D]);
+                if constexpr (ADV_TO_BASE) {
+                    adv_base = D == 0 ? -(__builtin_fabs(v) * w) : __builtin_fma(-__builtin_fabs(v), w, adv_base);
+                    return 0.0;
+                } else {
+                    return __builtin_fabs(v) * w;
+                }
 #endif
             } else {
 #if LSM_STRICT
@@ -560,39 +597,55 @@ LSM_DEV void node_update(const StageArgs& a, const NV& nv, const NodeOps& op, do
             if (d == 0) { mA = x; mB = y; } else { mA = mA + x; mB = mB + y; }
         }
         const double n2 = mA + mB;
-#else
-        double n2 = 0.0;
-        // the sign of ϕ is the same across most waves (away from the interface): a scalar branch to the version
-        // without the sign factor
-        const unsigned long long poss = __builtin_amdgcn_ballot_w64(s > 0);
-        if (LSM_UNIFORM_PATHS && poss == __builtin_amdgcn_ballot_w64(true)) {
-            n2 = godunov_sum<NDIM, true>(A, B, a.inv_h2, a.uniform_h != 0);
-        } else if (LSM_UNIFORM_PATHS && poss == 0) {
-            n2 = godunov_sum<NDIM, false>(A, B, a.inv_h2, a.uniform_h != 0);
-        } else {
-            const double sg = s > 0 ? 1.0 : -1.0;
-#pragma unroll
-            for (int d = 0; d < NDIM; ++d) n2 += godunov_term(sg, A[d], B[d], a.inv_h2[d]);
-        }
-#endif
-#if LSM_STRICT
         const double nrm = lsm_sqrt(n2);
-#else
-        const double nrm = fast_norm(n2);
-#endif
         double S;
         if constexpr (EIK == 1) {
             S = s;
         } else {
-#if LSM_STRICT
             const double den = lsm_sqrt(c * c + (nrm * nrm) * (a.dxmin * a.dxmin));
             S = den == 0.0 ? 0.0 : lsm_div(c, den);
-#else
-            const double d2 = __builtin_fma(n2, a.dxmin * a.dxmin, c * c);
-            S = c * fast_rsqrt(__builtin_fmax(d2, 1.0e-300));   // d2 == 0 implies c == 0: S = 0
-#endif
         }
         Leik = S * (nrm - 1);
+#else
+        // the sign of ϕ is the same across most waves (away from the interface): a scalar branch to the version
+        // without the sign factor
+        const unsigned long long poss = __builtin_amdgcn_ballot_w64(s > 0);
+        if (EIK_RAW && a.uniform_h != 0) {          // wave-uniform: a scalar branch, where godunov_sum has its own
+            double s2 = 0.0;                        // h²|∇ϕ|²
+            if (LSM_UNIFORM_PATHS && poss == __builtin_amdgcn_ballot_w64(true)) {
+                s2 = godunov_sum<NDIM, true, true>(A, B, a.inv_h2, true);
+            } else if (LSM_UNIFORM_PATHS && poss == 0) {
+                s2 = godunov_sum<NDIM, false, true>(A, B, a.inv_h2, true);
+            } else {
+                const double sg = s > 0 ? 1.0 : -1.0;
+#pragma unroll
+                for (int d = 0; d < NDIM; ++d) s2 += godunov_term_raw(sg, A[d], B[d]);
+            }
+            double root, S;
+            eikonal_tail_raw(vmax_floor(s2), c, root, S);
+            Leik = S * __builtin_fma(root, a.inv_h[0], -1.0);      // |∇ϕ| - 1 = √s/h - 1 in one FMA
+        } else {
+            double n2 = 0.0;
+            if (LSM_UNIFORM_PATHS && poss == __builtin_amdgcn_ballot_w64(true)) {
+                n2 = godunov_sum<NDIM, true>(A, B, a.inv_h2, a.uniform_h != 0);
+            } else if (LSM_UNIFORM_PATHS && poss == 0) {
+                n2 = godunov_sum<NDIM, false>(A, B, a.inv_h2, a.uniform_h != 0);
+            } else {
+                const double sg = s > 0 ? 1.0 : -1.0;
+#pragma unroll
+                for (int d = 0; d < NDIM; ++d) n2 += godunov_term(sg, A[d], B[d], a.inv_h2[d]);
+            }
+            const double nrm = fast_norm(n2);
+            double S;
+            if constexpr (EIK == 1) {
+                S = s;
+            } else {
+                const double d2 = __builtin_fma(n2, a.dxmin * a.dxmin, c * c);
+                S = c * fast_rsqrt(__builtin_fmax(d2, 1.0e-300));   // d2 == 0 implies c == 0: S = 0
+            }
+            Leik = S * (nrm - 1);
+        }
+#endif
     }
 
     // ---- stage combination — src/timestepping.jl:129-136,147-163,172-200
@@ -607,7 +660,7 @@ LSM_DEV void node_update(const StageArgs& a, const NV& nv, const NodeOps& op, do
     // no control flow between the loads issued before the barrier and this first use of ϕⁿ, which therefore stays
     // BEHIND the arithmetic (the scheduling barrier pins it there) — its latency is hidden, not waited for.
     __builtin_amdgcn_sched_barrier(0);
-    base = __builtin_fma(a.base_a, op.phin, a.base_b * c);
+    base = __builtin_fma(a.base_a, op.phin, ADV_TO_BASE ? __builtin_fma(a.base_b, c, adv_base) : a.base_b * c);     // adv_base = -cdt·Ladv
 #endif
     double b2 = !PLAIN && a.out2_accum ? op.out2 : c;
     const bool has2 = !PLAIN && a.out2 != nullptr;
@@ -617,7 +670,7 @@ LSM_DEV void node_update(const StageArgs& a, const NV& nv, const NodeOps& op, do
             base -= a.cdt * L;
             if (has2) b2 -= a.cdt2 * L;
         };
-        if constexpr (ADV != 0) acc(Ladv);
+        if constexpr (ADV != 0 && !ADV_TO_BASE) acc(Ladv);
         if constexpr (NM != 0) acc(Lnm);
         if constexpr (CURV != 0) acc(Lcurv);
         if constexpr (EIK != 0) acc(Leik);
@@ -781,7 +834,7 @@ __device__ __forceinline__ void stage_tile(const StageArgs& a, unsigned tile_id,
     double pre_adv[3] = {0, 0, 0}, pre_nm[3] = {0, 0, 0}, pre_curv[3] = {0, 0, 0};
     {
         const int gi0 = cx + a.goff[0], gi1 = HAS_Y ? cy + a.goff[1] : 0;
-        if constexpr (ADV != 0) coeff_prep<NDIM, NDIM, ADV_SCALED, AK>(a.adv, a, gi0, gi1, pre_adv);
+        if constexpr (ADV != 0) coeff_prep<NDIM, NDIM, ADV_SCALED, AK, adv_factor_kind(ADV, PLAIN)>(a.adv, a, gi0, gi1, pre_adv);
         if constexpr (NM != 0) coeff_prep<NDIM, 1, false, CK>(a.nm, a, gi0, gi1, pre_nm);
         if constexpr (CURV != 0) coeff_prep<NDIM, 1, false, CK>(a.curv, a, gi0, gi1, pre_curv);
     }
@@ -1301,8 +1354,9 @@ void launch_tiled(const StageArgs& a, hipStream_t s) {
     // coefficients, and a catalogued advection coefficient
 #if !LSM_STRICT
     int ak = -1;
+    // (cdt >= 0: the plain WENO5 variants carry cdt in the advection factor, whose sign picks the stencil)
     const bool plain = !b.out2 && b.natural && (!NM || b.nm.kind == LSM_COEFF_CONST) && (!CURV || b.curv.kind == LSM_COEFF_CONST) &&
-                       !b.tune->stage_generic;
+                       !b.tune->stage_generic && (ADV != 2 || b.cdt >= 0.0);
     const bool masked = b.mask != nullptr;          // narrow band: the plain variants exist with and without the band mask
     if (plain) ak = ADV ? b.adv.kind : (int)LSM_COEFF_CONST;
     if (ak == LSM_COEFF_FIELD) ak = -1;

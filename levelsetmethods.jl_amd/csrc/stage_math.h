@@ -87,6 +87,20 @@ LSM_DEV double lsm_div(double a, double b) { return a / b; }
 
 #else  // ------------------------------------------------------------------ FAST
 
+// A/B (build) switches of the headline tail work:
+//   LSM_T1  a WENO5 line returns THREE times its value, the 1/3 rides in the advection factor (1/h_d, g(t), ...)
+//   LSM_T2  plain variants: cdt in that factor too, the advection sum goes straight into the stage base
+//   LSM_T3  Eikonal (current sign, equal spacings): the tail works on the undivided Godunov sum
+#ifndef LSM_T1
+#define LSM_T1 1
+#endif
+#ifndef LSM_T2
+#define LSM_T2 1
+#endif
+#ifndef LSM_T3
+#define LSM_T3 1
+#endif
+
 // Reciprocal / reciprocal square root: hardware seed (measured on MI355X: 2^-24.4 / 2^-24.2 relative,
 // tools/seedacc.hip) + ONE Newton step -> 2.1e-15 / 4.1e-15.  That is ample here: these values only
 // scale correction terms that are themselves O(Δϕ), so their error enters a stage as
@@ -134,7 +148,7 @@ LSM_DEV double lsm_sqrt(double x0) {
 // sum max(σA,0)² + min(σB,0)² does not see, so a fused WENO5 + NormalMotion/Eikonal node computes its
 // ENO pairs for free.
 LSM_DEV double minmod_fast(double x, double y);
-template <bool PQ>
+template <bool PQ, bool X3 = false>
 LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, double e5, double eps_floor, double& P, double& Q) {
     const double w1 = e2 - e1, w2 = e3 - e2, w3 = e4 - e3, w4 = e5 - e4;
     if constexpr (PQ) {
@@ -157,7 +171,6 @@ LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, do
     const double r2 = __builtin_fma(A2, A2, __builtin_fma(t2, w3, eps));
     const double r3 = __builtin_fma(A3, A3, __builtin_fma(t3, w3 - A3, eps));
     const double s1 = r1 * r1, s2 = r2 * r2, s3 = r3 * r3;
-    const double dphi2 = __builtin_fma(1.0 / 3, w3, __builtin_fma(1.0 / 6, w2, e3));   // (-e2 + 5 e3 + 2 e4)/6 = e3 + w3/3 + w2/6
     // α_k ∝ c_k/s_k with c = (0.1, 0.6, 0.3); numerator and denominator multiplied by 10·s₁s₂s₃ and s₂ factored out:
     //   (ω₁/3)(A₁-A₂) + (ω₃/6)(A₂-A₃) = s₂(s₃(A₁-A₂) + 1.5 s₁(A₂-A₃)) / (3(6 s₁s₃ + s₂(3 s₁ + s₃)))
     // — 11 operations instead of 12, no pair product kept.
@@ -165,6 +178,10 @@ LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, do
     // (exactly flat data gives 0·(1/Dn) = 0, as the reference)
     const double N = s2 * __builtin_fma(1.5, s1 * (A2 - A3), s3 * (A1 - A2));
     const double Dn = __builtin_fma(6.0, s1 * s3, s2 * __builtin_fma(3.0, s1, s3));
+    // X3: three times the value — 3dϕ₂ = 3e₃ + w₃ + ½w₂ and N/Dn as it stands: the multiplication of the reciprocal by ⅓ is
+    // gone, the caller's factor (|u_d|/h_d, constant along the march axis or a product it forms anyway) carries the ⅓
+    if constexpr (X3) return __builtin_fma(fast_rcp(Dn), N, __builtin_fma(0.5, w2, __builtin_fma(3.0, e3, w3)));
+    const double dphi2 = __builtin_fma(1.0 / 3, w3, __builtin_fma(1.0 / 6, w2, e3));   // (-e2 + 5 e3 + 2 e4)/6 = e3 + w3/3 + w2/6
     return __builtin_fma(fast_rcp(Dn) * (1.0 / 3), N, dphi2);
 }
 LSM_DEV double weno5_undivided(double e1, double e2, double e3, double e4, double e5, double eps_floor) {
@@ -230,9 +247,10 @@ LSM_DEV double godunov_neg(double A, double B, double inv_h2) {   // min(A,0)² 
 }
 // Σ_d over NDIM dimensions with one sign per wave; equal spacings (the rule): the undivided squares are summed in one
 // FMA chain and scaled once (2 instructions fewer in 3-D than scaling per dimension)
-template <int NDIM, bool POS>
+// (RAW: the caller knows the spacings to be equal and takes the sum UNDIVIDED, h²·Σ — see eikonal_tail_raw)
+template <int NDIM, bool POS, bool RAW = false>
 LSM_DEV double godunov_sum(const double* A, const double* B, const double* inv_h2, bool uniform_h) {
-    if (uniform_h) {
+    if (RAW || uniform_h) {
         double s = 0.0;
 #pragma unroll
         for (int d = 0; d < NDIM; ++d) {
@@ -241,12 +259,33 @@ LSM_DEV double godunov_sum(const double* A, const double* B, const double* inv_h
             s = d == 0 ? a * a : __builtin_fma(a, a, s);
             s = __builtin_fma(b, b, s);
         }
+        if constexpr (RAW) return s;
         return s * inv_h2[0];
     }
     double s = 0.0;
 #pragma unroll
     for (int d = 0; d < NDIM; ++d) s += POS ? godunov_pos(A[d], B[d], inv_h2[d]) : godunov_neg(A[d], B[d], inv_h2[d]);
     return s;
+}
+// max(x, 1e-300) through the instruction itself, as vmax0: x arrives from the blocks of the sign branches
+LSM_DEV double vmax_floor(double x) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "s"(1.0e-300)); return r; }
+// the undivided term with a per-lane sign (waves that straddle the interface)
+LSM_DEV double godunov_term_raw(double sg, double A, double B) {
+    const double a = __builtin_fmax(sg * A, 0.0);
+    const double b = __builtin_fmin(sg * B, 0.0);
+    return __builtin_fma(a, a, b * b);
+}
+// Eikonal term with the current sign on equal spacings, from the UNDIVIDED Godunov sum s = h²|∇ϕ|² (dx = h: the smoothed
+// sign's n2·dx² IS s).  Returns √s (|∇ϕ| = √s/h is left to the caller's FMA) and S = ϕ/√(ϕ² + s).  One floor serves both:
+// sf = max(s, 1e-300), applied by the caller, makes d2 = ϕ² + sf > 0, and ϕ = 0 gives S = 0·(1/√sf) = 0.  √s by one Goldschmidt
+// step on the v_rsq_f64 seed (r ≈ 1/√sf to 2^-24: a = sf·r, q = ½ - a·½r = O(2^-24), a + a·q: relative error 1.5·q² ≈ 4e-15, what
+// fast_norm has).
+LSM_DEV void eikonal_tail_raw(double sf, double c, double& root, double& S) {
+    const double r = __builtin_amdgcn_rsq(sf);
+    const double g = sf * r, hh = 0.5 * r;
+    const double q = __builtin_fma(-g, hh, 0.5);
+    root = __builtin_fma(g, q, g);
+    S = c * fast_rsqrt(__builtin_fma(c, c, sf));
 }
 #endif
 
