@@ -30,6 +30,7 @@ struct LdsElems {              // a position in the LDS brick; reads widen exact
 };
 template <int W, int HW, class LT>
 struct BrickView {
+    static constexpr bool ZD = false;      // values, not a ring of differences (NodeView)
     LdsElems<LT> T0;
     double c;
     LSM_DEV double z(int k) const { return T0[k * HW]; }

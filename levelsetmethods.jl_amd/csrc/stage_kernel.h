@@ -31,6 +31,8 @@ namespace lsm {
 namespace LSM_NS {
 
 #if LSM_STRICT
+#define LSM_LDS7 0    // the march-ring switches (stage_math.h) are FAST only
+#define LSM_ZD 0
 constexpr bool ADV_SCALED = false;
 #else
 constexpr bool ADV_SCALED = true;    // the advection velocity is carried as u_d/h_d (see coeff_prep)
@@ -276,21 +278,34 @@ LSM_DEV void node_operands(const StageArgs& a, const NodeIO& io, const double pr
 // RN > 0: the register line is a RING of RN = 2G+1 entries — plane m+k sits in zl[(R + G + k) % RN], R = the
 // iteration's rotation, a compile-time constant of an RN-fold unrolled plane loop: advancing a plane overwrites the
 // oldest entry instead of shifting the line (2G v_mov_b64 per plane, 4 issue cycles each on gfx950).
-template <int NDIM, int G, int W, int R = 0, int RN = 0>
+// ZD (LSM_ZD, ring only): the ring holds the six undivided intervals I(j) = ϕ(j+1) - ϕ(j), j = m-3 … m+2, instead of the seven
+// values — I(m+k) sits in zl[(R + G + k) % RN], the seventh entry is the one the iteration overwrites with I(m+3) — so a plane
+// forms ONE new difference where the value ring forms five (each of them again in the four other planes that use it).  The
+// centre value comes from the LDS tile; z() is not available.
+template <int NDIM, int G, int W, int R = 0, int RN = 0, bool ZD_ = false>
 struct NodeView {
+    static constexpr bool ZD = ZD_;
     const double* T0;   // plane m   (own position)
     const double* Tm;   // plane m-1 (curvature only)
     const double* Tp;   // plane m+1 (curvature only)
     const double* zl;   // register line, z(0) = centre (MARCH only)
     double c;           // centre value
     // neighbour at offset k along the march axis
-    LSM_DEV double z(int k) const { return zl[RN > 0 ? (R + G + k + RN) % (RN > 0 ? RN : 1) : G + k]; }
+    LSM_DEV double z(int k) const {
+        static_assert(!ZD_, "a ring of differences holds no march-axis values: dz()");
+        return zl[RN > 0 ? (R + G + k + RN) % (RN > 0 ? RN : 1) : G + k];
+    }
+    // ZD: the interval between planes m+k and m+k+1, k = -3 … 2
+    LSM_DEV double dz(int k) const { return zl[(R + G + k + RN) % (RN > 0 ? RN : 1)]; }
     // neighbour at offset k along dimension D
     template <int D>
     LSM_DEV double at(int k) const {
         if constexpr (D == 0) return T0[k];
         else if constexpr (D == 1 && NDIM == 3) return T0[k * W];
-        else return z(k);
+        else {
+            static_assert(!ZD_ || D < NDIM - 1, "a ring of differences holds no march-axis values");
+            return z(k);
+        }
     }
     // neighbour at (sa along A, sb along B), A<B, for the mixed second difference
     template <int A, int B>
@@ -332,8 +347,18 @@ LSM_DEV double weno_term(const NV& nv, const StageArgs& a, double v, bool have_n
     };
     auto reg = [&](auto Sc) {            // march-axis neighbours from the register line
         constexpr int ss = decltype(Sc)::value;
-        return weno5_undivided_pq<PQ, LSM_T1 != 0>(nv.z(-2 * ss) - nv.z(-3 * ss), nv.z(-ss) - nv.z(-2 * ss), nv.c - nv.z(-ss),
-                                      nv.z(ss) - nv.c, nv.z(2 * ss) - nv.z(ss), epsf, P, Q);
+        if constexpr (NV::ZD) {          // the same differences, carried in the ring; the flipped line negates them (operand modifiers)
+            // (max |e_k| from the entries as they stand: they come from earlier iterations' blocks, stage_math.h max_abs5)
+            if constexpr (ss > 0)
+                return weno5_undivided_pq<PQ, LSM_T1 != 0, true>(nv.dz(-3), nv.dz(-2), nv.dz(-1), nv.dz(0), nv.dz(1), epsf, P, Q,
+                                                                 max_abs5(nv.dz(-3), nv.dz(-2), nv.dz(-1), nv.dz(0), nv.dz(1)));
+            else
+                return weno5_undivided_pq<PQ, LSM_T1 != 0, true>(-nv.dz(2), -nv.dz(1), -nv.dz(0), -nv.dz(-1), -nv.dz(-2), epsf, P, Q,
+                                                                 max_abs5(nv.dz(2), nv.dz(1), nv.dz(0), nv.dz(-1), nv.dz(-2)));
+        } else {
+            return weno5_undivided_pq<PQ, LSM_T1 != 0>(nv.z(-2 * ss) - nv.z(-3 * ss), nv.z(-ss) - nv.z(-2 * ss), nv.c - nv.z(-ss),
+                                          nv.z(ss) - nv.c, nv.z(2 * ss) - nv.z(ss), epsf, P, Q);
+        }
     };
     constexpr bool IN_LDS = D == 0 || (D == 1 && NDIM == 3);
     double w;
@@ -346,22 +371,27 @@ LSM_DEV double weno_term(const NV& nv, const StageArgs& a, double v, bool have_n
         else w = reg(std::integral_constant<int, -1>{});
     } else {
         const int m = ~(__double2hiint(v) >> 31);   // all ones when the sign bit of u_d is clear
-        double q[6];
-        if constexpr (IN_LDS) {
-            constexpr int st = D == 0 ? 1 : W;
-            const int ss = (st & m) | (-st & ~m);
-            q[0] = nv.T0[-3 * ss]; q[1] = nv.T0[-2 * ss]; q[2] = nv.T0[-ss];
-            q[3] = nv.c;
-            q[4] = nv.T0[ss]; q[5] = nv.T0[2 * ss];
+        if constexpr (!IN_LDS && NV::ZD) {          // per lane among the ring's intervals: what the subtractions below give
+            w = weno5_undivided_pq<PQ, LSM_T1 != 0>(sel64(m, nv.dz(-3), -nv.dz(2)), sel64(m, nv.dz(-2), -nv.dz(1)), sel64(m, nv.dz(-1), -nv.dz(0)),
+                                                    sel64(m, nv.dz(0), -nv.dz(-1)), sel64(m, nv.dz(1), -nv.dz(-2)), epsf, P, Q);
         } else {
-            q[0] = sel64(m, nv.z(-3), nv.z(3));
-            q[1] = sel64(m, nv.z(-2), nv.z(2));
-            q[2] = sel64(m, nv.z(-1), nv.z(1));
-            q[3] = nv.c;
-            q[4] = sel64(m, nv.z(1), nv.z(-1));
-            q[5] = sel64(m, nv.z(2), nv.z(-2));
+            double q[6];
+            if constexpr (IN_LDS) {
+                constexpr int st = D == 0 ? 1 : W;
+                const int ss = (st & m) | (-st & ~m);
+                q[0] = nv.T0[-3 * ss]; q[1] = nv.T0[-2 * ss]; q[2] = nv.T0[-ss];
+                q[3] = nv.c;
+                q[4] = nv.T0[ss]; q[5] = nv.T0[2 * ss];
+            } else {
+                q[0] = sel64(m, nv.z(-3), nv.z(3));
+                q[1] = sel64(m, nv.z(-2), nv.z(2));
+                q[2] = sel64(m, nv.z(-1), nv.z(1));
+                q[3] = nv.c;
+                q[4] = sel64(m, nv.z(1), nv.z(-1));
+                q[5] = sel64(m, nv.z(2), nv.z(-2));
+            }
+            w = weno5_undivided_pq<PQ, LSM_T1 != 0>(q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] - q[3], q[5] - q[4], epsf, P, Q);
         }
-        w = weno5_undivided_pq<PQ, LSM_T1 != 0>(q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] - q[3], q[5] - q[4], epsf, P, Q);
     }
     return w;          // times |v|, v = u_d/h_d (LSM_T1: u_d/3h_d and three times the line's value): the caller's
 }
@@ -715,13 +745,23 @@ __device__ __forceinline__ void stage_tile(const StageArgs& a, unsigned tile_id,
     constexpr int G = halo_of(ADV, NM, CURV, EIK);
     constexpr bool HAS_Y = NDIM == 3, MARCH = NDIM >= 2;
     constexpr int LEAD = (CURV && MARCH) ? 1 : 0;
-    constexpr int NSLOT = MARCH ? 2 * LEAD + 2 : 1;
     // the march line as a register ring with the plane loop unrolled 2G+1-fold: the WENO5 kernels in 3-D (7 moves a plane)
     // (the ring for the lighter 3-D kernels too, with 0 / 1 / 2 more planes of ψ in flight: ±3 %, no pattern — round 2, not kept)
     constexpr bool ZROT = LSM_ZROT && !LSM_STRICT && NDIM == 3 && ADV == 2;
+    // ... and without curvature one LDS slot per ring position: plane m0+k lives in slot k mod (2G+1), the unrolled copy's rotation —
+    // a compile-time constant, so every ds_read / ds_write of the plane loop takes its slot as an immediate offset from per-thread
+    // bases formed once per tile (two slots need the slot's parity, which a 7-fold unrolled loop has to compute every plane)
     constexpr int W = TX + 2 * G;
     constexpr int H = HAS_Y ? TY + 2 * G : 1;
     constexpr int HW = H * W;
+    // (five workgroups per CU share 160 KB of LDS: a tile whose seven slots exceed 32 KB less the tail ticket keeps two; the largest
+    // immediate, slot 6 + the tile's last element, then fits the 16-bit DS offset as well)
+    // Only the plain dense WENO5 + Eikonal (current sign) kernels, which sit at five waves per SIMD with two slots as with seven: the
+    // lighter WENO5 kernels run seven or eight waves on 8.5 KB of LDS and would fall to five, the masked and general variants stand
+    // at the 96-register edge and lose a wave to the ring's registers (compiler's resource summary)
+    constexpr bool LDS7 = LSM_LDS7 && ZROT && LEAD == 0 && PLAIN && !MASKED && !NM && EIK == 2 && (2 * G + 1) * HW * 8 + 64 <= 32768;
+    constexpr bool ZD = LSM_ZD && LDS7;             // the ring holds first differences (NodeView)
+    constexpr int NSLOT = LDS7 ? 2 * G + 1 : (MARCH ? 2 * LEAD + 2 : 1);
     constexpr int NT = TX * TY;
     constexpr int NHX = 2 * G * TY;
     constexpr int WY = CURV ? W : TX;
@@ -881,6 +921,17 @@ __device__ __forceinline__ void stage_tile(const StageArgs& a, unsigned tile_id,
             for (int h = 0; h < HPT; ++h)
                 if (hv[h]) tile[slot * HW + hl[h]] = hp[slot][h];
         }
+        // ZD: a plane's centre values go to their LDS slot when they arrive — here those of planes m0+1 … m0+G, in the loop plane
+        // m+G+1 at the end of iteration m (with 2G+1 slots that slot was last read at iteration m-G; the one barrier per plane
+        // still orders every write before its reads) — and the line becomes the ring of intervals, zlast the value to form the next from
+        [[maybe_unused]] double zlast = 0.0;
+        if constexpr (ZD) {
+#pragma unroll
+            for (int s = 1; s <= G; ++s) tile[s * HW + lpos] = zl[G + s];
+            zlast = zl[2 * G];
+#pragma unroll
+            for (int j = 0; j < 2 * G; ++j) zl[j] = zl[j + 1] - zl[j];
+        }
         // narrow band: only band nodes are updated (src/timestepping.jl loops over active_nodeindices).  The mask byte
         // of a plane is fetched one plane ahead, unconditionally: without a mask the descriptor's range is 0 and the
         // load returns 0 without an access (a load inside a branch would cost the loop its exact wait counts).
@@ -940,25 +991,29 @@ __device__ __forceinline__ void stage_tile(const StageArgs& a, unsigned tile_id,
             const bool on = active && (nomask || mk != 0);
             double r1 = 0.0, r2 = 0.0;
             if (NOMASK ? any_active : __builtin_amdgcn_ballot_w64(on) != 0) {   // a wave without a node to update skips the arithmetic (band mode)
-                const int rel = m - m0;
-                const double* T0 = tile + ((rel + LEAD) % NSLOT) * HW + lpos;
+                const int rel = m - m0;          // LDS7: rel % NSLOT == R, every copy of the unrolled loop starts at a multiple of NSLOT
+                const double* T0 = tile + (LDS7 ? R : (rel + LEAD) % NSLOT) * HW + lpos;
                 const double* Tm = tile + ((rel + LEAD + NSLOT - 1) % NSLOT) * HW + lpos;
                 const double* Tp = tile + ((rel + LEAD + 1) % NSLOT) * HW + lpos;
-                NodeView<NDIM, G, W, R, ROT> nv{T0, Tm, Tp, zl, zl[ROT > 0 ? (R + G) % RM : G]};
+                NodeView<NDIM, G, W, R, ROT, ZD> nv{T0, LDS7 ? nullptr : Tm, LDS7 ? nullptr : Tp, zl, ZD ? T0[0] : zl[ROT > 0 ? (R + G) % RM : G]};
                 node_update<NDIM, ADV, NM, CURV, EIK, G, W, ST, PLAIN>(a, nv, op, r1, r2);
             }
             // next plane's table entries: scalar loads, issued behind the LDS reads (they share a counter with them)
             plane_tab<NDIM, ADV, NM, CURV, AK>(a, (m + 1 < m1 ? m + 1 : m) + a.goff[NDIM - 1], pt);
             // advance the register line (ring: overwrite the oldest entry; otherwise shift), write the next plane to its ring slot
-            if constexpr (ROT > 0) {
+            if constexpr (ZD) {
+                zl[(R + 2 * G) % RM] = nxt - zlast;          // I(m+G): the one new difference, over the entry no plane reads any more
+                zlast = nxt;
+            } else if constexpr (ROT > 0) {
                 zl[R % RM] = nxt;
             } else {
 #pragma unroll
                 for (int j = 0; j < 2 * G; ++j) zl[j] = zl[j + 1];
                 zl[2 * G] = nxt;
             }
-            const int wslot = (m - m0 + 1 + 2 * LEAD) % NSLOT;
-            tile[wslot * HW + lpos] = zl[ROT > 0 ? (R + 1 + G + LEAD) % RM : G + LEAD];
+            const int wslot = LDS7 ? (R + 1) % NSLOT : (m - m0 + 1 + 2 * LEAD) % NSLOT;
+            if constexpr (ZD) tile[((R + G + 1) % NSLOT) * HW + lpos] = nxt;       // centre values of plane m+G+1
+            else tile[wslot * HW + lpos] = zl[ROT > 0 ? (R + 1 + G + LEAD) % RM : G + LEAD];
 #pragma unroll
             for (int h = 0; h < HPT; ++h)
                 if (hv[h]) tile[wslot * HW + hl[h]] = hn[h];

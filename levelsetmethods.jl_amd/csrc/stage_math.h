@@ -100,6 +100,15 @@ LSM_DEV double lsm_div(double a, double b) { return a / b; }
 #ifndef LSM_T3
 #define LSM_T3 1
 #endif
+// A/B (build) switches of the march-ring work:
+//   LSM_LDS7  3-D WENO5 kernels without curvature: one LDS slot per position of the 7-fold unrolled plane loop (immediate DS offsets)
+//   LSM_ZD    ... and the march line as a register ring of first differences (needs LSM_LDS7)
+#ifndef LSM_LDS7
+#define LSM_LDS7 1
+#endif
+#ifndef LSM_ZD
+#define LSM_ZD 1
+#endif
 
 // Reciprocal / reciprocal square root: hardware seed (measured on MI355X: 2^-24.4 / 2^-24.2 relative,
 // tools/seedacc.hip) + ONE Newton step -> 2.1e-15 / 4.1e-15.  That is ample here: these values only
@@ -148,8 +157,20 @@ LSM_DEV double lsm_sqrt(double x0) {
 // sum max(σA,0)² + min(σB,0)² does not see, so a fused WENO5 + NormalMotion/Eikonal node computes its
 // ENO pairs for free.
 LSM_DEV double minmod_fast(double x, double y);
-template <bool PQ, bool X3 = false>
-LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, double e5, double eps_floor, double& P, double& Q) {
+// max |e_k| of five differences through the instruction itself (as vmax0 below): differences that reach the line from another
+// basic block — the march ring of LSM_ZD — are not known to be canonical there, and __builtin_fmax would put a v_max_f64 |x|,|x|
+// in front of each of the five.  The same four instructions, the same value.
+LSM_DEV double max_abs5(double e1, double e2, double e3, double e4, double e5) {
+    double a, b, m;
+    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(a) : "v"(e1), "v"(e2));
+    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(b) : "v"(e3), "v"(e4));
+    asm("v_max_f64 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
+    asm("v_max_f64 %0, %1, |%2|" : "=v"(m) : "v"(m), "v"(e5));
+    return m;
+}
+// MPRE: the caller supplies m = max |e_k| (max_abs5)
+template <bool PQ, bool X3 = false, bool MPRE = false>
+LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, double e5, double eps_floor, double& P, double& Q, double m_pre = 0.0) {
     const double w1 = e2 - e1, w2 = e3 - e2, w3 = e4 - e3, w4 = e5 - e4;
     if constexpr (PQ) {
         // minmod(x, w3) = clamp of x to the interval between 0 and w3: the two share max(w3,0), min(w3,0)
@@ -158,9 +179,10 @@ LSM_DEV double weno5_undivided_pq(double e1, double e2, double e3, double e4, do
         Q = __builtin_fma(-0.5, __builtin_fmax(__builtin_fmin(w4, hi), lo), e4);
     }
     const double A1 = w2 - w1, A2 = w3 - w2, A3 = w4 - w3;
-    const double m = __builtin_fmax(__builtin_fmax(__builtin_fmax(__builtin_fabs(e1), __builtin_fabs(e2)),
-                                                   __builtin_fmax(__builtin_fabs(e3), __builtin_fabs(e4))),
-                                    __builtin_fabs(e5));
+    const double m = MPRE ? m_pre
+                          : __builtin_fmax(__builtin_fmax(__builtin_fmax(__builtin_fabs(e1), __builtin_fabs(e2)),
+                                                          __builtin_fmax(__builtin_fabs(e3), __builtin_fabs(e4))),
+                                           __builtin_fabs(e5));
     // S_k + ε scaled by 3/4 (the weights only see ratios).  (12/13)(S_k + ε) = A_k² + (3/13)·B_k² + (12/13)·ε with
     // B₁ = A₁ + 2w₂, B₂ = w₂ + w₃, B₃ = A₃ - 2w₃; B₂² = A₂² + 4w₂w₃ and (4·3/13)/(1 + 3/13) = 3/4 exactly, so dividing by
     // 16/13 leaves  r₁ = A₁² + ¾w₂(A₁ + w₂),  r₂ = A₂² + ¾w₂w₃,  r₃ = A₃² + ¾w₃(w₃ - A₃)  (+ ¾ε): no B, 10 operations
