@@ -11,73 +11,48 @@
 // stored.  The fixed components hold zero in every vector the operator is applied to (search directions, smoother iterates), so
 // the eliminated operator needs no mask on the neighbours; the rows of fixed components are set to zero.
 //
-// One PCG iteration and the V-cycle are lsm_elliptic.hip's, per component, with ω = 0.6: D⁻¹A of Q1 elasticity has eigenvalues
+// The PCG iteration and the V-cycle are mg_pcg.h's, with N components per node and ω = 0.6: D⁻¹A of Q1 elasticity has eigenvalues
 // above 2/0.8 in 3-D, where the scalar solve's ω = 0.8 is no convergent smoother.  A level with stretched cells
 // takes ω = 1.9/λ instead, λ its symbol bound on λmax(D⁻¹A), where that is smaller: with 0.6 there the V-cycle is indefinite.
+// What is this file's own:
 //   dir p = z + β p (a pass of its own, in place);  K1  q = A p,  σ = p·q   → α = ρ/σ
-//   K2  x += α p,  r −= α q,  r·r → converged?  (Jacobi: z = r/D, ρ' = r·z as well)
-// Reductions by wave.h's block_reduce_ordered; every kernel returns at once when the device status is set, the host enqueues
-// iterations in chunks and reads the status once per chunk.
 //
 // The apply (K1, the residual, the smoother) is one thread per node with all N rows: the 3^N·N neighbour values are loaded once
 // into registers (zero where there is no node), then 2^N cells × N rows × 2^N·N columns of multiply and add in the stated order.
-// -DLSM_ES_PRELOAD=0 loads each value where a cell uses it instead (measured: DESIGN.md §7.18).
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <memory>
-#include <vector>
 
 #include "el_cell.h"
-#include "lsm_handle.h"
-#include "wave.h"
+#include "mg_pcg.h"
 
 namespace lsm {
 
-#ifndef LSM_ES_PRELOAD
-#define LSM_ES_PRELOAD 1
-#endif
-static const int ES_THREADS = 256;
-static const int ES_MAXB = 2048;
-static const int ES_NCOARSE = 16;
 static const double ES_OMEGA = 0.6;
 static const double ES_SAFE = 1.9;      // ω·λmax(D⁻¹A) stays below 2 with this margin where ES_OMEGA would exceed it
-enum { ES_RUN = 0, ES_CONVERGED = 1, ES_MAXITER = 2, ES_BREAK_INPUT = -1, ES_BREAK_SIGMA = -2, ES_BREAK_RHO = -3 };
 enum { ES_BAD_PHI = 0, ES_BAD_E = 1, ES_NFIX = 2 /* 2, 3, 4: per component */, ES_NSTAT = 8 };
 
-struct EsState {
-    double rho, alpha, beta, bb, rr, rtol2, out;
-    int status, iters, max_iters, first;
-    unsigned long long nonfinite;
-    unsigned ticket[4];
-};
+struct EsVec : MgVec { double* p; };     // the search direction, updated in place
 
 struct EsLevel {
     int n[3];
     int nn;
     double h[3];
     const double* E;              // cell moduli, n−1 per axis
-    const unsigned char* fixed;   // one byte per node: bit i = component i is fixed
+    const unsigned char* mask;    // one byte per node: bit i = component i is fixed
     const double* D;              // the diagonal, component-major
     const double* K;              // the level's K0, (2^N·N)² row-major
-    double omega;                 // the level's damping: min(ES_OMEGA, ES_SAFE/λ), λ the level's symbol bound (es_symbol_lambda)
+    double om;                    // the level's damping: min(ES_OMEGA, ES_SAFE/λ), λ the level's symbol bound (es_symbol_lambda)
+
+    using Vec = EsVec;
+    static constexpr int comps(int N) { return N; }
+    __device__ __forceinline__ bool fixed(int id, int i) const { return (mask[id] >> i) & 1; }
+    __device__ __forceinline__ double omega() const { return om; }
+    static void launch_resid(int N, unsigned nb, hipStream_t s, const EsLevel& L, const double* r, const double* x, double* res, const MgState* st);
+    // the eliminated operator's N rows at a node; x holds zero on the fixed components, so there is nothing to mask
+    template <int N, bool MASK>
+    __device__ __forceinline__ void apply(int id, const int I[3], const double* x, int stride, double out[N]) const;
 };
 
-// where the fields of the handle live (padded layout)
-struct EsField { long long s1, s2, origin; int f32; };
 struct EsU { void* p[3]; };
-
-template <int N>
-__device__ __forceinline__ void es_coords(const EsLevel& L, int id, int I[3]) {
-    I[0] = id % L.n[0];
-    const int r = id / L.n[0];
-    I[1] = N > 2 ? r % L.n[1] : r;
-    I[2] = N > 2 ? r / L.n[1] : 0;
-}
-__device__ __forceinline__ long long es_padded(const EsField& F, const int I[3]) { return F.origin + I[0] + I[1] * F.s1 + I[2] * F.s2; }
-__device__ __forceinline__ bool es_fixed(const EsLevel& L, int id, int i) { return (L.fixed[id] >> i) & 1; }
-__device__ __forceinline__ bool es_finite(double x) { return x - x == 0.0; }
 
 // cell m of the 2^N around node I (bit d of m set: cell index I_d along d, clear: I_d − 1): its modulus, or zero where there is none
 template <int N>
@@ -89,15 +64,7 @@ __device__ __forceinline__ double es_cell(const EsLevel& L, const int I[3], int 
         C[d] = I[d] - 1 + ((m >> d) & 1);
         in = in && C[d] >= 0 && C[d] < L.n[d] - 1;
     }
-    return in ? L.E[C[0] + (L.n[0] - 1) * (C[1] + (N > 2 ? (L.n[1] - 1) * C[2] : 0))] : 0.0;
-}
-template <int N>
-__device__ __forceinline__ double es_mass(const EsLevel& L, const int I[3]) {
-    double m = 1.0;
-#pragma unroll
-    for (int d = 0; d < N; ++d)
-        if (I[d] == 0 || I[d] == L.n[d] - 1) m = m * 0.5;
-    return m;
+    return in ? L.E[mg_cell_index<N>(L.n, C)] : 0.0;
 }
 
 // (A x)_{I,·} in the stated order: the cells ascending; per cell and row the columns from +0, corner b ascending, component j
@@ -113,7 +80,6 @@ __device__ __forceinline__ void es_apply(const EsLevel& L, int id, const int I[3
         lo[d] = d < N && I[d] > 0;
         hi[d] = d < N && I[d] < L.n[d] - 1;
     }
-#if LSM_ES_PRELOAD
     double v[NB][N];
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
@@ -127,7 +93,6 @@ __device__ __forceinline__ void es_apply(const EsLevel& L, int id, const int I[3
             for (int j = 0; j < N; ++j) v[k][j] = xat(q, o0, o1, o2, j);
         }
     }
-#endif
     const double* __restrict__ K = L.K;
 #pragma unroll
     for (int i = 0; i < N; ++i) out[i] = 0.0;
@@ -144,11 +109,7 @@ __device__ __forceinline__ void es_apply(const EsLevel& L, int id, const int I[3
             const int o0 = (m & 1) + (b & 1) - 1, o1 = ((m >> 1) & 1) + ((b >> 1) & 1) - 1, o2 = N > 2 ? ((m >> 2) & 1) + ((b >> 2) & 1) - 1 : 0;
 #pragma unroll
             for (int j = 0; j < N; ++j) {
-#if LSM_ES_PRELOAD
                 const double val = v[(o0 + 1) + 3 * (o1 + 1) + (N > 2 ? 9 * (o2 + 1) : 0)][j];
-#else
-                const double val = in ? xat(id + o0 + o1 * s1 + o2 * s2, o0, o1, o2, j) : 0.0;
-#endif
 #pragma unroll
                 for (int i = 0; i < N; ++i) inner[i] = inner[i] + K[(a * N + i) * R + b * N + j] * val;
             }
@@ -158,20 +119,23 @@ __device__ __forceinline__ void es_apply(const EsLevel& L, int id, const int I[3
     }
 }
 
-#define ES_LOOP(id, nn) for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < (nn); id += gridDim.x * blockDim.x)
+template <int N, bool MASK>
+__device__ __forceinline__ void EsLevel::apply(int id, const int I[3], const double* x, int stride, double out[N]) const {
+    es_apply<N>(*this, id, I, [&](int q, int, int, int, int j) { return x[j * stride + q]; }, out);
+}
 
 // ---- setup of level 0: the cell moduli from ϕ (or the caller's, checked), the fixed bits counted per component
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_setup_kernel(EsLevel L, EsField F, const void* __restrict__ phi, double level, double e_in, double e_out,
+__global__ void __launch_bounds__(MG_THREADS) es_setup_kernel(EsLevel L, MgField F, const void* __restrict__ phi, double level, double e_in, double e_out,
                                                               double hmin, const double* __restrict__ e_given, double* __restrict__ E, unsigned long long* st) {
     unsigned cnt[5] = {0, 0, 0, 0, 0};
-    ES_LOOP(id, L.nn) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        if (phi && !es_finite(ld_val(phi, es_padded(F, I), F.f32))) ++cnt[ES_BAD_PHI];
+        mg_coords<N>(L.n, id, I);
+        if (phi && !mg_finite(ld_val(phi, mg_padded(F, I), F.f32))) ++cnt[ES_BAD_PHI];
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            if (es_fixed(L, id, i)) ++cnt[ES_NFIX + i];
+            if (L.fixed(id, i)) ++cnt[ES_NFIX + i];
         bool corner = true;
 #pragma unroll
         for (int d = 0; d < N; ++d) corner = corner && I[d] < L.n[d] - 1;
@@ -180,9 +144,9 @@ __global__ void __launch_bounds__(ES_THREADS) es_setup_kernel(EsLevel L, EsField
         double ev;
         if (e_given) {
             ev = e_given[ci];
-            if (!(ev > 0.0) || !es_finite(ev)) ++cnt[ES_BAD_E];
+            if (!(ev > 0.0) || !mg_finite(ev)) ++cnt[ES_BAD_E];
         } else {
-            ev = el_cell_from_phi<N>(phi, es_padded(F, I), F.s1, F.s2, F.f32, level, e_in, e_out, hmin);
+            ev = el_cell_from_phi<N>(phi, mg_padded(F, I), F.s1, F.s2, F.f32, level, e_in, e_out, hmin);
             if (!(ev > 0.0)) ++cnt[ES_BAD_E];
         }
         E[ci] = ev;
@@ -196,48 +160,30 @@ __global__ void __launch_bounds__(ES_THREADS) es_setup_kernel(EsLevel L, EsField
 
 // ---- a coarse level from the fine one: cells averaged, the fixed bits of fine node 2J.  co: the axes that coarsen
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_coarsen_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, double* __restrict__ Ec,
+__global__ void __launch_bounds__(MG_THREADS) es_coarsen_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, double* __restrict__ Ec,
                                                                 unsigned char* __restrict__ fixc) {
     const int co[3] = {co0, co1, co2};
-    const int k = co0 + co1 + co2;
-    const double scale = k == 1 ? 0.5 : k == 2 ? 0.25 : 0.125;
-    ES_LOOP(id, Lc.nn) {
+    const double scale = mg_coarsen_scale(co0 + co1 + co2);
+    MG_LOOP(id, Lc.nn) {
         int J[3];
-        es_coords<N>(Lc, id, J);
+        mg_coords<N>(Lc.n, id, J);
         const int fid = (co[0] ? 2 * J[0] : J[0]) + Lf.n[0] * ((co[1] ? 2 * J[1] : J[1]) + (N > 2 ? Lf.n[1] * (co[2] ? 2 * J[2] : J[2]) : 0));
-        fixc[id] = Lf.fixed[fid];
+        fixc[id] = Lf.mask[fid];
         bool corner = true;
 #pragma unroll
         for (int d = 0; d < N; ++d) corner = corner && J[d] < Lc.n[d] - 1;
         if (!corner) continue;
-        double s = 0.0;
-        bool first = true;
-#pragma unroll
-        for (int m = 0; m < (1 << N); ++m) {    // the fine cells {2J, 2J+1} per coarsened axis, ascending
-            int C[3] = {0, 0, 0};
-            bool use = true;
-#pragma unroll
-            for (int d = 0; d < N; ++d) {
-                const int b = (m >> d) & 1;
-                if (!co[d] && b) use = false;
-                C[d] = co[d] ? 2 * J[d] + b : J[d];
-            }
-            if (!use) continue;
-            const double v = Lf.E[C[0] + (Lf.n[0] - 1) * (C[1] + (N > 2 ? (Lf.n[1] - 1) * C[2] : 0))];
-            s = first ? v : s + v;
-            first = false;
-        }
-        Ec[J[0] + (Lc.n[0] - 1) * (J[1] + (N > 2 ? (Lc.n[1] - 1) * J[2] : 0))] = s * scale;
+        Ec[mg_cell_index<N>(Lc.n, J)] = mg_cell_average<N>(Lf.E, Lf.n, J, co, scale);
     }
 }
 
 // ---- the diagonal of a level: D_{I,i} = Σ_C E_C·K0[(a,i),(a,i)]
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_diag_kernel(EsLevel L, double* __restrict__ D) {
+__global__ void __launch_bounds__(MG_THREADS) es_diag_kernel(EsLevel L, double* __restrict__ D) {
     constexpr int NC = 1 << N, R = NC * N;
-    ES_LOOP(id, L.nn) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
+        mg_coords<N>(L.n, id, I);
         double acc[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) acc[i] = 0.0;
@@ -256,11 +202,11 @@ __global__ void __launch_bounds__(ES_THREADS) es_diag_kernel(EsLevel L, double* 
 
 // ---- y = A x on all components, no elimination (lsm_elastic_apply)
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_apply_kernel(EsLevel L, const double* __restrict__ x, double* __restrict__ y) {
+__global__ void __launch_bounds__(MG_THREADS) es_apply_kernel(EsLevel L, const double* __restrict__ x, double* __restrict__ y) {
     const int nn = L.nn;
-    ES_LOOP(id, nn) {
+    MG_LOOP(id, nn) {
         int I[3];
-        es_coords<N>(L, id, I);
+        mg_coords<N>(L.n, id, I);
         double out[N];
         es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
 #pragma unroll
@@ -270,13 +216,13 @@ __global__ void __launch_bounds__(ES_THREADS) es_apply_kernel(EsLevel L, const d
 
 // ---- the energy density e_I = (Σ_C E_C·q_C)/(existing cells around I), q_C = Σ_r u_r·(Σ_s K0[r,s]·u_s), into a field of the handle
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_energy_kernel(EsLevel L, EsField F, EsU U, void* __restrict__ e_out) {
+__global__ void __launch_bounds__(MG_THREADS) es_energy_kernel(EsLevel L, MgField F, EsU U, void* __restrict__ e_out) {
     constexpr int NC = 1 << N, R = NC * N;
     const double* __restrict__ K = L.K;
-    ES_LOOP(id, L.nn) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        const long long at = es_padded(F, I);
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
         double acc = 0.0, cnt = 0.0;
 #pragma unroll 1
         for (int m = 0; m < NC; ++m) {
@@ -308,35 +254,29 @@ __global__ void __launch_bounds__(ES_THREADS) es_energy_kernel(EsLevel L, EsFiel
 
 // ---- Πh·Σ b·u is finished on the host: this reduces Σ (m·f)·u over the components
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_compliance_kernel(EsLevel L, EsField F, const double* __restrict__ f, EsU U, double* partial, EsState* st) {
+__global__ void __launch_bounds__(MG_THREADS) es_compliance_kernel(EsLevel L, MgField F, const double* __restrict__ f, EsU U, double* partial, MgState* st) {
     double red[1] = {0.0};
-    ES_LOOP(id, L.nn) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        const double m = es_mass<N>(L, I);
-        const long long at = es_padded(F, I);
+        mg_coords<N>(L.n, id, I);
+        const double m = mg_mass<N>(L.n, I);
+        const long long at = mg_padded(F, I);
 #pragma unroll
         for (int i = 0; i < N; ++i) red[0] += (m * f[i * L.nn + id]) * ld_val(U.p[i], at, F.f32);
     }
-    if (!block_reduce_ordered<1, ES_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<1, MG_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
     st->out = red[0];
 }
 
 // ---- PCG
-struct EsVec {
-    double *x, *r, *q, *p, *z;   // z: where the preconditioner leaves M r
-    double* partial;
-    EsState* st;
-};
-
 // x₀ = u (the guess and the prescribed values) as fp64, p = 0
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_load_kernel(EsLevel L, EsField F, EsVec V, EsU U) {
+__global__ void __launch_bounds__(MG_THREADS) es_load_kernel(EsLevel L, MgField F, EsVec V, EsU U) {
     const int nn = L.nn;
-    ES_LOOP(id, nn) {
+    MG_LOOP(id, nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        const long long at = es_padded(F, I);
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             V.x[i * nn + id] = ld_val(U.p[i], at, F.f32);
@@ -346,22 +286,22 @@ __global__ void __launch_bounds__(ES_THREADS) es_load_kernel(EsLevel L, EsField 
 }
 // b = m·f, r₀ = b − A x₀ on the free components, 0 on the fixed ones; ‖b_free‖², ‖r₀‖²; jac: z = r/D and ρ = r·z as well
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_init_kernel(EsLevel L, EsVec V, const double* __restrict__ x, const double* __restrict__ f,
+__global__ void __launch_bounds__(MG_THREADS) es_init_kernel(EsLevel L, EsVec V, const double* __restrict__ x, const double* __restrict__ f,
                                                              double* __restrict__ rv, double* __restrict__ zv, int jac) {
     double red[4] = {0.0, 0.0, 0.0, 0.0};     // ‖b_free‖², ‖r₀‖², r·z, non-finite entries (a count below 2^53: exact)
     const int nn = L.nn;
-    ES_LOOP(id, nn) {
+    MG_LOOP(id, nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        const double m = es_mass<N>(L, I);
+        mg_coords<N>(L.n, id, I);
+        const double m = mg_mass<N>(L.n, I);
         double out[N];
         es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const double ui = x[i * nn + id], fi = f[i * nn + id];
-            if (!es_finite(ui) || !es_finite(fi)) red[3] += 1.0;
+            if (!mg_finite(ui) || !mg_finite(fi)) red[3] += 1.0;
             double r = 0.0, z = 0.0;
-            if (!es_fixed(L, id, i)) {
+            if (!L.fixed(id, i)) {
                 const double b = m * fi;
                 r = b - out[i];
                 red[0] += b * b;
@@ -375,306 +315,81 @@ __global__ void __launch_bounds__(ES_THREADS) es_init_kernel(EsLevel L, EsVec V,
             if (jac) zv[i * nn + id] = z;
         }
     }
-    if (!block_reduce_ordered<4, ES_THREADS>(red, V.partial, &V.st->ticket[0]) || threadIdx.x != 0) return;
-    EsState& S = *V.st;
-    S.bb = red[0] > 0.0 ? red[0] : red[1];      // f ≡ 0 on the free components: the norm of the eliminated right-hand side
-    S.rr = red[1];
-    S.rho = red[2];
-    S.alpha = 0.0; S.beta = 0.0;
-    S.iters = 0;
-    S.first = 1;
-    S.nonfinite = (unsigned long long)red[3];
-    if (red[3] > 0.0 || !es_finite(red[0]) || !es_finite(red[1])) S.status = ES_BREAK_INPUT;
-    else if (red[1] <= S.rtol2 * S.bb) S.status = ES_CONVERGED;
-    else if (jac && !(red[2] > 0.0)) S.status = ES_BREAK_RHO;
-    else S.status = ES_RUN;
-    if (jac) S.first = 0;
+    if (!block_reduce_ordered<4, MG_THREADS>(red, V.partial, &V.st->ticket[0]) || threadIdx.x != 0) return;
+    mg_init_tail(*V.st, red, jac);
 }
 
 // the search direction over the nt = N·nn unknowns, in place: p = z + β p (z and p are zero on the fixed components, so p stays zero there)
-__global__ void __launch_bounds__(ES_THREADS) es_dir_kernel(int nt, EsVec V) {
-    if (V.st->status != ES_RUN) return;
+__global__ void __launch_bounds__(MG_THREADS) es_dir_kernel(int nt, EsVec V) {
+    if (V.st->status != MG_RUN) return;
     const double beta = V.st->beta;
     const double* __restrict__ z = V.z;
     double* __restrict__ p = V.p;
-    ES_LOOP(k, nt) p[k] = z[k] + beta * p[k];
+    MG_LOOP(k, nt) p[k] = z[k] + beta * p[k];
 }
 // K1: q = A p, σ = p·q, α = ρ/σ.  The direction has a pass of its own, in place: one vector less than lsm_elliptic.hip's double-buffered
 // p, and the apply loads 3^N·N values, not twice as many.  The vectors are __restrict__ parameters, not fields of V: read through
 // the struct, this kernel and es_init_kernel compiled to 3.2 KB of scratch per lane in 3-D.
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_k1_kernel(EsLevel L, const double* __restrict__ p, double* __restrict__ qv, double* partial, EsState* st) {
-    if (st->status != ES_RUN) return;
+__global__ void __launch_bounds__(MG_THREADS) es_k1_kernel(EsLevel L, const double* __restrict__ p, double* __restrict__ qv, double* partial, MgState* st) {
+    if (st->status != MG_RUN) return;
     const int nn = L.nn;
     double red[1] = {0.0};
-    ES_LOOP(id, nn) {
+    MG_LOOP(id, nn) {
         int I[3];
-        es_coords<N>(L, id, I);
+        mg_coords<N>(L.n, id, I);
         double out[N];
         es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return p[j * nn + q]; }, out);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             double q = 0.0;
-            if (!es_fixed(L, id, i)) {
+            if (!L.fixed(id, i)) {
                 q = out[i];
                 red[0] += p[i * nn + id] * q;
             }
             qv[i * nn + id] = q;
         }
     }
-    if (!block_reduce_ordered<1, ES_THREADS>(red, partial, &st->ticket[1]) || threadIdx.x != 0) return;
-    EsState& S = *st;
-    const double alpha = S.rho / red[0];
-    if (!(red[0] > 0.0) || !es_finite(alpha)) { S.status = ES_BREAK_SIGMA; return; }
-    S.alpha = alpha;
-}
-
-// K2 over the nt = N·nn unknowns: x += α p, r −= α q, r·r → converged?; JAC: z = r/D, ρ' = r·z, β = ρ'/ρ
-template <int JAC>
-__global__ void __launch_bounds__(ES_THREADS) es_k2_kernel(const double* __restrict__ D, int nt, EsVec V) {
-    if (V.st->status != ES_RUN) return;
-    const double alpha = V.st->alpha;
-    const double* __restrict__ p = V.p;
-    double red[2] = {0.0, 0.0};
-    ES_LOOP(k, nt) {
-        V.x[k] = V.x[k] + alpha * p[k];
-        const double r = V.r[k] - alpha * V.q[k];
-        V.r[k] = r;
-        red[0] += r * r;
-        if (JAC) {
-            const double z = r / D[k];      // r is zero on the fixed components
-            V.z[k] = z;
-            red[1] += r * z;
-        }
-    }
-    if (!block_reduce_ordered<2, ES_THREADS>(red, V.partial, &V.st->ticket[2]) || threadIdx.x != 0) return;
-    EsState& S = *V.st;
-    S.iters += 1;
-    S.rr = red[0];
-    if (red[0] <= S.rtol2 * S.bb) { S.status = ES_CONVERGED; return; }
-    if (!es_finite(red[0])) { S.status = ES_BREAK_RHO; return; }
-    if (JAC) {
-        if (!(red[1] > 0.0) || !es_finite(red[1])) { S.status = ES_BREAK_RHO; return; }
-        S.beta = red[1] / S.rho;
-        S.rho = red[1];
-    }
-    if (S.iters >= S.max_iters) S.status = ES_MAXITER;
-}
-
-// the scalars after z = M r of the V-cycle: ρ' = r·z, β = ρ'/ρ (0 the first time)
-__device__ __forceinline__ void es_rho_update(EsState& S, double rz) {
-    if (!(rz > 0.0) || !es_finite(rz)) { S.status = ES_BREAK_RHO; return; }
-    S.beta = S.first ? 0.0 : rz / S.rho;
-    S.rho = rz;
-    S.first = 0;
-}
-
-// ---- the V-cycle's kernels (any level)
-// first sweep from zero: x = ω r/D, over the N·nn unknowns
-template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_smooth0_kernel(EsLevel L, const double* __restrict__ r, double* __restrict__ x, const EsState* st) {
-    if (st->status != ES_RUN) return;
-    const int nn = L.nn;
-    ES_LOOP(id, nn) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) x[i * nn + id] = es_fixed(L, id, i) ? 0.0 : (L.omega * r[i * nn + id]) / L.D[i * nn + id];
-    }
-}
-// xn = x + ω (r − A x)/D; DOT (the cycle's last sweep on level 0): r·xn and the scalars
-template <int N, int DOT>
-__global__ void __launch_bounds__(ES_THREADS) es_smooth_kernel(EsLevel L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ xn,
-                                                               double* partial, EsState* st) {
-    if (st->status != ES_RUN) return;
-    const int nn = L.nn;
-    double red[1] = {0.0};
-    ES_LOOP(id, nn) {
-        int I[3];
-        es_coords<N>(L, id, I);
-        double out[N];
-        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double v = 0.0;
-            if (!es_fixed(L, id, i)) {
-                const double ri = r[i * nn + id];
-                v = x[i * nn + id] + (L.omega * (ri - out[i])) / L.D[i * nn + id];
-                if (DOT) red[0] += ri * v;
-            }
-            xn[i * nn + id] = v;
-        }
-    }
-    if (DOT) {
-        if (!block_reduce_ordered<1, ES_THREADS>(red, partial, &st->ticket[3]) || threadIdx.x != 0) return;
-        es_rho_update(*st, red[0]);
-    }
-}
-// the fine residual, zero on the fixed components, written once (into the level's free smoother buffer), then gathered
-template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_resid_kernel(EsLevel L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ res,
-                                                              const EsState* st) {
-    if (st->status != ES_RUN) return;
-    const int nn = L.nn;
-    ES_LOOP(id, nn) {
-        int I[3];
-        es_coords<N>(L, id, I);
-        double out[N];
-        es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
-#pragma unroll
-        for (int i = 0; i < N; ++i) res[i * nn + id] = es_fixed(L, id, i) ? 0.0 : r[i * nn + id] - out[i];
-    }
-}
-// r_c = Pᵀ res / 2^k per component (blockIdx.y): a coarse node gathers from the fine nodes 2J + o, o ∈ {−1, 0, 1} per coarsened axis
-template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_gather_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, const double* __restrict__ res,
-                                                               double* __restrict__ rc, const EsState* st) {
-    if (st->status != ES_RUN) return;
-    const int co[3] = {co0, co1, co2};
-    const int k = co0 + co1 + co2;
-    const double scale = k == 1 ? 0.5 : k == 2 ? 0.25 : 0.125;
-    const int comp = blockIdx.y;
-    res += (size_t)comp * Lf.nn;
-    rc += (size_t)comp * Lc.nn;
-    ES_LOOP(id, Lc.nn) {
-        double acc = 0.0;
-        if (!es_fixed(Lc, id, comp)) {
-            int J[3];
-            es_coords<N>(Lc, id, J);
-            for (int m = 0; m < (N == 2 ? 9 : 27); ++m) {
-                const int o[3] = {m % 3 - 1, (m / 3) % 3 - 1, N > 2 ? m / 9 - 1 : 0};
-                int I[3] = {0, 0, 0};
-                double w = 1.0;
-                bool use = true;
-#pragma unroll
-                for (int d = 0; d < N; ++d) {
-                    if (!co[d]) {
-                        if (o[d] != 0) use = false;
-                        I[d] = J[d];
-                        continue;
-                    }
-                    I[d] = 2 * J[d] + o[d];
-                    if (I[d] < 0 || I[d] >= Lf.n[d]) use = false;
-                    if (o[d] == -1 || (o[d] == 1 && J[d] + 1 < Lc.n[d])) w = w * 0.5;     // the unpaired last fine node gives all it has
-                }
-                if (use) acc += w * res[I[0] + Lf.n[0] * (I[1] + (N > 2 ? Lf.n[1] * I[2] : 0))];     // zero on fixed fine components
-            }
-        }
-        rc[id] = acc * scale;
-    }
-}
-// x += P x_c on the free fine components, per component (blockIdx.y)
-template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_prolong_kernel(EsLevel Lf, EsLevel Lc, int co0, int co1, int co2, const double* __restrict__ xc,
-                                                                double* __restrict__ x, const EsState* st) {
-    if (st->status != ES_RUN) return;
-    const int co[3] = {co0, co1, co2};
-    const int comp = blockIdx.y;
-    xc += (size_t)comp * Lc.nn;
-    x += (size_t)comp * Lf.nn;
-    ES_LOOP(id, Lf.nn) {
-        if (es_fixed(Lf, id, comp)) continue;
-        int I[3];
-        es_coords<N>(Lf, id, I);
-        int J0[3] = {0, 0, 0}, two[3] = {0, 0, 0};
-#pragma unroll
-        for (int d = 0; d < N; ++d) {
-            J0[d] = co[d] ? I[d] >> 1 : I[d];
-            two[d] = co[d] && (I[d] & 1) && J0[d] + 1 < Lc.n[d];
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int m = 0; m < (1 << N); ++m) {
-            double w = 1.0;
-            bool use = true;
-            int J[3] = {0, 0, 0};
-#pragma unroll
-            for (int d = 0; d < N; ++d) {
-                const int b = (m >> d) & 1;
-                if (b && !two[d]) use = false;
-                if (two[d]) w = w * 0.5;
-                J[d] = J0[d] + b;
-            }
-            if (use) acc += w * xc[J[0] + Lc.n[0] * (J[1] + (N > 2 ? Lc.n[1] * J[2] : 0))];
-        }
-        x[id] = x[id] + acc;
-    }
-}
-// the coarsest level (≤ 128 nodes, ≤ 384 unknowns): ES_NCOARSE sweeps from zero in one workgroup, x in LDS, double-buffered
-template <int N, int DOT>
-__global__ void __launch_bounds__(128) es_coarsest_kernel(EsLevel L, const double* __restrict__ r, double* __restrict__ x, EsState* st) {
-    __shared__ double xs[2][N * 128];
-    __shared__ double red[2];
-    if (st->status != ES_RUN) return;
-    const int id = threadIdx.x, nn = L.nn;
-    const bool node = id < nn;
-    int I[3] = {0, 0, 0};
-    if (node) es_coords<N>(L, id, I);
-    bool on[N];
-    double ri[N], Di[N], v[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        on[i] = node && !es_fixed(L, id, i);
-        ri[i] = on[i] ? r[i * nn + id] : 0.0;
-        Di[i] = on[i] ? L.D[i * nn + id] : 1.0;
-        v[i] = on[i] ? (L.omega * ri[i]) / Di[i] : 0.0;
-    }
-    int cur = 0;
-    for (int s = 1; s < ES_NCOARSE; ++s) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) xs[cur][i * 128 + id] = v[i];
-        __syncthreads();
-        if (node) {
-            const double* xb = xs[cur];
-            double out[N];
-            es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return xb[j * 128 + q]; }, out);     // fixed components hold zero
-#pragma unroll
-            for (int i = 0; i < N; ++i)
-                if (on[i]) v[i] = v[i] + (L.omega * (ri[i] - out[i])) / Di[i];
-        }
-        cur ^= 1;
-    }
-    if (node) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) x[i * nn + id] = v[i];
-    }
-    if (DOT) {
-        double t = 0.0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) t += ri[i] * v[i];
-        const double s = wave_sum(t);
-        if ((id & 63) == 0) red[id >> 6] = s;
-        __syncthreads();
-        if (id == 0) es_rho_update(*st, red[0] + red[1]);
-    }
+    if (!block_reduce_ordered<1, MG_THREADS>(red, partial, &st->ticket[1]) || threadIdx.x != 0) return;
+    mg_k1_tail(*st, red[0]);
 }
 
 // ---- x → u on the free components (rounded to the storage type); the fixed components and the ghosts are left as they are
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) es_store_kernel(EsLevel L, EsField F, const double* __restrict__ x, EsU U) {
-    ES_LOOP(id, L.nn) {
+__global__ void __launch_bounds__(MG_THREADS) es_store_kernel(EsLevel L, MgField F, const double* __restrict__ x, EsU U) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        const long long at = es_padded(F, I);
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            if (!es_fixed(L, id, i)) st_val(U.p[i], at, F.f32, x[i * L.nn + id]);
+            if (!L.fixed(id, i)) st_val(U.p[i], at, F.f32, x[i * L.nn + id]);
+    }
+}
+
+// the V-cycle's fine residual in 2-D, zero on the fixed components.  mg_resid_kernel<2, EsLevel> is the same loop with the operator
+// called through EsLevel::apply, and compiled to 106 SGPRs where this form takes 98: one wave per SIMD less.
+__global__ void __launch_bounds__(MG_THREADS) es_resid2_kernel(EsLevel L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ res,
+                                                               const MgState* st) {
+    if (st->status != MG_RUN) return;
+    const int nn = L.nn;
+    MG_LOOP(id, nn) {
+        int I[3];
+        mg_coords<2>(L.n, id, I);
+        double out[2];
+        es_apply<2>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) res[i * nn + id] = L.fixed(id, i) ? 0.0 : r[i * nn + id] - out[i];
     }
 }
 
 // ---- host side
-struct ElasticObject {
-    int N = 0, precond = 0, last_iters = 0;
-    int co[32][3];                       // co[l]: the axes that coarsen from level l to l+1
-    std::vector<EsLevel> lev;
+void EsLevel::launch_resid(int N, unsigned nb, hipStream_t s, const EsLevel& L, const double* r, const double* x, double* res, const MgState* st) {
+    if (N == 2) hipLaunchKernelGGL(es_resid2_kernel, dim3(nb), dim3(MG_THREADS), 0, s, L, r, x, res, st);
+    else hipLaunchKernelGGL((mg_resid_kernel<3, EsLevel>), dim3(nb), dim3(MG_THREADS), 0, s, L, r, x, res, st);
+}
+struct ElasticObject : MgSolver<EsLevel> {
     std::vector<std::vector<double>> k0; // the levels' K0 as computed (what the device holds)
-    std::vector<double*> rhs, xa, xb;    // per level ≥ 1: right-hand side and the two smoother buffers; level 0: xa, xb only
-    EsVec V;
-    EsField F;
-    long long nfree = 0, nfixed = 0;
-    DevBuf<double> buf, partial;
-    DevBuf<unsigned char> fx;
-    DevBuf<EsState> st;
-    DevBuf<unsigned long long> cnt;
-    PinnedBuf<EsState> h_st;
 };
 
 // the unit element matrix of a box cell with sides h, scaled by 1/∏h (include/lsm.h states the formula): a product over the axes
@@ -747,120 +462,37 @@ static double es_symbol_lambda(int N, const std::vector<double>& K) {
     return best;
 }
 
-static unsigned es_blocks(long long n) { return (unsigned)std::min<long long>((n + ES_THREADS - 1) / ES_THREADS, ES_MAXB); }
-
-#define ES_LAUNCH(N, kernel, grid, block, stream, ...)                                              \
-    do {                                                                                            \
-        if ((N) == 2) hipLaunchKernelGGL(kernel<2>, grid, dim3(block), 0, stream, __VA_ARGS__);     \
-        else hipLaunchKernelGGL(kernel<3>, grid, dim3(block), 0, stream, __VA_ARGS__);              \
-    } while (0)
-#define ES_LAUNCH2(N, kernel, flag, grid, block, stream, ...)                                               \
-    do {                                                                                                    \
-        if ((N) == 2) hipLaunchKernelGGL((kernel<2, flag>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kernel<3, flag>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__);        \
-    } while (0)
-
-// z = M r for M = one V-cycle; the last kernel leaves ρ and β
-static void es_vcycle(ElasticObject& o, hipStream_t s) {
-    const int N = o.N, nl = (int)o.lev.size();
-    EsState* st = o.st;
-    for (int l = 0; l + 1 < nl; ++l) {
-        const EsLevel& L = o.lev[l];
-        const double* r = l == 0 ? o.V.r : o.rhs[l];
-        const unsigned nb = es_blocks(L.nn);
-        ES_LAUNCH(N, es_smooth0_kernel, dim3(nb), ES_THREADS, s, L, r, o.xa[l], (const EsState*)st);
-        ES_LAUNCH2(N, es_smooth_kernel, 0, nb, ES_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
-        ES_LAUNCH(N, es_resid_kernel, dim3(nb), ES_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], (const EsState*)st);      // xa is free until the post-smoothing
-        ES_LAUNCH(N, es_gather_kernel, dim3(es_blocks(o.lev[l + 1].nn), N), ES_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2],
-                  (const double*)o.xa[l], o.rhs[l + 1], (const EsState*)st);
-    }
-    {
-        const int l = nl - 1;
-        const double* r = l == 0 ? o.V.r : o.rhs[l];
-        if (l == 0) ES_LAUNCH2(N, es_coarsest_kernel, 1, 1, 128, s, o.lev[l], r, o.xb[l], st);
-        else ES_LAUNCH2(N, es_coarsest_kernel, 0, 1, 128, s, o.lev[l], r, o.xb[l], st);
-    }
-    for (int l = nl - 2; l >= 0; --l) {
-        const EsLevel& L = o.lev[l];
-        const double* r = l == 0 ? o.V.r : o.rhs[l];
-        const unsigned nb = es_blocks(L.nn);
-        ES_LAUNCH(N, es_prolong_kernel, dim3(nb, N), ES_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2], (const double*)o.xb[l + 1], o.xb[l],
-                  (const EsState*)st);
-        ES_LAUNCH2(N, es_smooth_kernel, 0, nb, ES_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], o.partial.p, st);
-        if (l == 0) ES_LAUNCH2(N, es_smooth_kernel, 1, nb, ES_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
-        else ES_LAUNCH2(N, es_smooth_kernel, 0, nb, ES_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
-    }
-}
-
 }  // namespace lsm
 
 using namespace lsm;
 
 struct LsmElastic { LsmHandle* h; ElasticObject* o; };
 
-#define ES_HIP(h, call)                                                                                       \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) return lsm_fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double level, double e_in, double e_out, const double* e_cells, double lam, double mu,
                      const unsigned char* fixed, int64_t stats[4]) {
     const int N = h->grid.ndim;
     o.N = N;
-    o.F = EsField{h->lay.stride[1], N > 2 ? h->lay.stride[2] : 0, h->lay.origin, h->dtype == LSM_DTYPE_F32 ? 1 : 0};
-    // the hierarchy's shapes: axis d coarsens while n_d > 5, to (n_d+1)/2 nodes; it ends when no axis coarsens
+    o.F = MgField{h->lay.stride[1], N > 2 ? h->lay.stride[2] : 0, h->lay.origin, h->dtype == LSM_DTYPE_F32 ? 1 : 0};
     std::vector<EsLevel> lev;
     EsLevel L;
     memset(&L, 0, sizeof(L));
-    long long nn = 1;
-    double hmin = INFINITY;
-    for (int d = 0; d < 3; ++d) {
-        L.n[d] = d < N ? h->nloc[d] : 1;
-        L.h[d] = d < N ? h->h[d] : 1.0;
-        nn *= L.n[d];
-        if (d < N) hmin = std::min(hmin, L.h[d]);
-    }
-    if (nn >= (1LL << 28)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the grid is too large (2^28 nodes at most)");
-    L.nn = (int)nn;
-    lev.push_back(L);
-    for (;;) {
-        const EsLevel& f = lev.back();
-        EsLevel c = f;
-        bool any = false;
-        const int l = (int)lev.size() - 1;
-        c.nn = 1;
-        for (int d = 0; d < 3; ++d) {
-            o.co[l][d] = d < N && f.n[d] > 5;
-            if (o.co[l][d]) {
-                any = true;
-                c.n[d] = (f.n[d] + 1) / 2;
-                c.h[d] = f.h[d] * 2.0;
-            }
-            c.nn *= c.n[d];
-        }
-        if (!any || lev.size() >= 31) break;
-        lev.push_back(c);
-    }
+    double hmin;
+    const long long nn = mg_shapes(h, L, 1LL << 28, lev, o.co, hmin);
+    if (lev.empty()) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the grid is too large (2^28 nodes at most)");
     const int nl = (int)lev.size();
     if (lev[nl - 1].nn > 128) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_create: the coarsest level has more than 128 nodes");
     const size_t RR = (size_t)((1 << N) * N) * (size_t)((1 << N) * N);
     // one allocation of doubles: per level K0, cells, D, xa, xb, [rhs]; level 0: x r q p as well
-    auto ncell = [&](const EsLevel& q) { long long m = 1; for (int d = 0; d < N; ++d) m *= q.n[d] - 1; return m; };
     size_t nd = 0, nb = 0;
     for (int l = 0; l < nl; ++l) {
-        nd += RR + (size_t)ncell(lev[l]) + (size_t)N * (size_t)lev[l].nn * (size_t)(3 + (l ? 1 : 4));
+        nd += RR + mg_ncells(N, lev[l]) + (size_t)N * (size_t)lev[l].nn * (size_t)(3 + (l ? 1 : 4));
         nb += (size_t)lev[l].nn;
     }
-    ES_HIP(h, o.buf.alloc(nd * sizeof(double)));
-    ES_HIP(h, o.fx.alloc(nb));
-    ES_HIP(h, o.partial.alloc(4 * ES_MAXB * sizeof(double)));
-    ES_HIP(h, o.st.alloc(sizeof(EsState)));
-    ES_HIP(h, o.cnt.alloc(ES_NSTAT * sizeof(unsigned long long)));
-    ES_HIP(h, o.h_st.alloc(sizeof(EsState)));
+    MG_HIP(h, o.buf.alloc(nd * sizeof(double)));
+    MG_HIP(h, o.fx.alloc(nb));
     hipStream_t s = h->stream;
-    ES_HIP(h, hipMemsetAsync(o.cnt.p, 0, ES_NSTAT * sizeof(unsigned long long), s));
-    ES_HIP(h, hipMemsetAsync(o.st.p, 0, sizeof(EsState), s));
+    const int ra = mg_alloc_scalars(h, o, ES_NSTAT, s);
+    if (ra != LSM_OK) return ra;
     double* b = o.buf;
     unsigned char* fb = o.fx;
     std::vector<double*> ecell(nl), dg(nl), kd(nl);
@@ -870,7 +502,7 @@ static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double lev
     for (int l = 0; l < nl; ++l) {
         const size_t m = (size_t)N * (size_t)lev[l].nn;
         kd[l] = b; b += RR;
-        ecell[l] = b; b += ncell(lev[l]);
+        ecell[l] = b; b += mg_ncells(N, lev[l]);
         dg[l] = b; b += m;
         o.xa[l] = b; b += m;
         o.xb[l] = b; b += m;
@@ -879,21 +511,19 @@ static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double lev
             o.V.x = b; b += m; o.V.r = b; b += m; o.V.q = b; b += m; o.V.p = b; b += m;
         }
         fxl[l] = fb; fb += lev[l].nn;
-        lev[l].E = ecell[l]; lev[l].D = dg[l]; lev[l].K = kd[l]; lev[l].fixed = fxl[l];
+        lev[l].E = ecell[l]; lev[l].D = dg[l]; lev[l].K = kd[l]; lev[l].mask = fxl[l];
         es_k0(N, lev[l].h, lam, mu, o.k0[l]);       // o.k0 outlives the copy: it belongs to the object
-        lev[l].omega = std::min(ES_OMEGA, ES_SAFE / es_symbol_lambda(N, o.k0[l]));
-        ES_HIP(h, hipMemcpyAsync(kd[l], o.k0[l].data(), RR * sizeof(double), hipMemcpyHostToDevice, s));
+        lev[l].om = std::min(ES_OMEGA, ES_SAFE / es_symbol_lambda(N, o.k0[l]));
+        MG_HIP(h, hipMemcpyAsync(kd[l], o.k0[l].data(), RR * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    o.V.partial = o.partial;
-    o.V.st = o.st;
-    if (fixed) ES_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
-    else ES_HIP(h, hipMemsetAsync(fxl[0], 0, (size_t)nn, s));
-    ES_LAUNCH(N, es_setup_kernel, dim3(es_blocks(nn)), ES_THREADS, s, lev[0], o.F, e_cells ? (const void*)nullptr : phi, level, e_in, e_out, hmin, e_cells,
+    if (fixed) MG_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
+    else MG_HIP(h, hipMemsetAsync(fxl[0], 0, (size_t)nn, s));
+    MG_LAUNCH(N, es_setup_kernel, dim3(mg_blocks(nn)), MG_THREADS, s, lev[0], o.F, e_cells ? (const void*)nullptr : phi, level, e_in, e_out, hmin, e_cells,
               ecell[0], o.cnt.p);
-    ES_HIP(h, hipGetLastError());
+    MG_HIP(h, hipGetLastError());
     unsigned long long c[ES_NSTAT] = {};
-    ES_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
-    ES_HIP(h, hipStreamSynchronize(s));
+    MG_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
+    MG_HIP(h, hipStreamSynchronize(s));
     o.nfixed = 0;
     int unfixed = -1;
     for (int i = N - 1; i >= 0; --i) {
@@ -911,11 +541,11 @@ static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double lev
         return lsm_fail(h, LSM_ERR_INVALID, why[reason - 1]);
     }
     for (int l = 1; l < nl; ++l)
-        ES_LAUNCH(N, es_coarsen_kernel, dim3(es_blocks(lev[l].nn)), ES_THREADS, s, lev[l - 1], lev[l], o.co[l - 1][0], o.co[l - 1][1], o.co[l - 1][2], ecell[l],
+        MG_LAUNCH(N, es_coarsen_kernel, dim3(mg_blocks(lev[l].nn)), MG_THREADS, s, lev[l - 1], lev[l], o.co[l - 1][0], o.co[l - 1][1], o.co[l - 1][2], ecell[l],
                   fxl[l]);
-    for (int l = 0; l < nl; ++l) ES_LAUNCH(N, es_diag_kernel, dim3(es_blocks(lev[l].nn)), ES_THREADS, s, lev[l], dg[l]);
-    ES_HIP(h, hipGetLastError());
-    ES_HIP(h, hipStreamSynchronize(s));
+    for (int l = 0; l < nl; ++l) MG_LAUNCH(N, es_diag_kernel, dim3(mg_blocks(lev[l].nn)), MG_THREADS, s, lev[l], dg[l]);
+    MG_HIP(h, hipGetLastError());
+    MG_HIP(h, hipStreamSynchronize(s));
     o.lev = lev;
     o.V.z = o.precond == LSM_PRECOND_JACOBI ? o.xa[0] : o.xb[0];
     if (stats) { stats[0] = nl; stats[1] = o.nfree; stats[2] = o.nfixed; stats[3] = 0; }
@@ -965,8 +595,8 @@ int lsm_elastic_apply(LsmElastic* s, const double* x, double* y) {
     if (!s) return LSM_ERR_INVALID;
     if (!x || !y || x == y) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_apply: x and y must be two arrays");
     const EsLevel& L = s->o->lev[0];
-    ES_LAUNCH(s->o->N, es_apply_kernel, dim3(es_blocks(L.nn)), ES_THREADS, s->h->stream, L, x, y);
-    ES_HIP(s->h, hipGetLastError());
+    MG_LAUNCH(s->o->N, es_apply_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, x, y);
+    MG_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -974,9 +604,8 @@ int lsm_elastic_cells(LsmElastic* s, double* e_out_cells) {
     if (!s) return LSM_ERR_INVALID;
     if (!e_out_cells) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_cells: null argument");
     const EsLevel& L = s->o->lev[0];
-    size_t m = 1;
-    for (int d = 0; d < s->o->N; ++d) m *= (size_t)(L.n[d] - 1);
-    ES_HIP(s->h, hipMemcpyAsync(e_out_cells, L.E, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
+    const size_t m = mg_ncells(s->o->N, L);
+    MG_HIP(s->h, hipMemcpyAsync(e_out_cells, L.E, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
     return LSM_OK;
 }
 
@@ -994,8 +623,8 @@ int lsm_elastic_energy(LsmElastic* s, const void* u0, const void* u1, const void
     if (!es_fields(s->o->N, u0, u1, u2, U) || !e_out || e_out == u0 || e_out == u1 || e_out == u2)
         return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_energy: the components of u and e_out must be distinct fields");
     const EsLevel& L = s->o->lev[0];
-    ES_LAUNCH(s->o->N, es_energy_kernel, dim3(es_blocks(L.nn)), ES_THREADS, s->h->stream, L, s->o->F, U, e_out);
-    ES_HIP(s->h, hipGetLastError());
+    MG_LAUNCH(s->o->N, es_energy_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, s->o->F, U, e_out);
+    MG_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1006,10 +635,10 @@ int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const
     ElasticObject& o = *s->o;
     const EsLevel& L = o.lev[0];
     hipStream_t st = s->h->stream;
-    ES_LAUNCH(o.N, es_compliance_kernel, dim3(es_blocks(L.nn)), ES_THREADS, st, L, o.F, f, U, o.partial.p, o.st.p);
-    ES_HIP(s->h, hipGetLastError());
-    ES_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(EsState), hipMemcpyDeviceToHost, st));
-    ES_HIP(s->h, hipStreamSynchronize(st));
+    MG_LAUNCH(o.N, es_compliance_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, f, U, o.partial.p, o.st.p);
+    MG_HIP(s->h, hipGetLastError());
+    MG_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+    MG_HIP(s->h, hipStreamSynchronize(st));
     double vol = 1.0;
     for (int d = 0; d < o.N; ++d) vol *= L.h[d];
     *out = vol * o.h_st.p->out;
@@ -1028,55 +657,26 @@ int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* 
     const int jac = o.precond == LSM_PRECOND_JACOBI;
     (void)hipSetDevice(h->device);
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    EsState s0;
-    memset(&s0, 0, sizeof(s0));
-    s0.rtol2 = rtol * rtol;
-    s0.max_iters = max_iters;
-    ES_HIP(h, hipMemcpyAsync(o.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
-    const unsigned nb = es_blocks(L.nn), nbt = es_blocks((long long)N * L.nn);
+    const int r0 = mg_reset(h, o, rtol, max_iters, st);
+    if (r0 != LSM_OK) return r0;
+    const unsigned nb = mg_blocks(L.nn), nbt = mg_blocks((long long)N * L.nn);
     const int nt = N * L.nn;
-    ES_LAUNCH(N, es_load_kernel, dim3(nb), ES_THREADS, st, L, o.F, o.V, U);
-    ES_LAUNCH(N, es_init_kernel, dim3(nb), ES_THREADS, st, L, o.V, (const double*)o.V.x, f, o.V.r, o.V.z, jac);
-    ES_HIP(h, hipGetLastError());
-    // iterations in chunks: the first as long as the last solve took, then doubling
-    int enq = 0;
-    int chunk = std::max(4, o.last_iters + 1);
-    for (;;) {
-        const int k = std::min(chunk, max_iters - enq);
-        for (int it = 0; it < k; ++it, ++enq) {
-            if (!jac) es_vcycle(o, st);
-            hipLaunchKernelGGL(es_dir_kernel, dim3(nbt), dim3(ES_THREADS), 0, st, nt, o.V);
-            ES_LAUNCH(N, es_k1_kernel, dim3(nb), ES_THREADS, st, L, (const double*)o.V.p, o.V.q, o.partial.p, o.st.p);
-            if (jac) hipLaunchKernelGGL(es_k2_kernel<1>, dim3(nbt), dim3(ES_THREADS), 0, st, L.D, nt, o.V);
-            else hipLaunchKernelGGL(es_k2_kernel<0>, dim3(nbt), dim3(ES_THREADS), 0, st, L.D, nt, o.V);
-        }
-        ES_HIP(h, hipGetLastError());
-        ES_HIP(h, hipMemcpyAsync(o.h_st, o.st, sizeof(EsState), hipMemcpyDeviceToHost, st));
-        ES_HIP(h, hipStreamSynchronize(st));
-        if (o.h_st.p->status != ES_RUN || enq >= max_iters) break;
-        chunk = std::min(2 * chunk, 64);
-    }
-    const EsState S = *o.h_st;
-    const double rel = S.bb > 0 ? std::sqrt(S.rr / S.bb) : (S.rr == 0 ? 0.0 : std::sqrt(S.rr));
-    if (iters_out) *iters_out = S.iters;
-    if (relres_out) *relres_out = rel;
-    if (S.status == ES_BREAK_INPUT) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "lsm_elastic_solve: f and u must be finite (%llu entries are not); u is unchanged", S.nonfinite);
-        return lsm_fail(h, LSM_ERR_INVALID, msg);
-    }
-    if (S.status != ES_CONVERGED) {
-        char msg[320];
-        const char* why = S.status == ES_MAXITER || S.status == ES_RUN ? "no convergence within max_iters"
-                          : S.status == ES_BREAK_SIGMA ? "PCG breakdown (p·Ap not positive)"
-                                                       : "PCG breakdown (r·Mr not positive, or a non-finite residual)";
-        snprintf(msg, sizeof(msg), "lsm_elastic_solve: %s: %d iterations, relative residual %.3e (rtol %.3e); u is unchanged", why, S.iters, rel, rtol);
-        return lsm_fail(h, LSM_ERR_NOT_CONVERGED, msg);
-    }
-    o.last_iters = S.iters;
-    ES_LAUNCH(N, es_store_kernel, dim3(nb), ES_THREADS, st, L, o.F, (const double*)o.V.x, U);
-    ES_HIP(h, hipGetLastError());
-    ES_HIP(h, hipStreamSynchronize(st));
+    MG_LAUNCH(N, es_load_kernel, dim3(nb), MG_THREADS, st, L, o.F, o.V, U);
+    MG_LAUNCH(N, es_init_kernel, dim3(nb), MG_THREADS, st, L, o.V, (const double*)o.V.x, f, o.V.r, o.V.z, jac);
+    MG_HIP(h, hipGetLastError());
+    const int r1 = mg_iterate(h, o, max_iters, st, [&](int) {
+        if (!jac) mg_vcycle(o, o.V.r, st);
+        hipLaunchKernelGGL(es_dir_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, nt, o.V);
+        MG_LAUNCH(N, es_k1_kernel, dim3(nb), MG_THREADS, st, L, (const double*)o.V.p, o.V.q, o.partial.p, o.st.p);
+        if (jac) hipLaunchKernelGGL(mg_k2_kernel<1>, dim3(nbt), dim3(MG_THREADS), 0, st, L.D, nt, (MgVec)o.V, (const double*)o.V.p);
+        else hipLaunchKernelGGL(mg_k2_kernel<0>, dim3(nbt), dim3(MG_THREADS), 0, st, L.D, nt, (MgVec)o.V, (const double*)o.V.p);
+    });
+    if (r1 != LSM_OK) return r1;
+    const int r2 = mg_report(h, o, "lsm_elastic_solve", rtol, iters_out, relres_out);
+    if (r2 != LSM_OK) return r2;
+    MG_LAUNCH(N, es_store_kernel, dim3(nb), MG_THREADS, st, L, o.F, (const double*)o.V.x, U);
+    MG_HIP(h, hipGetLastError());
+    MG_HIP(h, hipStreamSynchronize(st));
     return LSM_OK;
 }
 
@@ -1088,13 +688,13 @@ void lsm_elastic_destroy(LsmElastic* s) {
 
 // ======================================================================================================================================
 // elasticity_modes: the m ≤ 8 smallest eigenpairs of A x = λ M x on the free components, M the lumped mass of the ersatz density, by a
-// locally optimal block preconditioned CG (LOBPCG) whose preconditioner is es_vcycle (or 1/D).  include/lsm.h ("elasticity_modes") is
+// locally optimal block preconditioned CG (LOBPCG) whose preconditioner is mg_vcycle (or 1/D).  include/lsm.h ("elasticity_modes") is
 // the normative text, tests/_modes_ref.py restates it, DESIGN.md §7.19 has the measurements.
 //
 // Blocks.  Six blocks of m columns of nt = N·nn doubles in one allocation: X, W, P, A·X, A·W, A·P; column k of block b starts at
 // (b·m + k)·nt.  W and P hold na ≤ m columns, in slots 0 … na−1: one per column of X that has not converged (soft locking).
 // One iteration: em_resid (R = A·X − M·X·Λ into W's slots, the 2m norms) → the host picks the active columns → per active column one
-// es_vcycle with V.r pointed at the residual's slot, its result copied into W's next slot → em_apply (A·W, fixed rows zero) → em_gram
+// mg_vcycle on the residual's slot, its result copied into W's next slot → em_apply (A·W, fixed rows zero) → em_gram
 // (SᵀA S, SᵀM S, S = [X, W, P]) → the host's Rayleigh–Ritz (cyclic Jacobi) → em_update (X, P, A·X, A·P ← S·C, in place, row by row).
 // The Gram pass forms 4×4 tiles of the upper triangle, one tile per blockIdx.y: 32 fp64 accumulators a thread (both matrices), plain
 // multiply and add; each entry is summed over a thread's rows ascending, then by block_reduce_ordered.  The host mirrors the triangle.
@@ -1125,20 +725,20 @@ __device__ __forceinline__ double em_cell(const EsLevel& L, const double* __rest
 
 // ---- the cell densities: el_cell.h's value with (ρ_in, ρ_out), or the caller's, checked; cnt[0]: non-finite ϕ, cnt[1]: ρ not finite and positive
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) em_rho_kernel(EsLevel L, EsField F, const void* __restrict__ phi, double level, double rho_in, double rho_out,
+__global__ void __launch_bounds__(MG_THREADS) em_rho_kernel(EsLevel L, MgField F, const void* __restrict__ phi, double level, double rho_in, double rho_out,
                                                             double hmin, const double* __restrict__ given, double* __restrict__ rho, unsigned long long* cnt) {
     unsigned bad[2] = {0, 0};
-    ES_LOOP(id, L.nn) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        if (phi && !es_finite(ld_val(phi, es_padded(F, I), F.f32))) ++bad[0];
+        mg_coords<N>(L.n, id, I);
+        if (phi && !mg_finite(ld_val(phi, mg_padded(F, I), F.f32))) ++bad[0];
         bool corner = true;
 #pragma unroll
         for (int d = 0; d < N; ++d) corner = corner && I[d] < L.n[d] - 1;
         if (!corner) continue;
         const int ci = I[0] + (L.n[0] - 1) * (I[1] + (N > 2 ? (L.n[1] - 1) * I[2] : 0));
-        const double v = given ? given[ci] : el_cell_from_phi<N>(phi, es_padded(F, I), F.s1, F.s2, F.f32, level, rho_in, rho_out, hmin);
-        if (!(v > 0.0) || !es_finite(v)) ++bad[1];
+        const double v = given ? given[ci] : el_cell_from_phi<N>(phi, mg_padded(F, I), F.s1, F.s2, F.f32, level, rho_in, rho_out, hmin);
+        if (!(v > 0.0) || !mg_finite(v)) ++bad[1];
         rho[ci] = v;
     }
 #pragma unroll
@@ -1149,10 +749,10 @@ __global__ void __launch_bounds__(ES_THREADS) em_rho_kernel(EsLevel L, EsField F
 }
 // ---- M_I = (Σ ρ_C over the existing cells around I, ascending, from +0)·2^−N
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) em_mass_kernel(EsLevel L, const double* __restrict__ rho, double* __restrict__ Mn) {
-    ES_LOOP(id, L.nn) {
+__global__ void __launch_bounds__(MG_THREADS) em_mass_kernel(EsLevel L, const double* __restrict__ rho, double* __restrict__ Mn) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
+        mg_coords<N>(L.n, id, I);
         double acc = 0.0;
 #pragma unroll
         for (int m = 0; m < (1 << N); ++m) {
@@ -1165,7 +765,7 @@ __global__ void __launch_bounds__(ES_THREADS) em_mass_kernel(EsLevel L, const do
 }
 
 // ---- the default start: splitmix64 of the entry's linear index, its top 53 bits a double in [0, 1), mapped to (−1, 1); zero on fixed components
-__global__ void __launch_bounds__(ES_THREADS) em_init_kernel(EsLevel L, int N, long long total, const double* __restrict__ x0, double* __restrict__ X) {
+__global__ void __launch_bounds__(MG_THREADS) em_init_kernel(EsLevel L, int N, long long total, const double* __restrict__ x0, double* __restrict__ X) {
     const long long nt = (long long)N * L.nn;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         const long long r = t % nt;
@@ -1179,28 +779,28 @@ __global__ void __launch_bounds__(ES_THREADS) em_init_kernel(EsLevel L, int N, l
             z = z ^ (z >> 31);
             v = 2.0 * ((double)(z >> 11) * 0x1p-53) - 1.0;
         }
-        X[t] = es_fixed(L, id, i) ? 0.0 : v;
+        X[t] = L.fixed(id, i) ? 0.0 : v;
     }
 }
 
 // ---- y = A x per column (blockIdx.y), the rows of fixed components zero; x is zero on the fixed components
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) em_apply_kernel(EsLevel L, const double* __restrict__ x, double* __restrict__ y) {
+__global__ void __launch_bounds__(MG_THREADS) em_apply_kernel(EsLevel L, const double* __restrict__ x, double* __restrict__ y) {
     const int nn = L.nn;
     x += (size_t)blockIdx.y * (size_t)N * nn;
     y += (size_t)blockIdx.y * (size_t)N * nn;
-    ES_LOOP(id, nn) {
+    MG_LOOP(id, nn) {
         int I[3];
-        es_coords<N>(L, id, I);
+        mg_coords<N>(L.n, id, I);
         double out[N];
         es_apply<N>(L, id, I, [&](int q, int, int, int, int j) { return x[j * nn + q]; }, out);
 #pragma unroll
-        for (int i = 0; i < N; ++i) y[i * nn + id] = es_fixed(L, id, i) ? 0.0 : out[i];
+        for (int i = 0; i < N; ++i) y[i * nn + id] = L.fixed(id, i) ? 0.0 : out[i];
     }
 }
 
 // ---- R_k = A·X_k − λ_k·(M·X_k) into slot k of W, and ‖R_k‖², ‖M·X_k‖² for every k, in one pass
-__global__ void __launch_bounds__(ES_THREADS) em_resid_kernel(EmBlocks B, int nn, EmLam lam, const double* __restrict__ Mn, double* partial, unsigned* ticket,
+__global__ void __launch_bounds__(MG_THREADS) em_resid_kernel(EmBlocks B, int nn, EmLam lam, const double* __restrict__ Mn, double* partial, unsigned* ticket,
                                                               double* __restrict__ out) {
     double red[2 * EM_MAXM];
 #pragma unroll
@@ -1209,7 +809,7 @@ __global__ void __launch_bounds__(ES_THREADS) em_resid_kernel(EmBlocks B, int nn
     const double* __restrict__ X = B.base;
     const double* __restrict__ AX = B.base + (size_t)3 * B.m * nt;
     double* __restrict__ W = B.base + (size_t)B.m * nt;
-    ES_LOOP(t, (int)B.nt) {
+    MG_LOOP(t, (int)B.nt) {
         const double mass = Mn[t % nn];
 #pragma unroll
         for (int k = 0; k < EM_MAXM; ++k) {
@@ -1222,18 +822,18 @@ __global__ void __launch_bounds__(ES_THREADS) em_resid_kernel(EmBlocks B, int nn
             }
         }
     }
-    if (!block_reduce_ordered<2 * EM_MAXM, ES_THREADS>(red, partial, ticket) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<2 * EM_MAXM, MG_THREADS>(red, partial, ticket) || threadIdx.x != 0) return;
 #pragma unroll
     for (int k = 0; k < 2 * EM_MAXM; ++k) out[k] = red[k];
 }
 
 // ---- dst = src (the V-cycle's result into its slot), or src/D on the free components (the diagonal preconditioner); elementwise, so src may be dst
-__global__ void __launch_bounds__(ES_THREADS) em_precond_kernel(EsLevel L, int nt, const double* src, const double* __restrict__ D, double* dst) {
-    ES_LOOP(t, nt) dst[t] = D ? (es_fixed(L, t % L.nn, t / L.nn) ? 0.0 : src[t] / D[t]) : src[t];
+__global__ void __launch_bounds__(MG_THREADS) em_precond_kernel(EsLevel L, int nt, const double* src, const double* __restrict__ D, double* dst) {
+    MG_LOOP(t, nt) dst[t] = D ? (L.fixed(t % L.nn, t / L.nn) ? 0.0 : src[t] / D[t]) : src[t];
 }
 
 // ---- tile (bi, bj) of SᵀA S and SᵀM S: entry (a, b) of the tile is Σ_t S_{4bi+a}[t]·(A S)_{4bj+b}[t] and Σ_t S_{4bi+a}[t]·(M[t]·S_{4bj+b}[t])
-__global__ void __launch_bounds__(ES_THREADS) em_gram_kernel(EmBlocks B, int nn, EmTiles tiles, const double* __restrict__ Mn, double* partial, unsigned* tickets,
+__global__ void __launch_bounds__(MG_THREADS) em_gram_kernel(EmBlocks B, int nn, EmTiles tiles, const double* __restrict__ Mn, double* partial, unsigned* tickets,
                                                              double* __restrict__ out) {
     const int T = blockIdx.y, bi = tiles.bi[T], bj = tiles.bj[T], q = B.m + B.na + B.np;
     const double *si[EM_TILE], *sj[EM_TILE], *aj[EM_TILE];
@@ -1249,7 +849,7 @@ __global__ void __launch_bounds__(ES_THREADS) em_gram_kernel(EmBlocks B, int nn,
     double red[2 * EM_TILE * EM_TILE];
 #pragma unroll
     for (int k = 0; k < 2 * EM_TILE * EM_TILE; ++k) red[k] = 0.0;
-    ES_LOOP(t, (int)B.nt) {
+    MG_LOOP(t, (int)B.nt) {
         const double mass = Mn[t % nn];
         double xi[EM_TILE], mj[EM_TILE], yj[EM_TILE];
 #pragma unroll
@@ -1266,18 +866,18 @@ __global__ void __launch_bounds__(ES_THREADS) em_gram_kernel(EmBlocks B, int nn,
                 red[EM_TILE * EM_TILE + a * EM_TILE + b] += xi[a] * mj[b];
             }
     }
-    if (!block_reduce_ordered<2 * EM_TILE * EM_TILE, ES_THREADS>(red, partial + (size_t)T * 2 * EM_TILE * EM_TILE * gridDim.x, &tickets[T]) || threadIdx.x != 0) return;
+    if (!block_reduce_ordered<2 * EM_TILE * EM_TILE, MG_THREADS>(red, partial + (size_t)T * 2 * EM_TILE * EM_TILE * gridDim.x, &tickets[T]) || threadIdx.x != 0) return;
 #pragma unroll
     for (int k = 0; k < 2 * EM_TILE * EM_TILE; ++k) out[T * 2 * EM_TILE * EM_TILE + k] = red[k];
 }
 
 // ---- X, P ← S·C (blockIdx.y = 0) and A·X, A·P ← (A S)·C (1), row by row in place.  C: two matrices of 24 rows × 8 columns, row-major,
 // the rows in slot order (X's 8 slots, W's, P's; zero where there is no column): Cx for the new X, Cp for the new P
-__global__ void __launch_bounds__(ES_THREADS) em_update_kernel(EmBlocks B, const double* __restrict__ C) {
+__global__ void __launch_bounds__(MG_THREADS) em_update_kernel(EmBlocks B, const double* __restrict__ C) {
     const size_t nt = (size_t)B.nt;
     double* __restrict__ base = B.base + (size_t)blockIdx.y * 3 * B.m * nt;
     const int cnt[3] = {B.m, B.na, B.np};
-    ES_LOOP(t, (int)B.nt) {
+    MG_LOOP(t, (int)B.nt) {
         double s[3 * EM_MAXM];
 #pragma unroll
         for (int b = 0; b < 3; ++b)
@@ -1308,27 +908,27 @@ __device__ __forceinline__ double em_round(double v, int f32) { return f32 ? (do
 
 // ---- mode k into the N fields: x·scale rounded once to the storage type, exact zeros on the fixed components; the ghosts stay
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) em_store_kernel(EsLevel L, EsField F, const double* __restrict__ x, double scale, EsU U) {
-    ES_LOOP(id, L.nn) {
+__global__ void __launch_bounds__(MG_THREADS) em_store_kernel(EsLevel L, MgField F, const double* __restrict__ x, double scale, EsU U) {
+    MG_LOOP(id, L.nn) {
         int I[3];
-        es_coords<N>(L, id, I);
-        const long long at = es_padded(F, I);
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
 #pragma unroll
-        for (int i = 0; i < N; ++i) st_val(U.p[i], at, F.f32, es_fixed(L, id, i) ? 0.0 : x[i * L.nn + id] * scale);
+        for (int i = 0; i < N; ++i) st_val(U.p[i], at, F.f32, L.fixed(id, i) ? 0.0 : x[i * L.nn + id] * scale);
     }
 }
 
 // ---- g_I = e_I − (λ·ρ̄_I)·(Σ_i u_{I,i}², from +0, i ascending), u = the stored mode (x·scale rounded to the storage type).  e_I is
 // es_energy_kernel's, the same operations in the same order on values read from x instead of fields; ρ̄_I = (Σ ρ_C, ascending from +0)/cells
 template <int N>
-__global__ void __launch_bounds__(ES_THREADS) em_sens_kernel(EsLevel L, EsField F, const double* __restrict__ x, double scale, double lam,
+__global__ void __launch_bounds__(MG_THREADS) em_sens_kernel(EsLevel L, MgField F, const double* __restrict__ x, double scale, double lam,
                                                              const double* __restrict__ rho, void* __restrict__ g_out) {
     constexpr int NC = 1 << N, R = NC * N;
     const double* __restrict__ K = L.K;
     const int nn = L.nn, s1 = L.n[0], s2 = N > 2 ? L.n[0] * L.n[1] : 0;
-    ES_LOOP(id, nn) {
+    MG_LOOP(id, nn) {
         int I[3];
-        es_coords<N>(L, id, I);
+        mg_coords<N>(L.n, id, I);
         double acc = 0.0, cnt = 0.0, rs = 0.0;
 #pragma unroll 1
         for (int m = 0; m < NC; ++m) {
@@ -1362,7 +962,7 @@ __global__ void __launch_bounds__(ES_THREADS) em_sens_kernel(EsLevel L, EsField 
             const double u = em_round(x[i * nn + id] * scale, F.f32);
             sq = sq + u * u;
         }
-        st_val(g_out, es_padded(F, I), F.f32, acc / cnt - (lam * (rs / cnt)) * sq);
+        st_val(g_out, mg_padded(F, I), F.f32, acc / cnt - (lam * (rs / cnt)) * sq);
     }
 }
 
@@ -1512,27 +1112,27 @@ int lsm_elastic_modes_create(LsmElastic* s, const void* phi, double level, doubl
         hmin = std::min(hmin, L.h[d]);
     }
     const size_t nblk = (size_t)6 * m * (size_t)o->nt;
-    ES_HIP(h, o->buf.alloc((nblk + (size_t)L.nn + ncell + EM_OUT_N + 6 * EM_MAXM * EM_MAXM) * sizeof(double)));
-    ES_HIP(h, o->partial.alloc((size_t)std::max(32 * EM_GRAMB * EM_MAXT, 2 * EM_MAXM * ES_MAXB) * sizeof(double)));
-    ES_HIP(h, o->tickets.alloc(32 * sizeof(unsigned)));
-    ES_HIP(h, o->cnt.alloc(2 * sizeof(unsigned long long)));
-    ES_HIP(h, o->h_out.alloc(EM_OUT_N * sizeof(double)));
-    ES_HIP(h, o->h_c.alloc(6 * EM_MAXM * EM_MAXM * sizeof(double)));
+    MG_HIP(h, o->buf.alloc((nblk + (size_t)L.nn + ncell + EM_OUT_N + 6 * EM_MAXM * EM_MAXM) * sizeof(double)));
+    MG_HIP(h, o->partial.alloc((size_t)std::max(32 * EM_GRAMB * EM_MAXT, 2 * EM_MAXM * MG_MAXB) * sizeof(double)));
+    MG_HIP(h, o->tickets.alloc(32 * sizeof(unsigned)));
+    MG_HIP(h, o->cnt.alloc(2 * sizeof(unsigned long long)));
+    MG_HIP(h, o->h_out.alloc(EM_OUT_N * sizeof(double)));
+    MG_HIP(h, o->h_c.alloc(6 * EM_MAXM * EM_MAXM * sizeof(double)));
     o->B = EmBlocks{o->buf.p, o->nt, m, 0, 0};
     o->Mn = o->buf.p + nblk;
     o->rho = o->Mn + L.nn;
     o->gout = o->rho + ncell;
     o->cdev = o->gout + EM_OUT_N;
     hipStream_t st = h->stream;
-    ES_HIP(h, hipMemsetAsync(o->tickets.p, 0, 32 * sizeof(unsigned), st));
-    ES_HIP(h, hipMemsetAsync(o->cnt.p, 0, 2 * sizeof(unsigned long long), st));
-    ES_LAUNCH(N, em_rho_kernel, dim3(es_blocks(L.nn)), ES_THREADS, st, L, eo.F, rho_cells ? (const void*)nullptr : phi, level, rho_in, rho_out, hmin, rho_cells,
+    MG_HIP(h, hipMemsetAsync(o->tickets.p, 0, 32 * sizeof(unsigned), st));
+    MG_HIP(h, hipMemsetAsync(o->cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    MG_LAUNCH(N, em_rho_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, eo.F, rho_cells ? (const void*)nullptr : phi, level, rho_in, rho_out, hmin, rho_cells,
               o->rho, o->cnt.p);
-    ES_LAUNCH(N, em_mass_kernel, dim3(es_blocks(L.nn)), ES_THREADS, st, L, (const double*)o->rho, o->Mn);
-    ES_HIP(h, hipGetLastError());
+    MG_LAUNCH(N, em_mass_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, (const double*)o->rho, o->Mn);
+    MG_HIP(h, hipGetLastError());
     unsigned long long c[2] = {0, 0};
-    ES_HIP(h, hipMemcpyAsync(c, o->cnt.p, sizeof(c), hipMemcpyDeviceToHost, st));
-    ES_HIP(h, hipStreamSynchronize(st));
+    MG_HIP(h, hipMemcpyAsync(c, o->cnt.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    MG_HIP(h, hipStreamSynchronize(st));
     if (c[0]) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_create: phi must be finite");
     if (c[1]) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_create: the cell densities must be finite and positive");
     *out = new LsmModes{s, guard.release()};
@@ -1543,7 +1143,7 @@ int lsm_elastic_modes_mass(LsmModes* md, double* node_mass) {
     if (!md) return LSM_ERR_INVALID;
     LsmHandle* h = md->e->h;
     if (!node_mass) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_mass: null argument");
-    ES_HIP(h, hipMemcpyAsync(node_mass, md->o->Mn, (size_t)md->e->o->lev[0].nn * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    MG_HIP(h, hipMemcpyAsync(node_mass, md->o->Mn, (size_t)md->e->o->lev[0].nn * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return LSM_OK;
 }
 
@@ -1560,12 +1160,12 @@ static int em_gram_rr(LsmHandle* h, ElasticObject& eo, ModesObject& o, int na, i
         }
     EmBlocks B = o.B;
     B.na = na; B.np = np;
-    const unsigned nb = std::min<unsigned>(es_blocks(o.nt), EM_GRAMB);
-    hipLaunchKernelGGL(em_gram_kernel, dim3(nb, T), dim3(ES_THREADS), 0, st, B, eo.lev[0].nn, tiles, (const double*)o.Mn, o.partial.p, o.tickets.p, o.gout + EM_OUT_GRAM);
-    ES_HIP(h, hipGetLastError());
-    ES_HIP(h, hipMemcpyAsync(o.h_out.p, o.gout, (size_t)T * 32 * sizeof(double), hipMemcpyDeviceToHost, st));
-    ES_HIP(h, hipMemcpyAsync(eo.h_st, eo.st, sizeof(EsState), hipMemcpyDeviceToHost, st));
-    ES_HIP(h, hipStreamSynchronize(st));
+    const unsigned nb = std::min<unsigned>(mg_blocks(o.nt), EM_GRAMB);
+    hipLaunchKernelGGL(em_gram_kernel, dim3(nb, T), dim3(MG_THREADS), 0, st, B, eo.lev[0].nn, tiles, (const double*)o.Mn, o.partial.p, o.tickets.p, o.gout + EM_OUT_GRAM);
+    MG_HIP(h, hipGetLastError());
+    MG_HIP(h, hipMemcpyAsync(o.h_out.p, o.gout, (size_t)T * 32 * sizeof(double), hipMemcpyDeviceToHost, st));
+    MG_HIP(h, hipMemcpyAsync(eo.h_st, eo.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+    MG_HIP(h, hipStreamSynchronize(st));
     std::vector<double> GA((size_t)q * q, 0.0), GM((size_t)q * q, 0.0), C;
     for (int t = 0; t < T; ++t)
         for (int a = 0; a < EM_TILE; ++a)
@@ -1576,7 +1176,7 @@ static int em_gram_rr(LsmHandle* h, ElasticObject& eo, ModesObject& o, int na, i
                 GM[(size_t)i * q + j] = o.h_out.p[t * 32 + 16 + a * EM_TILE + b];
             }
     double theta[EM_MAXM];
-    rr = eo.h_st.p->status != ES_RUN ? 1 : em_rayleigh_ritz(q, m, GA, GM, C, theta, dropped);
+    rr = eo.h_st.p->status != MG_RUN ? 1 : em_rayleigh_ritz(q, m, GA, GM, C, theta, dropped);
     if (rr) return LSM_OK;
     for (int k = 0; k < m; ++k) o.lam[k] = theta[k];
     // the rows in slot order: column c of S sits in slot (block, k)
@@ -1589,9 +1189,9 @@ static int em_gram_rr(LsmHandle* h, ElasticObject& eo, ModesObject& o, int na, i
         if (b > 0)
             for (int j = 0; j < na; ++j) hc[(3 * EM_MAXM + row) * EM_MAXM + j] = C[(size_t)c * m + act[j]];
     }
-    ES_HIP(h, hipMemcpyAsync(o.cdev, hc, 6 * EM_MAXM * EM_MAXM * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(em_update_kernel, dim3(es_blocks(o.nt), 2), dim3(ES_THREADS), 0, st, B, (const double*)o.cdev);
-    ES_HIP(h, hipGetLastError());
+    MG_HIP(h, hipMemcpyAsync(o.cdev, hc, 6 * EM_MAXM * EM_MAXM * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(em_update_kernel, dim3(mg_blocks(o.nt), 2), dim3(MG_THREADS), 0, st, B, (const double*)o.cdev);
+    MG_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1608,16 +1208,16 @@ int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max
     const int jac = eo.precond == LSM_PRECOND_JACOBI;
     (void)hipSetDevice(h->device);
     hipStream_t st = h->stream;
-    const unsigned nb = es_blocks(L.nn), nbt = es_blocks(o.nt);
+    const unsigned nb = mg_blocks(L.nn), nbt = mg_blocks(o.nt);
     double* const X = o.B.base;
     double* const W = X + (size_t)m * nt;
     double* const AX = X + (size_t)3 * m * nt;
     double* const AW = X + (size_t)4 * m * nt;
     o.solved = 0;
-    ES_HIP(h, hipMemsetAsync(eo.st, 0, sizeof(EsState), st));     // status ES_RUN: the V-cycle's kernels run
-    hipLaunchKernelGGL(em_init_kernel, dim3(es_blocks((long long)m * nt)), dim3(ES_THREADS), 0, st, L, N, (long long)m * nt, x0, X);
-    ES_LAUNCH(N, em_apply_kernel, dim3(nb, m), ES_THREADS, st, L, (const double*)X, AX);
-    ES_HIP(h, hipGetLastError());
+    MG_HIP(h, hipMemsetAsync(eo.st, 0, sizeof(MgState), st));     // status MG_RUN: the V-cycle's kernels run
+    hipLaunchKernelGGL(em_init_kernel, dim3(mg_blocks((long long)m * nt)), dim3(MG_THREADS), 0, st, L, N, (long long)m * nt, x0, X);
+    MG_LAUNCH(N, em_apply_kernel, dim3(nb, m), MG_THREADS, st, L, (const double*)X, AX);
+    MG_HIP(h, hipGetLastError());
     int dropped = 0, rr = 0, it = 0, na = 0, np = 0, act[EM_MAXM], why = 0;
     long long applies = 0;
     double rel[EM_MAXM];
@@ -1626,14 +1226,13 @@ int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max
     if (r0 != LSM_OK) return r0;
     if (rr == 2) return lsm_fail(h, LSM_ERR_INVALID, x0 ? "lsm_elastic_modes_solve: x0 must be finite" : "lsm_elastic_modes_solve: a non-finite Gram matrix at the start");
     if (rr) why = 2;
-    double* const saved_r = eo.V.r;
     while (!why) {
         EmLam lam;
         for (int k = 0; k < EM_MAXM; ++k) lam.v[k] = o.lam[k];
-        hipLaunchKernelGGL(em_resid_kernel, dim3(nbt), dim3(ES_THREADS), 0, st, o.B, L.nn, lam, (const double*)o.Mn, o.partial.p, o.tickets.p + 31, o.gout + EM_OUT_NORM);
-        ES_HIP(h, hipGetLastError());
-        ES_HIP(h, hipMemcpyAsync(o.h_out.p + EM_OUT_NORM, o.gout + EM_OUT_NORM, 2 * EM_MAXM * sizeof(double), hipMemcpyDeviceToHost, st));
-        ES_HIP(h, hipStreamSynchronize(st));
+        hipLaunchKernelGGL(em_resid_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, o.B, L.nn, lam, (const double*)o.Mn, o.partial.p, o.tickets.p + 31, o.gout + EM_OUT_NORM);
+        MG_HIP(h, hipGetLastError());
+        MG_HIP(h, hipMemcpyAsync(o.h_out.p + EM_OUT_NORM, o.gout + EM_OUT_NORM, 2 * EM_MAXM * sizeof(double), hipMemcpyDeviceToHost, st));
+        MG_HIP(h, hipStreamSynchronize(st));
         na = 0;
         for (int k = 0; k < m; ++k) {
             const double rn = std::sqrt(o.h_out.p[EM_OUT_NORM + 2 * k]), mn = std::sqrt(o.h_out.p[EM_OUT_NORM + 2 * k + 1]);
@@ -1645,24 +1244,22 @@ int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max
         for (int j = 0; j < na; ++j) {       // W_j = T(R_{act[j]}): ascending, and j ≤ act[j], so no residual is overwritten before its turn
             double* src = W + (size_t)act[j] * nt;
             double* dst = W + (size_t)j * nt;
-            if (jac) hipLaunchKernelGGL(em_precond_kernel, dim3(nbt), dim3(ES_THREADS), 0, st, L, nt, (const double*)src, L.D, dst);
+            if (jac) hipLaunchKernelGGL(em_precond_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, L, nt, (const double*)src, L.D, dst);
             else {
-                eo.V.r = src;
-                es_vcycle(eo, st);
-                eo.V.r = saved_r;
-                hipLaunchKernelGGL(em_precond_kernel, dim3(nbt), dim3(ES_THREADS), 0, st, L, nt, (const double*)eo.xb[0], (const double*)nullptr, dst);
+                mg_vcycle(eo, src, st);
+                hipLaunchKernelGGL(em_precond_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, L, nt, (const double*)eo.xb[0], (const double*)nullptr, dst);
             }
         }
         applies += na;
-        ES_LAUNCH(N, em_apply_kernel, dim3(nb, na), ES_THREADS, st, L, (const double*)W, AW);
-        ES_HIP(h, hipGetLastError());
+        MG_LAUNCH(N, em_apply_kernel, dim3(nb, na), MG_THREADS, st, L, (const double*)W, AW);
+        MG_HIP(h, hipGetLastError());
         const int r1 = em_gram_rr(h, eo, o, na, np, act, st, dropped, rr);
         if (r1 != LSM_OK) return r1;
         if (rr) { why = 2; break; }
         np = na;
         ++it;
     }
-    ES_HIP(h, hipStreamSynchronize(st));
+    MG_HIP(h, hipStreamSynchronize(st));
     for (int k = 0; k < m; ++k) {
         if (lambda) lambda[k] = o.lam[k];
         if (relres) relres[k] = rel[k];
@@ -1685,7 +1282,7 @@ int lsm_elastic_modes_vectors(LsmModes* md, double* x_out) {
     if (!md) return LSM_ERR_INVALID;
     LsmHandle* h = md->e->h;
     if (!x_out || !md->o->solved) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_vectors: null argument, or no solve has run");
-    ES_HIP(h, hipMemcpyAsync(x_out, md->o->B.base, (size_t)md->o->m * (size_t)md->o->nt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    MG_HIP(h, hipMemcpyAsync(x_out, md->o->B.base, (size_t)md->o->m * (size_t)md->o->nt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return LSM_OK;
 }
 
@@ -1704,8 +1301,8 @@ int lsm_elastic_modes_store(LsmModes* md, int k, void* u0, void* u1, void* u2) {
     if (!o.solved || k < 0 || k >= o.m) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_store: no such mode, or no solve has run");
     if (!es_fields(eo.N, u0, u1, u2, U)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_store: the N distinct fields of u must be given");
     const EsLevel& L = eo.lev[0];
-    ES_LAUNCH(eo.N, em_store_kernel, dim3(es_blocks(L.nn)), ES_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), U);
-    ES_HIP(h, hipGetLastError());
+    MG_LAUNCH(eo.N, em_store_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), U);
+    MG_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1716,9 +1313,9 @@ int lsm_elastic_modes_sensitivity(LsmModes* md, int k, void* g_out) {
     ModesObject& o = *md->o;
     if (!o.solved || k < 0 || k >= o.m || !g_out) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_sensitivity: no such mode, no solve has run, or a null field");
     const EsLevel& L = eo.lev[0];
-    ES_LAUNCH(eo.N, em_sens_kernel, dim3(es_blocks(L.nn)), ES_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), o.lam[k],
+    MG_LAUNCH(eo.N, em_sens_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), o.lam[k],
               (const double*)o.rho, g_out);
-    ES_HIP(h, hipGetLastError());
+    MG_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 

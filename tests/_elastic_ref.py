@@ -635,7 +635,7 @@ def edge_cases():
     # f and u0 as device fields
     out["64x48_devfield"] = dict(base["64x48_upper_patch"], f=rng.standard_normal((2,) + n), devfield=True)
     out["64x48_devfield"]["u0"] = free_guess(out["64x48_devfield"])
-    # launch shapes (the prototype problem): more than 256 workgroups per node and more than ES_MAXB per unknown
+    # launch shapes (the prototype problem): more than 256 workgroups per node and more than MG_MAXB per unknown
     for n in ((300, 230), (45, 41, 37), (600, 500)):
         t = [0.0] * len(n)
         t[1] = -1.0

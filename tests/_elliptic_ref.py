@@ -456,7 +456,7 @@ _EDGE_CASES = {}
 def edge_cases():
     """name → the dict of cases() with the optional keys u0 (the guess, n-shaped; the fixed nodes take g), level, max_iters,
     solve ("both" | "mg"), direct (False: no sparse direct solve — 3-D fill — and the restatement's distance to its own solve at
-    rtol/100 in its place), big (the two shapes beyond EL_MAXB workgroups: one mg solve, no comparison of u), devfield (c and f are
+    rtol/100 in its place), big (the two shapes beyond MG_MAXB workgroups: one mg solve, no comparison of u), devfield (c and f are
     given as device fields)"""
     if _EDGE_CASES:
         return _EDGE_CASES
@@ -496,7 +496,7 @@ def edge_cases():
     add("6x5_face", (6, 5), fixed=face_mask((6, 5), 0, 0))
     add("4x40_face", (4, 40), fixed=face_mask((4, 40), 1, 0))
     add("4x40_side", (4, 40), fixed=face_mask((4, 40), 0, 0))       # the first-iterate test's 4x40: the V-cycle is good enough on it
-    # launch shapes: more than 256 workgroups (the reduction's second pass strides), more than EL_MAXB (a second grid-stride trip)
+    # launch shapes: more than 256 workgroups (the reduction's second pass strides), more than MG_MAXB (a second grid-stride trip)
     add("300x230", (300, 230), fixed=face_mask((300, 230), 0, 0), max_iters=3000)
     add("45x41x37", (45, 41, 37), fixed=face_mask((45, 41, 37), 2, 0), direct=False)
     add("1000x530", (1000, 530), fixed=face_mask((1000, 530), 0, 0), big=True, solve="mg", direct=False)

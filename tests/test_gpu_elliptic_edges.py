@@ -97,7 +97,7 @@ def test_c_on_the_device_is_refused_for_a_negative_entry_and_for_a_nan():
             lsm.elliptic_solve(phi, cs["f"], c=_field(lsm, cs, c), dirichlet=(cs["fixed"], cs["g"]))
 
 
-# ---- D. beyond EL_MAXB workgroups: the second trip of the grid-stride loop, with a ragged tail
+# ---- D. beyond MG_MAXB workgroups: the second trip of the grid-stride loop, with a ragged tail
 @pytest.mark.parametrize("name", BIG)
 def test_beyond_the_grid_stride_threshold(name):
     lsm = _lsm()

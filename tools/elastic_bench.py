@@ -12,10 +12,9 @@ a zero guess; at 512² and 2048², 128³ and 256³.
                   applies reach since the other kernels take time too
   copy_tbs        tools/copy_bw's 8-bytes-per-lane copy of the same run (`--copy-tbs` to give it instead)
 Kernel shares: run `--no-write --only NAME --precond mg` under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR`, a run
-of its own, then `--stats DIR --only NAME` adds every es_* kernel's dispatches, total time and share to the file.
-What was tried: a library built with -DLSM_ES_PRELOAD=0 (make OBJDIR=… OUT=… EXTRA=…) and loaded with LSM_AMD_LIB loads each
-neighbour value where a cell uses it; `--no-write --only NAME --precond mg` with each library in turn is the comparison of
-DESIGN.md §7.18.  `--table` prints the restatement's iteration table (tests/_elastic_ref.py), no device needed."""
+of its own, then `--stats DIR --only NAME` adds every es_* and mg_* kernel's dispatches, total time and share to the file.
+Comparing two builds: a library built elsewhere (make OBJDIR=… OUT=…) is loaded with LSM_AMD_LIB; `--no-write --only NAME --precond mg`
+with each library in turn is how DESIGN.md §7.18 compared loading each neighbour value where a cell uses it (removed since).  `--table` prints the restatement's iteration table (tests/_elastic_ref.py), no device needed."""
 import argparse
 import csv
 import glob
@@ -126,7 +125,7 @@ def kernel_stats(dirname):
     f = glob.glob(dirname + "/**/*kernel_stats.csv", recursive=True)[0]
     out = {}
     for r in csv.DictReader(open(f)):
-        m = re.search(r"\bes_\w+_kernel(<[\d, ]+>)?", r["Name"].split("(")[0])
+        m = re.search(r"\b(es|mg)_\w+_kernel(<[\w:, ]+>)?", r["Name"].split("(")[0])
         if not m:
             continue
         e = out.setdefault(m.group(0), {"dispatches": 0, "total_ms": 0.0})

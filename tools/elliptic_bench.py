@@ -13,9 +13,9 @@ the face x = 0, rtol 1e-8, from a zero guess; at 512² and 2048², 128³ and 256
                   residual 33 and its restriction 8 + 8/2^N, prolong-and-correct 17 + 8/2^N; the coarser levels add the factor 1/(1 − 2^−N)
   regularize      regularize_ of a random field at α = 4h: ms_per_call, iterations
 Kernel shares: run `--no-write --only NAME --precond mg` under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR`, a run
-of its own, then `--stats DIR --only NAME` adds every el_* kernel's dispatches, total time and share to the file.
-What was tried: a library built with -DLSM_EL_SPLIT_RESTRICT=0 (make OBJDIR=… OUT=… EXTRA=…) and loaded with LSM_AMD_LIB runs the one-kernel
-residual-and-restrict; `--no-write --only NAME --precond mg` with each library in turn is the comparison of DESIGN.md §7.17.
+of its own, then `--stats DIR --only NAME` adds every el_* and mg_* kernel's dispatches, total time and share to the file.
+Comparing two builds: a library built elsewhere (make OBJDIR=… OUT=…) is loaded with LSM_AMD_LIB; `--no-write --only NAME --precond mg`
+with each library in turn is how DESIGN.md §7.17 compared the one-kernel residual-and-restrict (removed since) with the two-pass form.
 --demo: a small 2-D thermal-compliance descent (NormalMotionTerm whose update_func solves the state equation and sets the normal
 speed to e − ℓ, the descent direction of compliance + ℓ·volume for ϕ_t + v|∇ϕ| = 0; reinitialize_ every few steps); records the
 objective per outer step into the same file."""
@@ -172,7 +172,7 @@ def kernel_stats(dirname):
     f = glob.glob(dirname + "/**/*kernel_stats.csv", recursive=True)[0]
     out = {}
     for r in csv.DictReader(open(f)):
-        m = re.search(r"\bel_\w+_kernel", r["Name"].split("(")[0])
+        m = re.search(r"\b(el_\w+_kernel|mg_\w+_kernel(<[\w:, ]+>)?)", r["Name"].split("(")[0])
         if not m:
             continue
         e = out.setdefault(m.group(0), {"dispatches": 0, "total_ms": 0.0})

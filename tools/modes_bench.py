@@ -83,7 +83,7 @@ def kernel_stats(dirname):
     f = glob.glob(dirname + "/**/*kernel_stats.csv", recursive=True)[0]
     out = {}
     for r in csv.DictReader(open(f)):
-        k = re.search(r"\be[sm]_\w+_kernel(<[\d, ]+>)?", r["Name"].split("(")[0])
+        k = re.search(r"\b(es|em|mg)_\w+_kernel(<[\w:, ]+>)?", r["Name"].split("(")[0])
         if not k:
             continue
         e = out.setdefault(k.group(0), {"dispatches": 0, "total_ms": 0.0})
