@@ -683,6 +683,59 @@ int lsm_elastic_modes_store(LsmModes* md, int k, void* u0, void* u1, void* u2);
 int lsm_elastic_modes_sensitivity(LsmModes* md, int k, void* g_out);
 void lsm_elastic_modes_destroy(LsmModes* md);
 
+/* ---- stress recovery: the cell-mean strain and stress of a displacement u on an LsmElastic, the von Mises field, the p-norm
+ *      aggregate of the von Mises stress with its adjoint load and its sensitivity to the cell moduli — the stress objective of a
+ *      structural shape optimisation (csrc/lsm_elastic.hip; tests/_stress_ref.py restates every operation).  u0,
+ *      u1 (, u2: NULL in 2-D) are N distinct dense fields of the handle; any displacement, not only a solution.  No contraction;
+ *      every sum below starts from +0 and runs in the stated order.
+ *      Setting: a cell C has the corners b = 0 … 2^N−1, bit d of b set on the upper side along d; u_{b,i} the corner values, converted
+ *      to fp64 first on a float32 handle; c_j = (1/h_j)·2^−(N−1), computed on the host in fp64; lambda, mu the object's material at
+ *      E = 1 (plane-dependent); E_C the cell modulus.
+ *      Cell-mean gradient: d_ij = sum_b (bit j of b set ? u_{b,i} : −u_{b,i}), b ascending; G_ij = d_ij·c_j — the gradient at the
+ *      centroid, the superconvergent point of Q1.
+ *      Voigt order: 2-D (00, 11, 01); 3-D (00, 11, 22, 12, 02, 01); M = N(N+1)/2 components.
+ *      Strain: e_ii = G_ii; e_ij = G_ij + G_ji for i < j (engineering shear).  tr = G_00 + G_11 (+ G_22), left to right.
+ *      Unit stress: shat_ii = lambda·tr + (2·mu)·G_ii; tauhat_ij = mu·e_ij; in 2-D the out-of-plane normal stress shat_zz = lambda·tr
+ *      for LSM_PLANE_STRAIN and 0 for LSM_PLANE_STRESS.  The stress is E_C·shat, E_C·tauhat: the ersatz modulus relaxes it in the void.
+ *      Von Mises: with (a, b, c) = (shat_00, shat_11, shat_22 or shat_zz), v2 = 0.5·(((a−b)² + (b−c)²) + (c−a)²) + 3·(sum of tauhat²,
+ *      Voigt order); t_C = sqrt(v2); s_C = E_C·t_C.
+ *      Node fields: the value at node I is (sum of the cell values over the existing cells around I, ascending m as in
+ *      lsm_elastic_energy)/(their number), rounded once to the storage type; ghosts untouched.
+ *      Aggregate, for 2 <= p <= 64 and sref > 0: r_C = s_C/sref, J' = sum_C pow(r_C, p), each thread over its cells ascending (cell =
+ *      thread + k·threads), then the ordered workgroup reduction of the solver; smax = max_C s_C in the same pass.  The p-norm is
+ *      G_p = sref·(prod h·J')^(1/p), left to the caller.
+ *      Adjoint load g = dJ'/du, gathered without atomics: g_{I,i} = sum over the existing cells C around I, ascending, of
+ *      w_C·(sum_j ±(c_j·Z_ij(C)), j ascending), + where I is on C's upper side along j.  w_C = (p·((E_C/sref)·(E_C/sref)))·pow(r_C, p−2),
+ *      which has no singularity where the strain vanishes (hence p >= 2).  m_k = shat_k − 0.5·(shat_l + shat_n) over the three normal
+ *      stresses (l < n the other two; the third is shat_zz in 2-D); Z_ii = lambda·(sum of m_k over the normal stresses that depend on
+ *      the strain: (m_0 + m_1) + m_2 in 3-D and for plane strain, m_0 + m_1 for plane stress) + (2·mu)·m_i; Z_ij = Z_ji = (3·mu)·tauhat_ij.
+ *      What is written is f = g/m_I with lsm_elliptic's node mass, a power of two: lsm_elastic_solve takes it unchanged, b = m·f = g.
+ *      Sensitivity: with the solution a of A a = g on the free components, zero on the fixed ones, given as N fields l0, l1 (, l2),
+ *      d_I = (scale·(sum over the existing cells around I, ascending, of p·pow(r_C, p) − E_C·(sum_r a_r·(sum_s K0[r,s]·u_s))))/(their
+ *      number), the bilinear form in lsm_elastic_energy's order, rounded once.  Cell by cell the summand is E_C·dJ'/dE_C, exact for
+ *      the discrete problem, prescribed non-zero displacements included; with scale = G_p/(p·J') it is E_C·dG_p/dE_C, the convention
+ *      of lsm_elastic_energy: positive where more material raises G_p.  With zero prescribed values sum_I count_I·d_I = 0.
+ *      lsm_elastic_stress_cells: component-major fp64 cell arrays on the device (n−1 per axis, axis 0 fastest): the M components for
+ *      LSM_STRESS_STRAIN and LSM_STRESS_STRESS, s_C for LSM_STRESS_VON_MISES.  lsm_elastic_stress: the node fields into distinct
+ *      dense fields of the handle, o0 … o(M−1) (NULL past the last; LSM_STRESS_VON_MISES writes o0 only).  lsm_elastic_stress_norm:
+ *      out := {J', smax}, synchronous; a NaN stress makes both NaN.  lsm_elastic_stress_load: f, N·nn fp64 on the device,
+ *      component-major.  lsm_elastic_stress_sensitivity: d into the dense field g_out.
+ *      LSM_ERR_INVALID without running anything: an unknown `what`, p outside [2, 64], sref not positive and finite, scale not finite,
+ *      a missing or repeated field, an output that is one of the inputs.  A non-finite u propagates, as in lsm_elastic_energy.
+ *      The calls use the object's scratch vectors (but lsm_elastic_stress_cells, which writes the caller's array only): none must run
+ *      concurrently with a solve of the object or of its modes, and the results of a later lsm_elastic_solve or
+ *      lsm_elastic_modes_solve are unaffected by them. */
+#define LSM_STRESS_STRAIN 0
+#define LSM_STRESS_STRESS 1
+#define LSM_STRESS_VON_MISES 2
+int lsm_elastic_stress_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, int what, double* out);
+int lsm_elastic_stress(LsmElastic* s, const void* u0, const void* u1, const void* u2, int what, void* o0, void* o1, void* o2, void* o3, void* o4,
+                       void* o5);
+int lsm_elastic_stress_norm(LsmElastic* s, const void* u0, const void* u1, const void* u2, double p, double sref, double out[2]);
+int lsm_elastic_stress_load(LsmElastic* s, const void* u0, const void* u1, const void* u2, double p, double sref, double* f_out);
+int lsm_elastic_stress_sensitivity(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* l0, const void* l1, const void* l2,
+                                   double p, double sref, double scale, void* g_out);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

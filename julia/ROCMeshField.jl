@@ -702,6 +702,53 @@ modes_sensitivity!(g::ROCMeshField, M, k) =
 
 destroy_modes(M) = ccall((:lsm_elastic_modes_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), M.md)
 
+# Stress recovery of a displacement u (N fields; any displacement, not only a solution) on an elasticity_operator K (include/lsm.h,
+# lsm_elastic_stress_*).  `what`: 0 the strain, 1 the stress (both N(N+1)/2 components in Voigt order: 2-D (00, 11, 01), 3-D (00, 11,
+# 22, 12, 02, 01)), 2 the von Mises stress (one component).
+const LSM_STRESS_STRAIN, LSM_STRESS_STRESS, LSM_STRESS_VON_MISES = 0, 1, 2
+
+# the cell arrays, component-major, into a ROCArray{Float64} of M·prod(n .- 1) values (or prod(n .- 1) for the von Mises stress)
+function stress_cells!(a, K, u, what)
+    p = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_stress_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}),
+        K.op, p[1], p[2], p[3], what, pointer(a)), "lsm_elastic_stress_cells")
+end
+
+# the node fields (the mean over the cells around a node) into the tuple `out` of M distinct fields (one for the von Mises stress)
+function stress_fields!(out, K, u, what)
+    p = _u3(u)
+    o = ntuple(k -> k <= length(out) ? pointer(out[k].buf) : C_NULL, 6)
+    _check(K.h.ptr, ccall((:lsm_elastic_stress, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        K.op, p[1], p[2], p[3], what, o[1], o[2], o[3], o[4], o[5], o[6]), "lsm_elastic_stress")
+end
+
+# (J′, smax): J′ = Σ_C (s_C/sref)^p for 2 ≤ p ≤ 64, reduced on the device, and the largest cell stress.  The p-norm is
+# G_p = sref·(prod(h)·J′)^(1/p).
+function stress_norm(K, u, p, sref)
+    out = zeros(Float64, 2)
+    q = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_stress_norm, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}),
+        K.op, q[1], q[2], q[3], p, sref, out), "lsm_elastic_stress_norm")
+    return (; J = out[1], smax = out[2])
+end
+
+# the adjoint load ∂J′/∂u as elasticity_solve!'s f (a ROCArray{Float64} of N·nn values): solve with zero values on the fixed components
+function stress_load!(f, K, u, p, sref)
+    q = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_stress_load, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}),
+        K.op, q[1], q[2], q[3], p, sref, pointer(f)), "lsm_elastic_stress_load")
+end
+
+# the sensitivity into the field g from the state u and the adjoint λ (N fields each): with scale = G_p/(p·J′) it is E_C·∂G_p/∂E_C
+# averaged over the cells around a node, the convention of elasticity_energy!
+function stress_sensitivity!(g::ROCMeshField, K, u, λ, p, sref, scale)
+    q, l = _u3(u), _u3(λ)
+    _check(K.h.ptr, ccall((:lsm_elastic_stress_sensitivity, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Cvoid}),
+        K.op, q[1], q[2], q[3], l[1], l[2], l[3], p, sref, scale, pointer(g.buf)), "lsm_elastic_stress_sensitivity")
+end
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

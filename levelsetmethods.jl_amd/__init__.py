@@ -18,7 +18,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
                   components, remove_components_, prune_, Components,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
-                  elasticity_solve, ElasticityOperator, ElasticitySolution, elasticity_modes, ElasticityModes)
+                  elasticity_solve, ElasticityOperator, ElasticitySolution, elasticity_modes, ElasticityModes, StressSensitivity)
 
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
@@ -33,5 +33,5 @@ __all__ = [
     "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
     "components", "remove_components_", "prune_", "Components",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
-    "elasticity_solve", "ElasticityOperator", "ElasticitySolution", "elasticity_modes", "ElasticityModes",
+    "elasticity_solve", "ElasticityOperator", "ElasticitySolution", "elasticity_modes", "ElasticityModes", "StressSensitivity",
 ]

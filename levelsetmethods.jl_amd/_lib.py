@@ -30,6 +30,7 @@ COMM_ID_BYTES = 128
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 PRECOND_MG, PRECOND_JACOBI = 0, 1
 PLANE_STRESS, PLANE_STRAIN = 0, 1
+STRESS_STRAIN, STRESS_STRESS, STRESS_VON_MISES = 0, 1, 2
 
 
 class LsmGrid(C.Structure):
@@ -178,6 +179,13 @@ _SIGS = [
     ("lsm_elastic_modes_store", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_elastic_modes_sensitivity", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     ("lsm_elastic_modes_destroy", None, [C.c_void_p]),
+    ("lsm_elastic_stress_cells", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_elastic_stress", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    ("lsm_elastic_stress_norm", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    ("lsm_elastic_stress_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
+    ("lsm_elastic_stress_sensitivity", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                                 C.c_double, C.c_void_p]),
     ("lsm_extend_along_normals", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_double, C.c_double, C.c_double]),
     ("lsm_band_tile_count", C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),

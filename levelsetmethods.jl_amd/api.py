@@ -2776,7 +2776,9 @@ class ElasticitySolution:
     """elasticity_solve's result: `u` (a tuple of N ROCMeshFields on ϕ's backend), `iterations`, `relres` (the recursive
     ‖r‖₂/‖b_free‖₂), `levels` of the hierarchy; energy_density(): the ROCMeshField of e_I = the mean over the cells around I of
     E_C·(C₀ε:ε averaged over the cell) — the integrand of the compliance shape derivative, the normal speed of a compliance
-    descent (coeff.set_values takes it device to device); compliance() = ∏h·Σ b·u, reduced on the device."""
+    descent (coeff.set_values takes it device to device); compliance() = ∏h·Σ b·u, reduced on the device.  Stress recovery
+    (DESIGN.md §7.20): strain(), stress() (tuples of ROCMeshFields in Voigt order), von_mises(), stress_max(), stress_norm(p, sref),
+    stress_sensitivity(p, sref, rtol, max_iters) → StressSensitivity."""
 
     def __init__(self, op, u, f, iterations, relres):
         self.operator, self.u, self._f, self.iterations, self.relres, self.levels = op, tuple(u), f, int(iterations), float(relres), op.levels
@@ -2789,15 +2791,110 @@ class ElasticitySolution:
 
     def compliance(self):
         op = self.operator
+        if self._f is None:
+            raise ValueError("elasticity_solve: this displacement came without a load (with_displacement): it has no compliance")
         return op.backend.elastic_compliance(op._handle(), self._f, [c.buf for c in self.u])
+
+    # ---- stress recovery: cell-mean values at the centroids, node fields their means over the cells around a node
+    def _stress_fields(self, what, count):
+        op = self.operator
+        h = op._handle()
+        out = tuple(ROCMeshField(op.backend, self.u[0].mesh, self.u[0].bcs) for _ in range(count))
+        op.backend.elastic_stress(h, [c.buf for c in self.u], what, [c.buf for c in out])
+        return out
+
+    def strain(self):
+        """the strain as N(N+1)/2 ROCMeshFields in Voigt order — 2-D (00, 11, 01), 3-D (00, 11, 22, 12, 02, 01) — with engineering shears"""
+        N = self.operator.ndim
+        return self._stress_fields(L.STRESS_STRAIN, N * (N + 1) // 2)
+
+    def stress(self):
+        """the stress E_C·C₀:ε as N(N+1)/2 ROCMeshFields in Voigt order; the ersatz modulus relaxes it in the void"""
+        N = self.operator.ndim
+        return self._stress_fields(L.STRESS_STRESS, N * (N + 1) // 2)
+
+    def von_mises(self):
+        """the von Mises stress (with the out-of-plane normal stress in plane strain) as one ROCMeshField"""
+        return self._stress_fields(L.STRESS_VON_MISES, 1)[0]
+
+    def stress_max(self):
+        """the largest von Mises stress of a cell"""
+        op = self.operator
+        h = op._handle()
+        return op.backend.elastic_stress_norm(h, [c.buf for c in self.u], 2.0, 1.0)[1]
+
+    def _stress_norm(self, p, sref):
+        """(G_p, J′, sref) after the refusals; a zero state gives (0, 0, sref) and no aggregate is formed"""
+        op = self.operator
+        p, sref = _stress_args(p, sref)
+        h = op._handle()
+        if sref is None:
+            sref = self.stress_max()
+            if sref == 0.0:
+                return 0.0, 0.0, sref
+            if not math.isfinite(sref):
+                raise ValueError("stress_norm: the displacement must be finite")
+        J, _ = op.backend.elastic_stress_norm(h, [c.buf for c in self.u], p, sref)
+        vol = float(np.prod(self.u[0].mesh.meshsize()))
+        return sref * (vol * J) ** (1.0 / p), J, sref
+
+    def stress_norm(self, p=8.0, sref=None):
+        """the p-norm of the von Mises stress, G_p = sref·(∏h·Σ_C (s_C/sref)^p)^(1/p), 2 ≤ p ≤ 64, reduced on the device; sref (the
+        largest cell stress without one) only scales the powers"""
+        return self._stress_norm(p, sref)[0]
+
+    def stress_sensitivity(self, p=8.0, sref=None, rtol=1e-8, max_iters=500):
+        """G_p and its sensitivity: one adjoint solve A λ = ∂J′/∂u with the same operator and zero values on the fixed components, then
+        the node field E_C·∂G_p/∂E_C averaged over the cells around a node — energy_density()'s convention, positive where more
+        material raises G_p; a NormalMotionTerm speed through coeff.set_values.  Returns a StressSensitivity."""
+        op = self.operator
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("stress_sensitivity: rtol must be positive and finite, max_iters at least 1")
+        value, J, sref_used = self._stress_norm(p, sref)
+        b = op.backend
+        h = op._handle()
+        p = float(p)
+        field = ROCMeshField(b, self.u[0].mesh, self.u[0].bcs)
+        if J == 0.0:      # no stress anywhere: nothing to differentiate
+            return StressSensitivity(0.0, field, None, 0, p, sref_used)
+        if not math.isfinite(J):
+            raise ValueError("stress_sensitivity: the aggregate is not finite (a non-finite displacement, or sref too small for p)")
+        ubufs = [c.buf for c in self.u]
+        load = b.elastic_stress_load(h, ubufs, p, sref_used)
+        lam = op._fields(None, fixed="zero")
+        it, rel = b.elastic_solve(h, load, [c.buf for c in lam], rtol, int(max_iters))
+        adjoint = ElasticitySolution(op, lam, load, it, rel)
+        b.elastic_stress_sensitivity(h, ubufs, [c.buf for c in lam], p, sref_used, value / (p * J), field.buf)
+        return StressSensitivity(value, field, adjoint, it, p, sref_used)
+
+
+def _stress_args(p, sref):
+    """the refusals of the stress aggregate that need no device"""
+    p = float(p)
+    if not (math.isfinite(p) and 2.0 <= p <= 64.0):
+        raise ValueError(f"stress_norm: p must be finite with 2 <= p <= 64, not {p}")
+    if sref is not None:
+        sref = float(sref)
+        if not _finite_positive(sref):
+            raise ValueError("stress_norm: sref must be finite and positive")
+    return p, sref
+
+
+class StressSensitivity:
+    """stress_sensitivity's result: `value` (G_p), `field` (the ROCMeshField of E_C·∂G_p/∂E_C averaged over the cells around a node),
+    `adjoint` (the ElasticitySolution of the adjoint solve; None for a zero state), `iterations` of that solve, `p`, `sref`."""
+
+    def __init__(self, value, field, adjoint, iterations, p, sref):
+        self.value, self.field, self.adjoint, self.iterations, self.p, self.sref = float(value), field, adjoint, int(iterations), float(p), float(sref)
 
 
 class ElasticityOperator:
     """The discrete Q1 elasticity operator of ϕ's grid and its multigrid hierarchy, kept on the device for repeated solves with
     new loads and guesses: solve(f, u0=None, rtol=1e-8, max_iters=500) → ElasticitySolution.  The arguments are
     elasticity_solve's.  ϕ is read once, here: after ϕ has moved, build a new operator.  `levels`, `free_dofs`, `fixed_dofs`;
-    apply(x), cells(), stiffness(level) show the operator; modes(m, …) → ElasticityModes, its lowest vibration modes; close() releases
-    the device memory."""
+    apply(x), cells(), stiffness(level) show the operator; modes(m, …) → ElasticityModes, its lowest vibration modes;
+    with_displacement(u) → an ElasticitySolution around a given u, for the stress recovery; close() releases the device memory."""
 
     def __init__(self, phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", dirichlet=None, level=0.0, precond="mg"):
         what = "elasticity_solve"
@@ -2872,25 +2969,37 @@ class ElasticityOperator:
             raise ValueError("the ElasticityOperator is closed")
         return self._h
 
-    def _fields(self, u0):
-        """N new fields holding the guess (zero without one) and the prescribed values"""
+    def _fields(self, u0, fixed="prescribed", what="elasticity_solve: u0"):
+        """N new fields holding the guess (zero without one) and, on the fixed components, the prescribed values
+        (fixed="prescribed"), zero ("zero": an adjoint solve) or the guess's own values ("keep": with_displacement)"""
         b, N = self.backend, self.ndim
         n = tuple(int(m) for m in self.mesh.n)
         if u0 is not None and not (isinstance(u0, (tuple, list)) and all(isinstance(c, ROCMeshField) for c in u0)):
-            u0 = list(_component_values(u0, N, n, "elasticity_solve: u0"))
+            u0 = list(_component_values(u0, N, n, what))
         if u0 is not None and len(u0) != N:
-            raise ValueError(f"elasticity_solve: u0 has {len(u0)} components, the grid has {N} dimensions")
+            raise ValueError(f"{what} has {len(u0)} components, the grid has {N} dimensions")
         out = []
         for i in range(N):
             u = ROCMeshField(b, self.mesh, self.bcs)
             if u0 is not None:
                 if isinstance(u0[i], ROCMeshField) and u0[i].backend is not b:
-                    raise ValueError("elasticity_solve: u0 belongs to another field's backend")
+                    raise ValueError(f"{what} belongs to another field's backend")
                 u.copy_(u0[i])
-            iv = b.interior(u.buf)
-            iv.copy_(b.torch.where(self._mask[i], self._values[i].to(iv.dtype), iv))
+            if fixed != "keep":
+                iv = b.interior(u.buf)
+                vals = self._values[i].to(iv.dtype) if fixed == "prescribed" else b.torch.zeros_like(iv)
+                iv.copy_(b.torch.where(self._mask[i], vals, iv))
             out.append(u)
         return out
+
+    def with_displacement(self, u):
+        """An ElasticitySolution around displacements from elsewhere, without a solve: the entry to strain(), stress(), von_mises(),
+        stress_norm() and stress_sensitivity() for a given u — N host arrays, an array of shape (N,)+n, or N ROCMeshFields (copied).
+        It has no load, so compliance() raises."""
+        self._handle()
+        if u is None:
+            raise ValueError("with_displacement: u must be given")
+        return ElasticitySolution(self, self._fields(u, fixed="keep", what="with_displacement: u"), None, 0, 0.0)
 
     def _load(self, f):
         """f as one flat float64 device array, component-major"""

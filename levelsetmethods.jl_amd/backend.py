@@ -525,6 +525,34 @@ class HipBackend:
     def elastic_destroy(self, obj):
         self.lib.lsm_elastic_destroy(obj)
 
+    # ---- stress recovery (lsm_elastic_stress_*): `what` is L.STRESS_STRAIN, L.STRESS_STRESS or L.STRESS_VON_MISES
+    def elastic_stress_cells(self, obj, u, what):
+        """the component-major fp64 cell arrays as one flat device tensor"""
+        N = self.ndim
+        ncomp = 1 if what == L.STRESS_VON_MISES else N * (N + 1) // 2
+        out = self.torch.empty(ncomp * int(np.prod([m - 1 for m in self.local_shape()])), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_stress_cells(obj, *self._u3(u), int(what), self.ptr(out)), "lsm_elastic_stress_cells")
+        return out
+
+    def elastic_stress(self, obj, u, what, outs):
+        o = [self.ptr(t) for t in outs] + [None] * (6 - len(outs))
+        L.check(self.h, self.lib.lsm_elastic_stress(obj, *self._u3(u), int(what), *o), "lsm_elastic_stress")
+
+    def elastic_stress_norm(self, obj, u, p, sref):
+        """(J′, smax)"""
+        out = (C.c_double * 2)()
+        L.check(self.h, self.lib.lsm_elastic_stress_norm(obj, *self._u3(u), float(p), float(sref), out), "lsm_elastic_stress_norm")
+        return out[0], out[1]
+
+    def elastic_stress_load(self, obj, u, p, sref):
+        out = self.torch.empty(self.ndim * int(np.prod(self.local_shape())), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_stress_load(obj, *self._u3(u), float(p), float(sref), self.ptr(out)), "lsm_elastic_stress_load")
+        return out
+
+    def elastic_stress_sensitivity(self, obj, u, adj, p, sref, scale, g):
+        L.check(self.h, self.lib.lsm_elastic_stress_sensitivity(obj, *self._u3(u), *self._u3(adj), float(p), float(sref), float(scale), self.ptr(g)),
+                "lsm_elastic_stress_sensitivity")
+
     # ---- vibration modes (lsm_elastic_modes_*): the modes object borrows the elastic object
     def modes_create(self, obj, phi, level, rho_in, rho_out, rho_cells, m):
         out = C.c_void_p()

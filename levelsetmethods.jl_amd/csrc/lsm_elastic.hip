@@ -390,6 +390,8 @@ void EsLevel::launch_resid(int N, unsigned nb, hipStream_t s, const EsLevel& L, 
 }
 struct ElasticObject : MgSolver<EsLevel> {
     std::vector<std::vector<double>> k0; // the levels' K0 as computed (what the device holds)
+    double lam = 0.0, mu = 0.0;          // the material at E = 1 (plane-dependent), for the stress recovery
+    int plane = 0;
 };
 
 // the unit element matrix of a box cell with sides h, scaled by 1/∏h (include/lsm.h states the formula): a product over the axes
@@ -578,6 +580,7 @@ int lsm_elastic_create(LsmHandle* h, const void* phi, double level, double e_in,
     (void)hipSetDevice(h->device);
     ElasticObject* o = new ElasticObject();
     o->precond = precond;
+    o->lam = lam; o->mu = mu; o->plane = plane;
     const int r = es_create(h, *o, phi, level, e_in, e_out, e_cells, lam, mu, (const unsigned char*)fixed, stats);
     if (r != LSM_OK) { delete o; return r; }
     *out = new LsmElastic{h, o};
@@ -1323,4 +1326,380 @@ void lsm_elastic_modes_destroy(LsmModes* md) {
     if (!md) return;
     delete md->o;
     delete md;
+}
+
+// ======================================================================================================================================
+// Stress recovery: the cell-mean strain and stress of a displacement, the von Mises field, the p-norm aggregate J′ = Σ_C (s_C/sref)^p
+// with its adjoint load ∂J′/∂u and the cell sensitivity E_C·∂J′/∂E_C.  include/lsm.h ("stress recovery") is the normative text,
+// tests/_stress_ref.py restates it, DESIGN.md §7.20 has the kernels' compiler report.
+//
+// Every quantity is a function of a cell's 2^N·N corner displacements, so every pass is one thread per cell (x-contiguous, each u
+// value loaded by the 2^N cells that share it, from the cache) that leaves what the nodes need in the object's scratch vectors —
+// xa, xb, x, r, q, p of level 0 are one run of 6·N·nn doubles, which a solve overwrites before it reads — and then one thread per
+// node that gathers from the ≤ 2^N cells around it, ascending, without atomics.  Recomputing the cells per node, as es_energy_kernel
+// does, would load and compute 2^N times as much.  One pow per cell and pass.
+namespace lsm {
+
+struct SsMat { double lam, mu, c[3]; int strain; };     // c_j = (1/h_j)·2^−(N−1); strain: 2-D plane strain (ŝ_zz = λ·tr, else 0)
+struct SsOut { void* p[6]; };
+
+template <int N>
+__device__ __forceinline__ void ss_cell_coords(const int n[3], int ci, int C[3]) {
+    C[0] = ci % (n[0] - 1);
+    const int r = ci / (n[0] - 1);
+    C[1] = N > 2 ? r % (n[1] - 1) : r;
+    C[2] = N > 2 ? r / (n[1] - 1) : 0;
+}
+// the cell's corner values of the N fields, uc[b·N + i], as fp64
+template <int N>
+__device__ __forceinline__ void ss_corners(const MgField& F, const EsU& U, const int C[3], double uc[(1 << N) * N]) {
+    const long long c0 = mg_padded(F, C);
+#pragma unroll
+    for (int b = 0; b < (1 << N); ++b) {
+        const long long o = (b & 1) + ((b >> 1) & 1) * F.s1 + (N > 2 ? ((b >> 2) & 1) * F.s2 : 0);
+#pragma unroll
+        for (int i = 0; i < N; ++i) uc[b * N + i] = ld_val(U.p[i], c0 + o, F.f32);
+    }
+}
+// shear component k of the Voigt order is the pair (i, j), i < j: 2-D (0,1); 3-D (1,2), (0,2), (0,1)
+template <int N>
+__device__ __forceinline__ constexpr int ss_pi(int k) { return N == 2 ? 0 : k == 0 ? 1 : 0; }
+template <int N>
+__device__ __forceinline__ constexpr int ss_pj(int k) { return N == 2 ? 1 : k == 2 ? 1 : 2; }
+
+// the cell-mean gradient G_ij = d_ij·c_j, the strain e (Voigt), the unit normal stresses sn (the third is ŝ_zz in 2-D) and shears tau
+template <int N>
+__device__ __forceinline__ void ss_unit(const double uc[(1 << N) * N], const SsMat& P, double e[N * (N + 1) / 2], double sn[3], double tau[N == 2 ? 1 : 3]) {
+    double G[N][N];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            double d = 0.0;
+#pragma unroll
+            for (int b = 0; b < (1 << N); ++b) d = d + (((b >> j) & 1) ? uc[b * N + i] : -uc[b * N + i]);
+            G[i][j] = d * P.c[j];
+        }
+    double tr = G[0][0] + G[1][1];
+    if (N > 2) tr = tr + G[N - 1][N - 1];
+    const double lt = P.lam * tr, mu2 = 2.0 * P.mu;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        e[i] = G[i][i];
+        sn[i] = lt + mu2 * G[i][i];
+    }
+    if (N == 2) sn[2] = P.strain ? lt : 0.0;
+#pragma unroll
+    for (int k = 0; k < (N == 2 ? 1 : 3); ++k) {
+        e[N + k] = G[ss_pi<N>(k)][ss_pj<N>(k)] + G[ss_pj<N>(k)][ss_pi<N>(k)];
+        tau[k] = P.mu * e[N + k];
+    }
+}
+// v2 = 0.5·(((a−b)² + (b−c)²) + (c−a)²) + 3·Σ τ̂²
+template <int N>
+__device__ __forceinline__ double ss_v2(const double sn[3], const double tau[N == 2 ? 1 : 3]) {
+    const double ab = sn[0] - sn[1], bc = sn[1] - sn[2], ca = sn[2] - sn[0];
+    double q = 0.0;
+#pragma unroll
+    for (int k = 0; k < (N == 2 ? 1 : 3); ++k) q = q + tau[k] * tau[k];
+    return 0.5 * ((ab * ab + bc * bc) + ca * ca) + 3.0 * q;
+}
+
+// ---- the cell arrays, component-major: the strain, the stress E_C·(ŝ, τ̂), or s_C = E_C·sqrt(v2)
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) ss_cells_kernel(EsLevel L, MgField F, EsU U, SsMat P, int what, int nc, double* __restrict__ out) {
+    constexpr int M = N * (N + 1) / 2;
+    MG_LOOP(ci, nc) {
+        int C[3];
+        ss_cell_coords<N>(L.n, ci, C);
+        double uc[(1 << N) * N], e[M], sn[3], tau[M - N];
+        ss_corners<N>(F, U, C, uc);
+        ss_unit<N>(uc, P, e, sn, tau);
+        if (what == LSM_STRESS_STRAIN) {
+#pragma unroll
+            for (int k = 0; k < M; ++k) out[(size_t)k * nc + ci] = e[k];
+        } else if (what == LSM_STRESS_STRESS) {
+            const double E = L.E[ci];
+#pragma unroll
+            for (int k = 0; k < N; ++k) out[(size_t)k * nc + ci] = E * sn[k];
+#pragma unroll
+            for (int k = 0; k < M - N; ++k) out[(size_t)(N + k) * nc + ci] = E * tau[k];
+        } else {
+            out[ci] = L.E[ci] * sqrt(ss_v2<N>(sn, tau));
+        }
+    }
+}
+
+// the existing cells around node I, ascending m: their indices and their number
+template <int N>
+__device__ __forceinline__ double ss_around(const EsLevel& L, const int I[3], int ci[1 << N], bool in[1 << N]) {
+    double cnt = 0.0;
+#pragma unroll
+    for (int m = 0; m < (1 << N); ++m) {
+        int C[3] = {0, 0, 0};
+        in[m] = true;
+#pragma unroll
+        for (int d = 0; d < N; ++d) {
+            C[d] = I[d] - 1 + ((m >> d) & 1);
+            in[m] = in[m] && C[d] >= 0 && C[d] < L.n[d] - 1;
+        }
+        ci[m] = in[m] ? mg_cell_index<N>(L.n, C) : 0;
+        if (in[m]) cnt = cnt + 1.0;
+    }
+    return cnt;
+}
+
+// ---- node fields from ncomp cell arrays: (scale·(Σ over the existing cells, ascending, from +0))/(their number), rounded once;
+// scale = 1 for the plain fields, which changes no bit
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) ss_gather_kernel(EsLevel L, MgField F, const double* __restrict__ cell, int nc, int ncomp, double scale, SsOut O) {
+    MG_LOOP(id, L.nn) {
+        int I[3], ci[1 << N];
+        bool in[1 << N];
+        mg_coords<N>(L.n, id, I);
+        const double cnt = ss_around<N>(L, I, ci, in);
+        const long long at = mg_padded(F, I);
+        for (int k = 0; k < ncomp; ++k) {
+            double acc = 0.0;
+#pragma unroll
+            for (int m = 0; m < (1 << N); ++m)
+                if (in[m]) acc = acc + cell[(size_t)k * nc + ci[m]];
+            st_val(O.p[k], at, F.f32, (scale * acc) / cnt);
+        }
+    }
+}
+
+// ---- J′ = Σ_C pow(s_C/sref, p) in workgroup order and smax = max_C s_C, in one pass: out[0], out[1].  The workgroup's maximum goes
+// into the second gridDim.x words of partial before block_reduce_ordered publishes the workgroup's sum, so the last workgroup finds
+// both behind its acquire.  The maximum drops NaN; a NaN s_C makes J′ NaN, and smax is then set to it.
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) ss_norm_kernel(EsLevel L, MgField F, EsU U, SsMat P, int nc, double p, double sref, double* partial,
+                                                             unsigned* ticket, double* __restrict__ out) {
+    constexpr int M = N * (N + 1) / 2;
+    __shared__ double wm[MG_THREADS / 64];
+    double red[1] = {0.0}, mx = 0.0;
+    MG_LOOP(ci, nc) {
+        int C[3];
+        ss_cell_coords<N>(L.n, ci, C);
+        double uc[(1 << N) * N], e[M], sn[3], tau[M - N];
+        ss_corners<N>(F, U, C, uc);
+        ss_unit<N>(uc, P, e, sn, tau);
+        const double s = L.E[ci] * sqrt(ss_v2<N>(sn, tau));
+        red[0] += pow(s / sref, p);
+        mx = s > mx ? s : mx;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    mx = wave_max(mx);
+    if (lane == 0) wm[wave] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[gridDim.x + blockIdx.x] = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
+    if (!block_reduce_ordered<1, MG_THREADS>(red, partial, ticket)) return;
+    mx = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
+        const double v = partial[gridDim.x + b];
+        mx = v > mx ? v : mx;
+    }
+    mx = wave_max(mx);
+    __syncthreads();
+    if (lane == 0) wm[wave] = mx;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    out[0] = red[0];
+    out[1] = red[0] != red[0] ? red[0] : fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
+}
+
+// ---- the adjoint load's cell pass: w_C = p·(E_C/sref)²·pow(r_C, p−2) and Z (Voigt: Z_ii, then the shears 3μ·τ̂) into 1 + M cell arrays
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) ss_loadcell_kernel(EsLevel L, MgField F, EsU U, SsMat P, int nc, double p, double sref, double* __restrict__ cell) {
+    constexpr int M = N * (N + 1) / 2;
+    MG_LOOP(ci, nc) {
+        int C[3];
+        ss_cell_coords<N>(L.n, ci, C);
+        double uc[(1 << N) * N], e[M], sn[3], tau[M - N];
+        ss_corners<N>(F, U, C, uc);
+        ss_unit<N>(uc, P, e, sn, tau);
+        const double E = L.E[ci];
+        const double r = (E * sqrt(ss_v2<N>(sn, tau))) / sref, es = E / sref;
+        cell[ci] = (p * (es * es)) * pow(r, p - 2.0);
+        const double m[3] = {sn[0] - 0.5 * (sn[1] + sn[2]), sn[1] - 0.5 * (sn[0] + sn[2]), sn[2] - 0.5 * (sn[0] + sn[1])};
+        double sm = m[0] + m[1];
+        if (N > 2 || P.strain) sm = sm + m[2];
+        const double ls = P.lam * sm, mu2 = 2.0 * P.mu, mu3 = 3.0 * P.mu;
+#pragma unroll
+        for (int i = 0; i < N; ++i) cell[(size_t)(1 + i) * nc + ci] = ls + mu2 * m[i];
+#pragma unroll
+        for (int k = 0; k < M - N; ++k) cell[(size_t)(1 + N + k) * nc + ci] = mu3 * tau[k];
+    }
+}
+// ---- f_{I,i} = g_{I,i}/m_I, g_{I,i} = Σ over the existing cells, ascending, from +0, of w_C·(Σ_j ±(c_j·Z_ij), j ascending from +0): + where I is
+// on the cell's upper side along j (bit j of m clear)
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) ss_loadnode_kernel(EsLevel L, SsMat P, const double* __restrict__ cell, int nc, double* __restrict__ f_out) {
+    constexpr int M = N * (N + 1) / 2;
+    MG_LOOP(id, L.nn) {
+        int I[3], ci[1 << N];
+        bool in[1 << N];
+        mg_coords<N>(L.n, id, I);
+        ss_around<N>(L, I, ci, in);
+        double g[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) g[i] = 0.0;
+#pragma unroll
+        for (int m = 0; m < (1 << N); ++m) {
+            if (!in[m]) continue;
+            const double w = cell[ci[m]];
+            double Z[N][N];
+#pragma unroll
+            for (int i = 0; i < N; ++i) Z[i][i] = cell[(size_t)(1 + i) * nc + ci[m]];
+#pragma unroll
+            for (int k = 0; k < M - N; ++k) Z[ss_pi<N>(k)][ss_pj<N>(k)] = Z[ss_pj<N>(k)][ss_pi<N>(k)] = cell[(size_t)(1 + N + k) * nc + ci[m]];
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                double inner = 0.0;
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    const double t = P.c[j] * Z[i][j];
+                    inner = inner + (((m >> j) & 1) ? -t : t);
+                }
+                g[i] = g[i] + w * inner;
+            }
+        }
+        const double mass = mg_mass<N>(L.n, I);
+#pragma unroll
+        for (int i = 0; i < N; ++i) f_out[(size_t)i * L.nn + id] = g[i] / mass;
+    }
+}
+
+// ---- the sensitivity's cell pass: p·pow(r_C, p) − E_C·(Σ_r λ_r·(Σ_s K0[r,s]·u_s)), the bilinear form in es_energy_kernel's order
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) ss_senscell_kernel(EsLevel L, MgField F, EsU U, EsU A, SsMat P, int nc, double p, double sref, double* __restrict__ cell) {
+    constexpr int NC = 1 << N, R = NC * N, M = N * (N + 1) / 2;
+    const double* __restrict__ K = L.K;
+    MG_LOOP(ci, nc) {
+        int C[3];
+        ss_cell_coords<N>(L.n, ci, C);
+        double uc[R], e[M], sn[3], tau[M - N];
+        ss_corners<N>(F, U, C, uc);
+        ss_unit<N>(uc, P, e, sn, tau);
+        const double E = L.E[ci];
+        const double r = (E * sqrt(ss_v2<N>(sn, tau))) / sref;
+        double ac[R];
+        ss_corners<N>(F, A, C, ac);
+        double q = 0.0;
+#pragma unroll
+        for (int a = 0; a < R; ++a) {
+            double t = 0.0;
+#pragma unroll
+            for (int s = 0; s < R; ++s) t = t + K[a * R + s] * uc[s];
+            q = q + ac[a] * t;
+        }
+        cell[ci] = p * pow(r, p) - E * q;
+    }
+}
+
+static SsMat ss_mat(const ElasticObject& o) {
+    SsMat P;
+    P.lam = o.lam; P.mu = o.mu;
+    P.strain = o.N == 2 && o.plane == LSM_PLANE_STRAIN;
+    for (int d = 0; d < 3; ++d) P.c[d] = d < o.N ? (1.0 / o.lev[0].h[d]) * (o.N == 2 ? 0.5 : 0.25) : 0.0;
+    return P;
+}
+static bool ss_power(double p, double sref) { return p >= 2.0 && p <= 64.0 && std::isfinite(sref) && sref > 0.0; }
+
+}  // namespace lsm
+
+int lsm_elastic_stress_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, int what, double* out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (what != LSM_STRESS_STRAIN && what != LSM_STRESS_STRESS && what != LSM_STRESS_VON_MISES)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_cells: unknown quantity (LSM_STRESS_STRAIN, LSM_STRESS_STRESS or LSM_STRESS_VON_MISES)");
+    if (!es_fields(o.N, u0, u1, u2, U) || !out || out == u0 || out == u1 || out == u2)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_cells: the N distinct fields of u and an array of its own must be given");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    MG_LAUNCH(o.N, ss_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, s->h->stream, L, o.F, U, ss_mat(o), what, nc, out);
+    MG_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_stress(LsmElastic* s, const void* u0, const void* u1, const void* u2, int what, void* o0, void* o1, void* o2, void* o3, void* o4, void* o5) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (what != LSM_STRESS_STRAIN && what != LSM_STRESS_STRESS && what != LSM_STRESS_VON_MISES)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress: unknown quantity (LSM_STRESS_STRAIN, LSM_STRESS_STRESS or LSM_STRESS_VON_MISES)");
+    const int ncomp = what == LSM_STRESS_VON_MISES ? 1 : o.N * (o.N + 1) / 2;
+    SsOut O = {{o0, o1, o2, o3, o4, o5}};
+    bool ok = es_fields(o.N, u0, u1, u2, U);
+    for (int k = 0; k < ncomp; ++k) {
+        ok = ok && O.p[k] && O.p[k] != u0 && O.p[k] != u1 && O.p[k] != u2;
+        for (int l = 0; l < k; ++l) ok = ok && O.p[k] != O.p[l];
+    }
+    if (!ok) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress: the components of u and the output fields must be distinct fields");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    hipStream_t st = s->h->stream;
+    double* cell = o.xa[0];      // ≤ 6·(cells) of the 6·N·nn scratch doubles
+    MG_LAUNCH(o.N, ss_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, ss_mat(o), what, nc, cell);
+    MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, ncomp, 1.0, O);
+    MG_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_stress_norm(LsmElastic* s, const void* u0, const void* u1, const void* u2, double p, double sref, double out[2]) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (!out || !es_fields(o.N, u0, u1, u2, U)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_norm: the N distinct fields of u and out must be given");
+    if (!ss_power(p, sref)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_norm: p must lie in [2, 64] and sref must be positive and finite");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    hipStream_t st = s->h->stream;
+    (void)hipSetDevice(s->h->device);
+    double* res = o.partial.p + 2 * MG_MAXB;      // the reduction uses 2·gridDim.x ≤ 2·MG_MAXB words of the 4·MG_MAXB
+    MG_LAUNCH(o.N, ss_norm_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, ss_mat(o), nc, p, sref, o.partial.p, &o.st.p->ticket[3], res);
+    MG_HIP(s->h, hipGetLastError());
+    MG_HIP(s->h, hipMemcpyAsync(out, res, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    MG_HIP(s->h, hipStreamSynchronize(st));
+    return LSM_OK;
+}
+
+int lsm_elastic_stress_load(LsmElastic* s, const void* u0, const void* u1, const void* u2, double p, double sref, double* f_out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (!f_out || !es_fields(o.N, u0, u1, u2, U) || f_out == u0 || f_out == u1 || f_out == u2)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_load: the N distinct fields of u and an array of its own must be given");
+    if (!ss_power(p, sref)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_load: p must lie in [2, 64] and sref must be positive and finite");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    hipStream_t st = s->h->stream;
+    const SsMat P = ss_mat(o);
+    double* cell = o.xa[0];      // 1 + N(N+1)/2 ≤ 7 cell arrays of the 6·N·nn scratch doubles
+    MG_LAUNCH(o.N, ss_loadcell_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, P, nc, p, sref, cell);
+    MG_LAUNCH(o.N, ss_loadnode_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, P, (const double*)cell, nc, f_out);
+    MG_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_stress_sensitivity(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* l0, const void* l1, const void* l2, double p,
+                                   double sref, double scale, void* g_out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U, A;
+    if (!es_fields(o.N, u0, u1, u2, U) || !es_fields(o.N, l0, l1, l2, A) || !g_out || g_out == u0 || g_out == u1 || g_out == u2 || g_out == l0 || g_out == l1 ||
+        g_out == l2)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_sensitivity: the components of u, those of the adjoint and g_out must be distinct fields");
+    if (!ss_power(p, sref) || !std::isfinite(scale))
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_stress_sensitivity: p must lie in [2, 64], sref must be positive and finite, scale finite");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    hipStream_t st = s->h->stream;
+    double* cell = o.xa[0];
+    SsOut O = {{g_out, nullptr, nullptr, nullptr, nullptr, nullptr}};
+    MG_LAUNCH(o.N, ss_senscell_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, A, ss_mat(o), nc, p, sref, cell);
+    MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, 1, scale, O);
+    MG_HIP(s->h, hipGetLastError());
+    return LSM_OK;
 }
