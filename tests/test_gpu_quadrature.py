@@ -1,5 +1,7 @@
 """quadrature on the device (csrc/lsm_quad.hip, lsm_quad_* through the Python API) against the restatement tests/_quad_ref.py
-node for node, and the reference's own tests (test/test-quadrature.jl)."""
+node for node, and the reference's own tests (test/test-quadrature.jl).  The launch shapes and edges these grids do not reach
+(several chunks, a second scan round, two cells per workgroup, the depth limit in 3-D, q = 20, bands in 3-D) are in
+tests/test_gpu_quadrature_edges.py."""
 import math
 import warnings
 
@@ -34,20 +36,46 @@ def _ref(vals, lc, hc, P, k):
     return ReinitRef(_dense_getter(vals, P), vals.shape, lc, hc, order=k, cells=[])
 
 
-def _compare(q, ref, qo, surface):
+def _lin(cells, n):
+    """ascending linear index (x fastest) of (m, N) cell indices on a grid of n nodes"""
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, len(n))
+    lin, s = np.zeros(len(cells), dtype=np.int64), 1
+    for d in range(len(n)):
+        lin += cells[:, d] * s
+        s *= n[d] - 1
+    return lin
+
+
+def _compare(q, ref, qo, surface, cells=None, restated=None):
+    """cells: compare only those cells' slices of the device output (what the restatement gives for them: nodes, a full cell,
+    or nothing); restated: Q.quadrature's result if the caller has it already"""
     import _quad_ref as Q
-    cut, full, nfb = Q.quadrature(ref, qo, surface)
-    cells = sorted(cut, key=lambda I: tuple(I[::-1]))
-    assert [tuple(int(v) for v in I) for I in q.cells] == cells
-    assert [tuple(int(v) for v in I) for I in q.full_cells] == full
-    assert q.nfallback == nfb
-    counts = [len(cut[I][1]) for I in cells]
-    assert list(np.diff(q.offsets)) == counts
+    cut, full, nfb = restated if restated is not None else Q.quadrature(ref, qo, surface, cells=cells)
+    if cells is None:
+        cells = sorted(cut, key=lambda I: tuple(I[::-1]))
+        assert [tuple(int(v) for v in I) for I in q.cells] == cells
+        assert [tuple(int(v) for v in I) for I in q.full_cells] == full
+        assert q.nfallback == nfb
+        counts = [len(cut[I][1]) for I in cells]
+        assert list(np.diff(q.offsets)) == counts
+        dX, dW = q.coords, q.weights
+    else:
+        asked = sorted({tuple(int(v) for v in I) for I in cells}, key=lambda I: tuple(I[::-1]))
+        dcut, dfull = _lin(q.cells, ref.n), _lin(q.full_cells, ref.n)
+        where = np.flatnonzero(np.isin(dcut, _lin(asked, ref.n)))
+        assert [asked[i] for i in np.flatnonzero(np.isin(_lin(asked, ref.n), dfull))] == full
+        cells = [I for I in asked if I in cut]
+        assert [tuple(int(v) for v in q.cells[i]) for i in where] == cells
+        assert [int(q.offsets[i + 1] - q.offsets[i]) for i in where] == [len(cut[I][1]) for I in cells]
+        sl = [np.arange(q.offsets[i], q.offsets[i + 1]) for i in where]
+        dX, dW = (q.coords[np.concatenate(sl)], q.weights[np.concatenate(sl)]) if sl else (q.coords[:0], q.weights[:0])
     if cells:
         X = np.concatenate([cut[I][0] for I in cells])
         W = np.concatenate([cut[I][1] for I in cells])
-        assert np.abs(q.coords - X).max() <= 1e-12
-        assert np.abs(q.weights - W).max() <= 1e-12 * max(1.0, np.abs(W).max())
+        print(f"device vs restatement over {len(cells)} cells, {len(W)} nodes: coords {np.abs(dX - X).max():.3e}, "
+              f"weights {np.abs(dW - W).max():.3e} (max |w| {np.abs(W).max():.3e})")
+        assert np.abs(dX - X).max() <= 1e-12
+        assert np.abs(dW - W).max() <= 1e-12 * max(1.0, np.abs(W).max())
     rx, rw = Q.full_rule(qo, ref.N)
     assert np.abs(q.rule.coords - rx).max() <= 1e-12 and np.abs(q.rule.weights - rw).max() <= 1e-12
     return cut, full

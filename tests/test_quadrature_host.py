@@ -160,3 +160,138 @@ def test_api_errors_without_a_device():
         lsm.integrate(lambda x: x[:, 0], object())
     q = lsm.Quadrature(np.array([[0.25], [0.75]]), np.array([0.5, 0.5]))
     assert lsm.integrate(lambda x: x[:, 0], q) == pytest.approx(0.5)
+
+
+# ----------------------------------------------------------------------------- fixtures of tests/test_gpu_quadrature_edges.py
+# Fields whose classification is known in closed form or from a row pattern, so that grids far beyond what the restatement
+# can sweep (more than 2^20 cut cells) still have an exact expectation.  Each builder is cached: the GPU file shares them.
+
+def _ref_of(vals, lc, hc, k, P=None):
+    return ReinitRef(_getter(vals, k if P is None else P), vals.shape, lc, hc, order=k, cells=[])
+
+
+def _along_axis0(v, n):
+    return np.asfortranarray(np.broadcast_to(v.reshape((-1,) + (1,) * (len(n) - 1)), n))
+
+
+def stripes1(n):
+    """k = 1: the sign alternates from node to node along axis 0, so every cell is cut by one plane x = x*"""
+    i = np.arange(n[0])
+    v = np.where(i % 2 == 0, 1.0, -1.0) * (0.3 + 0.2 * np.sin(1.7 * i))
+    return _along_axis0(v, n), (0.25, -0.5, 1.0)[:len(n)], (1.75, 0.4, 2.5)[:len(n)]
+
+
+def stripes1_closed_form(n, surface):
+    """the one node of every cell of stripes1(n) at q = 1, cells in ascending linear order: (coords (ncell, N), weights)"""
+    vals, lc, hc = stripes1(n)
+    N = len(n)
+    h = [(hc[d] - lc[d]) / (n[d] - 1) for d in range(N)]
+    v = vals[(slice(None),) + (0,) * (N - 1)]
+    a, b = v[:-1], v[1:]
+    t = a / (a - b)
+    lo0 = lc[0] + np.arange(n[0] - 1) * h[0]
+    if surface:
+        x0, w0 = lo0 + t * h[0], np.ones(n[0] - 1)
+    else:                       # the piece where ψ < 0: [0, t] if a < 0, else [t, 1]
+        u, w = np.where(a < 0, 0.0, t), np.where(a < 0, t, 1.0)
+        x0, w0 = lo0 + (u + (w - u) * 0.5) * h[0], (w - u) * h[0]
+    dims = tuple(k - 1 for k in n)
+    idx = np.unravel_index(np.arange(int(np.prod(dims))), dims, order="F")
+    X = np.empty((len(idx[0]), N))
+    X[:, 0] = x0[idx[0]]
+    for d in range(1, N):
+        X[:, d] = (lc[d] + idx[d] * h[d]) + 0.5 * h[d]
+    return X, w0[idx[0]] * float(np.prod(h[1:]))
+
+
+def stripes3(ny):
+    """k = 3 (ExtrapolationBC(3)), constant along y: per row 18 candidate cells (the Bernstein bound does not exclude 0),
+    12 of them with nodes, 6 empty ones (ψ does not vanish in the cell), and 6 full cells"""
+    n = (61, ny)
+    i = np.arange(61)
+    v = np.cos(2 * np.pi * i / 5 + 0.4) + 1.005 - 0.6 * (i % 10 >= 5)
+    return _along_axis0(v, n), (0.0, 0.0), (6.0, 0.5)
+
+
+def row_pattern(ref, j, q, surface):
+    """row j of a 2-D field: (columns of the candidate cells, {column: (coords, weights)} of those with nodes, full columns)"""
+    cells = [(i, j) for i in range(ref.n[0] - 1)]
+    cand, full = [], []
+    for I in cells:
+        c = ref.coeffs(I)
+        m, M = float(c.min()), float(c.max())
+        if (m * M > 0.0) if surface else (m > 0.0):
+            continue
+        (full if not surface and M < 0.0 else cand).append(I[0])
+    cut, full2, nfb = Q.quadrature(ref, q, surface, cells=cells)
+    assert nfb == 0 and [I[0] for I in full2] == full and {I[0] for I in cut} <= set(cand)
+    return cand, {I[0]: xw for I, xw in cut.items()}, full
+
+
+_KINK3D = lambda X: np.maximum(np.sqrt((X[0] - 0.13) ** 2 + (X[1] - 0.07) ** 2 + (X[2] + 0.04) ** 2) - 0.55,
+                               -(np.sqrt(X[0] ** 2 + (X[1] - 0.07) ** 2 + (X[2] + 0.04) ** 2) - 0.45))
+_KINK2D = lambda X: np.maximum(np.hypot(X[0] - 0.13, X[1] - 0.07) - 0.55, -(np.hypot(X[0], X[1] - 0.07) - 0.45))
+KINKS = {"kink3d": ((10, 9, 8), _KINK3D, 2), "kink2d_aniso": ((47, 32), _KINK2D, 4)}     # shape, field, q
+
+
+def kink(name):
+    """(vals, lc, hc) of a kinked set off the square grid: boxes at the horns reach the depth limit"""
+    n, f, _ = KINKS[name]
+    lc, hc = (-1.0,) * len(n), (1.0,) * len(n)
+    ax = [np.linspace(lc[d], hc[d], n[d]) for d in range(len(n))]
+    return np.asfortranarray(f(np.meshgrid(*ax, indexing="ij"))), lc, hc
+
+
+_CACHE = {}
+
+
+def restated(key, vals, lc, hc, k, q, surface, P=None):
+    """Q.quadrature of the whole grid, computed once per key and shared between the CPU and the GPU tests"""
+    if key not in _CACHE:
+        _CACHE[key] = Q.quadrature(_ref_of(vals, lc, hc, k, P), q, surface)
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("n", [(12, 7), (9, 5, 4)])
+@pytest.mark.parametrize("surface", [False, True])
+def test_stripes1_closed_form(n, surface):
+    vals, lc, hc = stripes1(n)
+    cut, full, nfb = Q.quadrature(_ref_of(vals, lc, hc, 1), 1, surface)
+    dims = tuple(k - 1 for k in n)
+    cells = [tuple(int(v) for v in I) for I in zip(*np.unravel_index(np.arange(int(np.prod(dims))), dims, order="F"))]
+    assert list(sorted(cut, key=lambda I: I[::-1])) == cells and full == [] and nfb == 0     # every cell is cut
+    assert all(len(cut[I][1]) == 1 for I in cells)
+    X, W = stripes1_closed_form(n, surface)
+    d = max(np.abs(np.concatenate([cut[I][0] for I in cells]) - X).max(), np.abs(np.concatenate([cut[I][1] for I in cells]) - W).max())
+    print(f"restatement vs closed form: {d:.3e}")
+    assert d <= 1e-12
+
+
+@pytest.mark.parametrize("surface", [False, True])
+def test_stripes3_row_pattern(surface):
+    ny = 12
+    vals, lc, hc = stripes3(ny)
+    ref = _ref_of(vals, lc, hc, 3)
+    rows = [0, 1, 5, ny - 3, ny - 2]
+    pats = [row_pattern(ref, j, 2, surface) for j in rows]
+    hy = 0.5 / (ny - 1)
+    worst = 0.0
+    for j, (cand, cut, full) in zip(rows, pats):
+        assert len(cand) == 18 and len(cut) == 12 and len(full) == (0 if surface else 6)
+        assert cand == pats[2][0] and sorted(cut) == sorted(pats[2][1]) and full == pats[2][2]
+        for i, (x, w) in cut.items():
+            xm, wm = pats[2][1][i]
+            assert x.shape == xm.shape
+            worst = max(worst, np.abs(x[:, 0] - xm[:, 0]).max(), np.abs(w - wm).max(),
+                        np.abs((x[:, 1] - j * hy) - (xm[:, 1] - rows[2] * hy)).max())
+    print(f"rows against the middle row: {worst:.3e}")
+    assert worst <= 1e-12
+
+
+@pytest.mark.parametrize("name", sorted(KINKS))
+@pytest.mark.parametrize("surface", [False, True])
+def test_kinks_reach_the_depth_limit(name, surface):
+    vals, lc, hc = kink(name)
+    cut, full, nfb = restated((name, surface), vals, lc, hc, 3, KINKS[name][2], surface)
+    print(f"{name}: {len(cut)} cut cells, {len(full)} full cells, nfallback = {nfb}")
+    assert nfb > 0 and len(cut) > 0
