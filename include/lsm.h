@@ -494,6 +494,40 @@ int lsm_cc_read(LsmCc* s, void* labels, void* nodes, void* index_sums, void* bbo
 int lsm_cc_flip(LsmCc* s, void* phi, const void* which, int64_t* flipped);
 void lsm_cc_destroy(LsmCc* s);
 
+/* ---- nucleation: the centres that a criterion field t selects on phi's grid, and the punch that removes a ball around each — the
+ *      step by which a level-set optimisation creates holes (csrc/lsm_nucleate.hip; tests/_topo_ref.py restates
+ *      the definition).  t is any dense field of the handle: the topological derivative of lsm_elastic_topo, a criterion of the
+ *      caller's, T − l with a volume multiplier.  Only the interiors of phi and t are read; values are converted to fp64 first.
+ *      Candidates: the interior node I is a candidate iff t_I < threshold and phi_I <= level − clearance (the difference formed once,
+ *      in fp64); both are false for NaN.  phi is taken to be roughly a signed distance, so that a candidate lies at least
+ *      `clearance` inside the material: that is the caller's business.
+ *      Centres: w_d = ceil(spacing/h_d) nodes per axis.  I is a centre iff it is a candidate and its key (t_I, linear index I, axis 0
+ *      fastest) is the lexicographic minimum over the candidates J with |J_d − I_d| <= w_d for every d, the window clipped at the
+ *      grid; −0 and +0 are one value.  Two centres differ by more than w_d nodes along some axis, hence lie more than `spacing`
+ *      apart; the list does not depend on the schedule.
+ *      lsm_nucleate_create: *count := the number of centres.  lsm_nucleate_read copies into device buffers (each may be NULL):
+ *      indices int64[count], the linear indices in ascending order, and values fp64[count], t at them.  LSM_ERR_INVALID: a 1-D
+ *      grid, a slab handle or one with a communicator, a periodic dimension (the window does not wrap), a non-finite threshold,
+ *      level, clearance or spacing, a w_d outside [1, 32], 2^31 − 1 nodes or more.  No centre is LSM_OK with count 0.
+ *      lsm_nucleate_punch, for `count` linear node indices on the device (any list: the centres above, a part of them, the caller's
+ *      own; repeats allowed): B_d = floor(radius/h_d) in fp64, and for the node I of the box |I_d − c_d| <= B_d of centre c,
+ *      clipped at the grid, d2 = sum_d ((I_d − c_d)·h_d)², d ascending from +0, the difference converted exactly; v = level +
+ *      (radius − sqrt(d2)), no contraction.  V_I = the largest v over the centres whose box holds I; phi_I := V_I where phi_I < V_I
+ *      (false for a NaN phi, which stays), rounded once to the storage type; every other node and the ghosts are untouched.  The
+ *      maximum commutes, so the result does not depend on the order of the list or on the schedule.  *changed := the number of
+ *      nodes whose stored bits changed.  With radius < h_d for every d only the centres themselves can change.  The result is the
+ *      distance to the ball inside it and no distance function around it: reinitialize afterwards.  LSM_ERR_INVALID with phi
+ *      untouched: the refusals of lsm_nucleate_create, a non-finite level, a radius not finite and positive, a negative count, an
+ *      index outside the grid.  count == 0 is LSM_OK and runs nothing.
+ *      The window keys (24 bytes per node) belong to the handle and only grow; the lists belong to the object.  Synchronous, on
+ *      the handle's stream. */
+typedef struct LsmNucleate LsmNucleate;
+int lsm_nucleate_create(LsmHandle* h, const void* phi, const void* t, double threshold, double level, double clearance, double spacing,
+                        LsmNucleate** out, int64_t* count);
+int lsm_nucleate_read(LsmNucleate* s, void* indices, void* values);
+void lsm_nucleate_destroy(LsmNucleate* s);
+int lsm_nucleate_punch(LsmHandle* h, void* phi, const void* centres, int64_t count, double level, double radius, int64_t* changed);
+
 /* ---- elliptic_solve: −∇·(a∇u) + c·u = f on the box of a dense 2-D or 3-D grid, the state equation of a shape optimisation with
  *      an ersatz material outside the level set, and with constant coefficients the H¹ regularisation (I − α²Δ)V = g; solved on
  *      the device by conjugate gradients preconditioned by one geometric multigrid V-cycle (csrc/lsm_elliptic.hip, DESIGN.md
@@ -735,6 +769,30 @@ int lsm_elastic_stress_norm(LsmElastic* s, const void* u0, const void* u1, const
 int lsm_elastic_stress_load(LsmElastic* s, const void* u0, const void* u1, const void* u2, double p, double sref, double* f_out);
 int lsm_elastic_stress_sensitivity(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* l0, const void* l1, const void* l2,
                                    double p, double sref, double scale, void* g_out);
+
+/* ---- topological derivative of the compliance (Garreau, Guillaume & Masmoudi 2001; Allaire, de Gournay, Jouve & Toader 2005): T is
+ *      the cost per unit volume removed — a small traction-free hole of volume v around x raises lsm_elastic_compliance by about
+ *      T(x)·v — computed from the cell strain and unit stress of the stress recovery above, whose setting, notation and Voigt order
+ *      it shares (csrc/lsm_elastic.hip; tests/_topo_ref.py restates every operation).  No contraction; every sum
+ *      starts from +0 and runs in the stated order.
+ *      w = shat : e = sum_i shat_ii·G_ii (i ascending), continued by sum over the shears of tauhat_ij·e_ij in Voigt order, one
+ *      accumulator.  tr = G_00 + G_11 (+ G_22); trs = shat_00 + shat_11 (+ shat_22), left to right: in 2-D the in-plane traces, also for
+ *      LSM_PLANE_STRAIN (shat_zz stays out).  T_C = E_C·(a·w + b·(trs·tr)).
+ *      a and b come from lambda, mu (the object's material at E = 1, plane-dependent) once, on the host, in fp64:
+ *      N = 2: g = (lambda + 2·mu)/((2·mu)·(lambda + mu)), a = g·(4·mu), b = g·(lambda − mu);
+ *      N = 3: g = (3·(lambda + 2·mu))/((4·mu)·(9·lambda + 14·mu)), a = g·(20·mu), b = g·(3·lambda − 2·mu)
+ *      — the polarisation of a circular / spherical void divided by the volume of the unit ball (pi, 4·pi/3).  In plane stress
+ *      T = ((s1 + s2)² + 2·(s1 − s2)²)/E in the principal stresses; in plane strain (1 − nu²) times that; in 3-D
+ *      3(1 − nu)/(2(7 − 5nu))·(10·s:e − (1 − 5nu)/(1 − 2nu)·tr(s)·tr(e)).  The formula is the void's: the ersatz modulus of the
+ *      outside is taken for void, and T_C there is small like E_C.  T_C >= 0 and T_C >= E_C·w.
+ *      lsm_elastic_topo_cells: one fp64 cell array on the device (n−1 per axis, axis 0 fastest).  lsm_elastic_topo: the node field
+ *      into the dense field o0 by the stress recovery's rule — (sum of T_C over the existing cells around I, ascending m, from
+ *      +0)/(their number), rounded once to the storage type; ghosts untouched.
+ *      LSM_ERR_INVALID without running anything: a missing or repeated field of u, an output that is missing or one of the inputs.
+ *      A non-finite u propagates.  lsm_elastic_topo uses the object's scratch vectors as lsm_elastic_stress does: it must not run
+ *      concurrently with a solve of the object or of its modes, and the results of a later solve are unaffected. */
+int lsm_elastic_topo_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, double* out);
+int lsm_elastic_topo(LsmElastic* s, const void* u0, const void* u1, const void* u2, void* o0);
 
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,

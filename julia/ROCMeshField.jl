@@ -749,6 +749,57 @@ function stress_sensitivity!(g::ROCMeshField, K, u, λ, p, sref, scale)
         K.op, q[1], q[2], q[3], l[1], l[2], l[3], p, sref, scale, pointer(g.buf)), "lsm_elastic_stress_sensitivity")
 end
 
+# Topological derivative of the compliance for a displacement u on an elasticity_operator K (include/lsm.h, lsm_elastic_topo*): the
+# cost per unit volume of a small traction-free hole.  The cell array into a ROCArray{Float64} of prod(n .- 1) values; the node field
+# (the mean over the cells around a node) into the field g, distinct from the fields of u.
+function topological_derivative_cells!(a, K, u)
+    p = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_topo_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}),
+        K.op, p[1], p[2], p[3], pointer(a)), "lsm_elastic_topo_cells")
+end
+function topological_derivative!(g::ROCMeshField, K, u)
+    p = _u3(u)
+    _check(K.h.ptr, ccall((:lsm_elastic_topo, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        K.op, p[1], p[2], p[3], pointer(g.buf)), "lsm_elastic_topo")
+    return g
+end
+
+# Nucleation (include/lsm.h, lsm_nucleate_*).  find_nucleation_sites: the nodes where t < threshold and ϕ ≤ level − clearance whose
+# (value, linear index) is the smallest among such nodes within ceil(spacing/h) nodes along every axis; returns the 0-based linear
+# indices (ascending, on the device) and t at them.  punch!: a ball of `radius` removed around each of the 0-based linear node
+# indices `centres` (a ROCVector{Int64}: those above, a part of them, the caller's own): ϕ ← max(ϕ, level + radius − |x − c|) over
+# the ball's bounding box; returns the number of nodes changed.  Not a distance function afterwards: reinitialize! next.
+# nucleate!: both, with the `max_holes` lowest centres by (value, index), spacing = 2·radius and clearance = radius by default.
+function find_nucleation_sites(ϕ::ROCMeshField, t::ROCMeshField; threshold, radius, spacing = 2radius, clearance = radius, level = 0.0)
+    out, count = Ref{Ptr{Cvoid}}(), Ref{Int64}(0)
+    _check(ϕ.h.ptr, ccall((:lsm_nucleate_create, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Ref{Ptr{Cvoid}}, Ref{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), pointer(t.buf), threshold, level, clearance, spacing, out, count), "lsm_nucleate_create")
+    K = count[]
+    indices, values = ROCVector{Int64}(undef, K), ROCVector{Float64}(undef, K)
+    code = K == 0 ? Cint(0) : ccall((:lsm_nucleate_read, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), out[], pointer(indices), pointer(values))
+    ccall((:lsm_nucleate_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), out[])
+    _check(ϕ.h.ptr, code, "lsm_nucleate_read")
+    return (; indices, values)
+end
+
+function punch!(ϕ::ROCMeshField, centres::ROCVector{Int64}; radius, level = 0.0)
+    changed = Ref{Int64}(0)
+    _check(ϕ.h.ptr, ccall((:lsm_nucleate_punch, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ref{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), isempty(centres) ? C_NULL : pointer(centres), length(centres), level, radius, changed), "lsm_nucleate_punch")
+    return changed[]
+end
+
+function nucleate!(ϕ::ROCMeshField, t::ROCMeshField; threshold, radius, spacing = 2radius, clearance = radius, max_holes = nothing, level = 0.0)
+    s = find_nucleation_sites(ϕ, t; threshold, radius, spacing, clearance, level)
+    idx, val = Array(s.indices), Array(s.values)
+    order = sortperm(collect(zip(val .+ 0.0, idx)))      # −0 and +0 are one value, as on the device
+    max_holes === nothing || (order = order[1:min(max_holes, length(order))])
+    centres = idx[order]
+    changed = punch!(ϕ, ROCVector{Int64}(centres); radius, level)
+    return (; centres, values = val[order], found = length(idx), changed)
+end
+
 # render: one picture of the interface {ϕ = level} (include/lsm.h, lsm_render_*; what ext/MakieExt.jl:142-171 draws), on the device.
 # 3-D: `camera` = 13 Float64 (eye, forward, right·s_x, up·s_y, orthographic flag), `style` = 9 Float64 (colour, background, ambient,
 # step, bisections); returns rgba 4 x W x H UInt8 (row 1 the top of the picture), depth W x H and normal 3 x W x H.  2-D: `camera`

@@ -16,7 +16,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   vortex_deformation, show, LocalGroup, nodeindices, cellindices, getnode, getcell, active_nodeindices, active_cellindices,
                   update_band_, quadrature, integrate, Quadrature, CellQuadratures, isosurface, export_surface_mesh, InterfaceMesh, Camera, Renderer, render, record_, Image,
                   volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
-                  components, remove_components_, prune_, Components,
+                  components, remove_components_, prune_, Components, nucleate_, find_nucleation_sites, Nucleation,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
                   elasticity_solve, ElasticityOperator, ElasticitySolution, elasticity_modes, ElasticityModes, StressSensitivity)
 
@@ -31,7 +31,7 @@ __all__ = [
     "nodeindices", "cellindices", "getnode", "getcell", "active_nodeindices", "active_cellindices", "update_band_",
     "quadrature", "integrate", "Quadrature", "CellQuadratures", "isosurface", "export_surface_mesh", "InterfaceMesh", "Camera", "Renderer", "render", "record_", "Image",
     "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
-    "components", "remove_components_", "prune_", "Components",
+    "components", "remove_components_", "prune_", "Components", "nucleate_", "find_nucleation_sites", "Nucleation",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
     "elasticity_solve", "ElasticityOperator", "ElasticitySolution", "elasticity_modes", "ElasticityModes", "StressSensitivity",
 ]

@@ -186,6 +186,13 @@ _SIGS = [
     ("lsm_elastic_stress_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     ("lsm_elastic_stress_sensitivity", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                  C.c_double, C.c_void_p]),
+    ("lsm_elastic_topo_cells", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_topo", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_nucleate_create", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_int64)]),
+    ("lsm_nucleate_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_nucleate_destroy", None, [C.c_void_p]),
+    ("lsm_nucleate_punch", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_int64)]),
     ("lsm_extend_along_normals", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_double, C.c_double, C.c_double]),
     ("lsm_band_tile_count", C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),

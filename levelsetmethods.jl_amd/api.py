@@ -2514,6 +2514,104 @@ def prune_(phi_or_eq, min_nodes=None, keep_largest=None, level=0.0, side="inside
     return comps, remove_components_(phi, comps, which)
 
 
+# ----------------------------------------------------------------------------- hole nucleation
+
+class Nucleation:
+    """nucleate_ / find_nucleation_sites' result: `centres` int64 (K, N), the multi-indices of the chosen nodes sorted by
+    (value, linear index); `indices` int64 (K), their linear indices (axis 0 fastest); `values` float64 (K), the criterion at them;
+    `found`, the number of centres before the cut to max_holes; `changed`, the number of nodes the punch changed (0 without one)."""
+
+    def __init__(self, mesh, indices, values, found, changed=0):
+        self.mesh, self.indices, self.values, self.found, self.changed = mesh, indices, values, int(found), int(changed)
+        n = [int(m) for m in mesh.n]
+        self.centres = (np.stack(np.unravel_index(indices, n, order="F"), axis=1).astype(np.int64) if indices.size
+                        else np.zeros((0, len(n)), dtype=np.int64))
+
+    def __len__(self):
+        return int(self.indices.size)
+
+    def __repr__(self):
+        return (f"Nucleation on a {self.mesh.ndim}-dimensional grid: {len(self)} of {self.found} "
+                f"{'centre' if self.found == 1 else 'centres'}, {self.changed} nodes changed")
+
+
+def _nucleation_field(x, what, name):
+    """the dense single-device 2-D / 3-D field behind nucleate_ / find_nucleation_sites, or the refusal"""
+    if isinstance(x, LevelSetEquation):
+        x = x.current_state()
+    if not isinstance(x, ROCMeshField):
+        raise TypeError(f"{what} takes device fields (ROCMeshField), not {type(x).__name__} for {name}")
+    if isinstance(x, ROCNarrowBandMeshField):
+        raise ValueError(f"{what} is not supported on NarrowBandMeshField: a band does not hold the whole set. Use a full MeshField.")
+    if x.mesh.ndim == 1:
+        raise ValueError(f"{what} of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    if getattr(x.backend, "slab", None) is not None:
+        raise ValueError(f"{what} of a slab-decomposed field (a field with a comm) is not supported")
+    if x.bcs is not None and any(bc.kind == L.BC_PERIODIC for pair in x.bcs for bc in pair):
+        raise ValueError(f"{what} with a PeriodicBC dimension is not supported: the window and the balls do not wrap")
+    if int(np.prod([int(n) for n in x.mesh.n], dtype=object)) >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: the grid has 2^31 - 1 nodes or more")
+    return x
+
+
+def _nucleation_args(phi, t, what, threshold, radius, spacing, clearance, max_holes, level):
+    """(ϕ, t, threshold, radius, spacing, clearance, max_holes, level) checked: the refusals need no device call"""
+    threshold, radius, level = float(threshold), float(radius), float(level)
+    if not (math.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"{what}: radius must be finite and positive")
+    spacing = 2.0 * radius if spacing is None else float(spacing)
+    clearance = radius if clearance is None else float(clearance)
+    if not (math.isfinite(threshold) and math.isfinite(level) and math.isfinite(clearance)):
+        raise ValueError(f"{what}: threshold, level and clearance must be finite")
+    if not math.isfinite(spacing):
+        raise ValueError(f"{what}: spacing must be finite")
+    if max_holes is not None:
+        max_holes = int(max_holes)
+        if max_holes < 0:
+            raise ValueError(f"{what}: max_holes must not be negative")
+    phi, t = _nucleation_field(phi, what, "phi"), _nucleation_field(t, what, "t")
+    if t.backend is not phi.backend:
+        raise ValueError(f"{what}: t must be a field of phi's backend (the same grid and layout)")
+    w = [math.ceil(spacing / float(h)) for h in phi.mesh.meshsize()]
+    if min(w) < 1 or max(w) > 32:
+        raise ValueError(f"{what}: the window ceil(spacing/h) = {tuple(w)} nodes must lie in [1, 32] along every axis")
+    return phi, t, threshold, radius, spacing, clearance, max_holes, level
+
+
+def _nucleation_sites(phi, t, threshold, spacing, clearance, max_holes, level):
+    idx, val = phi.backend.nucleate_find(phi.buf, t.buf, threshold, level, clearance, spacing)
+    order = np.lexsort((idx, val))      # by (value, index); −0 and +0 compare equal, as on the device
+    found = int(idx.size)
+    if max_holes is not None:
+        order = order[:max_holes]
+    return idx[order], val[order], found
+
+
+def find_nucleation_sites(phi, t, *, threshold, radius, spacing=None, clearance=None, max_holes=None, level=0.0):
+    """nucleate_ without the punch: the centres the criterion field t selects, as a Nucleation with changed = 0; ϕ is not written."""
+    phi, t, threshold, radius, spacing, clearance, max_holes, level = _nucleation_args(phi, t, "find_nucleation_sites", threshold, radius, spacing, clearance,
+                                                                                         max_holes, level)
+    idx, val, found = _nucleation_sites(phi, t, threshold, spacing, clearance, max_holes, level)
+    return Nucleation(phi.mesh, idx, val, found)
+
+
+def nucleate_(phi, t, *, threshold, radius, spacing=None, clearance=None, max_holes=None, level=0.0):
+    """Punch holes into ϕ where the criterion field t is lowest, on the device: the step by which a level-set
+    optimisation changes topology.  t: a dense ROCMeshField on ϕ's backend — ElasticitySolution.topological_derivative(), or any
+    criterion of the caller's.  A node is a candidate where t < threshold and ϕ ≤ level − clearance (inside the material, away from
+    the boundary; ϕ is taken for a signed distance); a candidate is a centre iff its (value, index) is the smallest among the
+    candidates within ceil(spacing/h) nodes of it along every axis, so two centres are more than `spacing` apart.  The centres
+    are sorted by (value, index), cut to the `max_holes` lowest, and a ball of `radius` is removed around each:
+    ϕ ← max(ϕ, level + radius − |x − c|) over the ball's bounding box.  spacing defaults to 2·radius (disjoint balls), clearance
+    to radius.  Returns a Nucleation and sets ϕ.ghosts_dirty; follow with reinitialize_ before anything that relies on |∇ϕ| = 1."""
+    phi, t, threshold, radius, spacing, clearance, max_holes, level = _nucleation_args(phi, t, "nucleate_", threshold, radius, spacing, clearance, max_holes,
+                                                                                         level)
+    idx, val, found = _nucleation_sites(phi, t, threshold, spacing, clearance, max_holes, level)
+    changed = phi.backend.nucleate_punch(phi.buf, idx, level, radius) if idx.size else 0
+    phi.ghosts_dirty = True
+    return Nucleation(phi.mesh, idx, val, found, changed)
+
+
 # ----------------------------------------------------------------------------- elliptic solves (the state equation of a shape optimisation)
 
 _PRECONDS = {"mg": L.PRECOND_MG, "jacobi": L.PRECOND_JACOBI}
@@ -2778,7 +2876,8 @@ class ElasticitySolution:
     E_C·(C₀ε:ε averaged over the cell) — the integrand of the compliance shape derivative, the normal speed of a compliance
     descent (coeff.set_values takes it device to device); compliance() = ∏h·Σ b·u, reduced on the device.  Stress recovery
     (DESIGN.md §7.20): strain(), stress() (tuples of ROCMeshFields in Voigt order), von_mises(), stress_max(), stress_norm(p, sref),
-    stress_sensitivity(p, sref, rtol, max_iters) → StressSensitivity."""
+    stress_sensitivity(p, sref, rtol, max_iters) → StressSensitivity.  topological_derivative(): the ROCMeshField T that nucleate_ takes
+    (DESIGN.md §7.21)."""
 
     def __init__(self, op, u, f, iterations, relres):
         self.operator, self.u, self._f, self.iterations, self.relres, self.levels = op, tuple(u), f, int(iterations), float(relres), op.levels
@@ -2816,6 +2915,15 @@ class ElasticitySolution:
     def von_mises(self):
         """the von Mises stress (with the out-of-plane normal stress in plane strain) as one ROCMeshField"""
         return self._stress_fields(L.STRESS_VON_MISES, 1)[0]
+
+    def topological_derivative(self):
+        """the topological derivative of the compliance as one ROCMeshField: a small traction-free hole of volume
+        v around x raises compliance() by about T(x)·v.  T ≥ 0; nucleate_ punches holes where it is lowest."""
+        op = self.operator
+        h = op._handle()
+        out = ROCMeshField(op.backend, self.u[0].mesh, self.u[0].bcs)
+        op.backend.elastic_topo(h, [c.buf for c in self.u], out.buf)
+        return out
 
     def stress_max(self):
         """the largest von Mises stress of a cell"""

@@ -405,6 +405,37 @@ class HipBackend:
     def cc_destroy(self, cc):
         self.lib.lsm_cc_destroy(cc)
 
+    # ---- nucleation (lsm_nucleate_*)
+    def nucleate_find(self, phi, t, threshold, level, clearance, spacing):
+        """(linear indices int64, values fp64) of the centres, on the host, in ascending index"""
+        for x in (phi, t):
+            if not self.torch.is_tensor(x) or not x.is_cuda:
+                raise TypeError(f"nucleate_find takes device buffers of this backend, not {type(x).__name__}")
+        if self.slab is not None:     # a one-rank group's slab is the whole grid with no communicator: the library could not tell
+            raise L.LsmError("nucleate_find: this backend holds a slab of a decomposed grid; lsm_nucleate_create works on the whole grid of one device")
+        out, count = C.c_void_p(), C.c_int64(0)
+        L.check(self.h, self.lib.lsm_nucleate_create(self.h, self.ptr(phi), self.ptr(t), float(threshold), float(level), float(clearance), float(spacing),
+                                                     C.byref(out), C.byref(count)), "lsm_nucleate_create")
+        try:
+            K, tt = int(count.value), self.torch
+            idx = tt.empty((K,), dtype=tt.int64, device=self.device)
+            val = tt.empty((K,), dtype=tt.float64, device=self.device)
+            if K:
+                L.check(self.h, self.lib.lsm_nucleate_read(out, self.ptr(idx), self.ptr(val)), "lsm_nucleate_read")
+            return idx.cpu().numpy(), val.cpu().numpy()
+        finally:
+            self.lib.lsm_nucleate_destroy(out)
+
+    def nucleate_punch(self, phi, centres, level, radius):
+        """punch balls around the linear node indices `centres` (host int64) into ϕ; returns the number of nodes changed"""
+        if self.slab is not None:
+            raise L.LsmError("nucleate_punch: this backend holds a slab of a decomposed grid; lsm_nucleate_punch works on the whole grid of one device")
+        c = self.torch.from_numpy(np.ascontiguousarray(centres, dtype=np.int64)).to(self.device)
+        n = C.c_int64(0)
+        L.check(self.h, self.lib.lsm_nucleate_punch(self.h, self.ptr(phi), self.ptr(c) if c.numel() else None, int(c.numel()), float(level), float(radius),
+                                                    C.byref(n)), "lsm_nucleate_punch")
+        return int(n.value)
+
     # ---- elliptic solves (lsm_elliptic_*)
     def interior(self, t):
         """the interior of a padded field as a strided view, the grid's axes reversed (its C order is the grid's axis-0-fastest order)"""
@@ -552,6 +583,16 @@ class HipBackend:
     def elastic_stress_sensitivity(self, obj, u, adj, p, sref, scale, g):
         L.check(self.h, self.lib.lsm_elastic_stress_sensitivity(obj, *self._u3(u), *self._u3(adj), float(p), float(sref), float(scale), self.ptr(g)),
                 "lsm_elastic_stress_sensitivity")
+
+    # ---- topological derivative of the compliance (lsm_elastic_topo*)
+    def elastic_topo_cells(self, obj, u):
+        """the fp64 cell array T_C as a flat device tensor"""
+        out = self.torch.empty(int(np.prod([m - 1 for m in self.local_shape()])), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_topo_cells(obj, *self._u3(u), self.ptr(out)), "lsm_elastic_topo_cells")
+        return out
+
+    def elastic_topo(self, obj, u, out):
+        L.check(self.h, self.lib.lsm_elastic_topo(obj, *self._u3(u), self.ptr(out)), "lsm_elastic_topo")
 
     # ---- vibration modes (lsm_elastic_modes_*): the modes object borrows the elastic object
     def modes_create(self, obj, phi, level, rho_in, rho_out, rho_cells, m):

@@ -139,6 +139,7 @@ LsmHandle::~LsmHandle() {
     mdist_workspace_free(mdist_ws);
     eikonal_workspace_free(eikonal_ws);
     cc_workspace_free(cc_ws);
+    nu_workspace_free(nu_ws);
 }
 
 extern "C" {
@@ -1877,6 +1878,56 @@ void lsm_cc_destroy(LsmCc* s) {
     if (!s) return;
     cc_free(s->o);
     delete s;
+}
+
+// nucleation: the centres a criterion field selects on phi's grid, and the punch of a ball around each (lsm_nucleate.hip)
+struct LsmNucleate { LsmHandle* h; NuObject* o; };
+static int nucleate_refusals(LsmHandle* h, const char* who) {
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, std::string(who) + ": a 1-dimensional grid is not supported (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, std::string(who) + ": the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    for (int d = 0; d < N; ++d)
+        if (h->bc[d][0].kind == LSM_BC_PERIODIC || h->bc[d][1].kind == LSM_BC_PERIODIC)
+            return fail(h, LSM_ERR_INVALID, std::string(who) + ": a periodic dimension is not supported (the window and the balls do not wrap)");
+    return LSM_OK;
+}
+int lsm_nucleate_create(LsmHandle* h, const void* phi, const void* t, double threshold, double level, double clearance, double spacing, LsmNucleate** out,
+                        int64_t* count) {
+    if (!h || !phi || !t || !out || !count) return h ? fail(h, LSM_ERR_INVALID, "lsm_nucleate_create: null argument") : LSM_ERR_INVALID;
+    LSM_TRY(nucleate_refusals(h, "lsm_nucleate_create"));
+    const char* err = nullptr;
+    NuObject* o = nullptr;
+    long long c = 0;
+    const int r = nu_build(h, &h->nu_ws, phi, t, threshold, level, clearance, spacing, &o, &c, &err);
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_nucleate_create");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_nucleate_create");
+    *count = c;
+    *out = new LsmNucleate{h, o};
+    return LSM_OK;
+}
+int lsm_nucleate_read(LsmNucleate* s, void* indices, void* values) {
+    if (!s) return LSM_ERR_INVALID;
+    const char* err = nullptr;
+    if (nu_read(s->o, (long long*)indices, (double*)values, &err)) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_nucleate_read");
+    return LSM_OK;
+}
+void lsm_nucleate_destroy(LsmNucleate* s) {
+    if (!s) return;
+    nu_free(s->o);
+    delete s;
+}
+int lsm_nucleate_punch(LsmHandle* h, void* phi, const void* centres, int64_t count, double level, double radius, int64_t* changed) {
+    if (!h || !phi || !changed || (!centres && count > 0)) return h ? fail(h, LSM_ERR_INVALID, "lsm_nucleate_punch: null argument") : LSM_ERR_INVALID;
+    *changed = 0;
+    LSM_TRY(nucleate_refusals(h, "lsm_nucleate_punch"));
+    const char* err = nullptr;
+    long long n = 0;
+    const int r = nu_punch(h, &h->nu_ws, phi, (const long long*)centres, count, level, radius, &n, &err);
+    *changed = n;
+    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_nucleate_punch");
+    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_nucleate_punch");
+    return LSM_OK;
 }
 
 // volume_mesh (ext/MMGVolumeExt.jl up to the remesher): build once, copy the vertices, the elements and the interface elements out

@@ -1703,3 +1703,82 @@ int lsm_elastic_stress_sensitivity(LsmElastic* s, const void* u0, const void* u1
     MG_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
+
+// ======================================================================================================================================
+// Topological derivative of the compliance: what a small traction-free hole at a cell would cost per unit volume removed, from the
+// cell strain and unit stress of the stress recovery.  include/lsm.h ("topological derivative") is the normative text,
+// tests/_topo_ref.py restates it, DESIGN.md §7.21.  One thread per cell, then the stress recovery's gather for the node field.
+namespace lsm {
+
+struct TdMat { double a, b; };
+
+// a, b of T_C = E_C·(a·w + b·(trs·tr)), from the material at E = 1, in fp64 on the host
+static TdMat td_mat(const ElasticObject& o) {
+    const double lam = o.lam, mu = o.mu;
+    TdMat T;
+    if (o.N == 2) {
+        const double g = (lam + 2.0 * mu) / ((2.0 * mu) * (lam + mu));
+        T.a = g * (4.0 * mu);
+        T.b = g * (lam - mu);
+    } else {
+        const double g = (3.0 * (lam + 2.0 * mu)) / ((4.0 * mu) * (9.0 * lam + 14.0 * mu));
+        T.a = g * (20.0 * mu);
+        T.b = g * (3.0 * lam - 2.0 * mu);
+    }
+    return T;
+}
+
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) td_cells_kernel(EsLevel L, MgField F, EsU U, SsMat P, TdMat T, int nc, double* __restrict__ out) {
+    constexpr int M = N * (N + 1) / 2;
+    MG_LOOP(ci, nc) {
+        int C[3];
+        ss_cell_coords<N>(L.n, ci, C);
+        double uc[(1 << N) * N], e[M], sn[3], tau[M - N];
+        ss_corners<N>(F, U, C, uc);
+        ss_unit<N>(uc, P, e, sn, tau);
+        double w = 0.0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) w = w + sn[i] * e[i];
+#pragma unroll
+        for (int k = 0; k < M - N; ++k) w = w + tau[k] * e[N + k];
+        double tr = e[0] + e[1], trs = sn[0] + sn[1];      // the in-plane traces in 2-D, also for plane strain
+        if (N > 2) {
+            tr = tr + e[2];
+            trs = trs + sn[2];
+        }
+        out[ci] = L.E[ci] * (T.a * w + T.b * (trs * tr));
+    }
+}
+
+}  // namespace lsm
+
+int lsm_elastic_topo_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, double* out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (!es_fields(o.N, u0, u1, u2, U) || !out || out == u0 || out == u1 || out == u2)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_topo_cells: the N distinct fields of u and an array of its own must be given");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    MG_LAUNCH(o.N, td_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, s->h->stream, L, o.F, U, ss_mat(o), td_mat(o), nc, out);
+    MG_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_topo(LsmElastic* s, const void* u0, const void* u1, const void* u2, void* o0) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (!es_fields(o.N, u0, u1, u2, U) || !o0 || o0 == u0 || o0 == u1 || o0 == u2)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_topo: the components of u and the output field must be distinct fields");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    hipStream_t st = s->h->stream;
+    double* cell = o.xa[0];      // one cell array of the 6·N·nn scratch doubles
+    SsOut O = {{o0, nullptr, nullptr, nullptr, nullptr, nullptr}};
+    MG_LAUNCH(o.N, td_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, ss_mat(o), td_mat(o), nc, cell);
+    MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, 1, 1.0, O);
+    MG_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}

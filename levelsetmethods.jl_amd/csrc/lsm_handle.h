@@ -57,6 +57,7 @@ struct I2oeWorkspace;   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
 struct MdistWorkspace;  // lsm_mdist.hip: mesh_distance's scratch arrays
 struct EikonalWorkspace;   // lsm_eikonal.hip: eikonal's arrival times, frozen mask and tile lists
 struct CcWorkspace;     // lsm_cc.hip: components' parent array, chunk counts and counters
+struct NuWorkspace;     // lsm_nucleate.hip: nucleation's window keys, chunk counts and counters
 }  // namespace lsm
 struct LsmComm;   // lsm_comm.hip: slab communicator (RCCL or in-process), NULL on a single-device handle
 
@@ -144,6 +145,7 @@ struct LsmHandle {
     lsm::MdistWorkspace* mdist_ws = nullptr;     // lsm_mesh_distance's squared distances and flip counters, kept between calls (grow-only)
     lsm::EikonalWorkspace* eikonal_ws = nullptr; // lsm_eikonal's arrival times, frozen mask, tile flags and lists, kept between calls (grow-only)
     lsm::CcWorkspace* cc_ws = nullptr;           // lsm_cc_*'s parent array (4 bytes per node), chunk counts and counters, kept between calls (grow-only)
+    lsm::NuWorkspace* nu_ws = nullptr;           // lsm_nucleate_*'s window keys (24 bytes per node), chunk counts and counters, kept between calls (grow-only)
     LsmComm* comm = nullptr;       // multi-GPU: attached by lsm_comm_attach_* (slab handles)
     bool yredirect = false;        // ... and those of dimension 2 (3-D)
     bool mredirect = false;        // ... and the march axis' NeumannBC faces are served by clamping the march at the boundary plane: no fill is left
@@ -213,4 +215,14 @@ int cc_read(CcObject* o, int* labels, long long* nodes, long long* sums, int* bb
 int cc_flip(CcObject* o, CcWorkspace* w, void* phi, const unsigned char* which, long long* flipped, const char** err);
 void cc_free(CcObject* o);
 void cc_workspace_free(CcWorkspace* w);   // delete, where the type is complete
+}
+namespace lsm {   // lsm_nucleate.hip: the centres a criterion field selects by non-maximum suppression, and the punch of a ball around each
+struct NuObject;
+int nu_build(const LsmHandle* h, NuWorkspace** workspace, const void* phi, const void* t, double threshold, double level, double clearance, double spacing,
+             NuObject** out, long long* count, const char** err);
+int nu_read(NuObject* o, long long* indices, double* values, const char** err);
+int nu_punch(const LsmHandle* h, NuWorkspace** workspace, void* phi, const long long* centres, long long count, double level, double radius, long long* changed,
+             const char** err);
+void nu_free(NuObject* o);
+void nu_workspace_free(NuWorkspace* w);   // delete, where the type is complete
 }
