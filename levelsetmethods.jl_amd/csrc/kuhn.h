@@ -126,13 +126,9 @@ __device__ __forceinline__ void kuhn_advance(const KuhnArgs& a, int I[3]) {
 }
 // sums[r·nchunk + chunk] := the workgroup's sum of x_r, r < 3 (integer sums: any order gives the same).  Every thread calls this.
 __device__ __forceinline__ void kuhn_chunk_sums(unsigned x0, unsigned x1, unsigned x2, unsigned* sums, long long nchunk) {
-    __shared__ unsigned tot[3];
-    if (threadIdx.x < 3) tot[threadIdx.x] = 0;
-    __syncthreads();
-    x0 = wave_sum(x0); x1 = wave_sum(x1); x2 = wave_sum(x2);
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&tot[0], x0); atomicAdd(&tot[1], x1); atomicAdd(&tot[2], x2); }
-    __syncthreads();
-    if (threadIdx.x < 3) sums[threadIdx.x * nchunk + blockIdx.x] = tot[threadIdx.x];
+    __shared__ unsigned wsum[3][4];
+    x0 = block_sum<4>(x0, wsum[0]); x1 = block_sum<4>(x1, wsum[1]); x2 = block_sum<4>(x2, wsum[2]);
+    if (threadIdx.x == 0) { sums[blockIdx.x] = x0; sums[nchunk + blockIdx.x] = x1; sums[2 * nchunk + blockIdx.x] = x2; }
 }
 
 // ---- what the later kernels share
@@ -178,13 +174,6 @@ __device__ __forceinline__ void kuhn_interface_elements(const KuhnArgs& a, long 
 
 // ---- host side (defined in lsm_iso.hip)
 
-// kernel<2> or kernel<3> by the number of dimensions, 256 threads per workgroup
-#define KUHN_LAUNCH(ndim, kernel, grid, stream, ...)                                                          \
-    do {                                                                                                      \
-        if ((ndim) == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(256), 0, stream, __VA_ARGS__);        \
-        else hipLaunchKernelGGL(kernel<3>, dim3(grid), dim3(256), 0, stream, __VA_ARGS__);                    \
-    } while (0)
-
 // the front half of a build: kuhn_begin, the feature's classify sweep over w.nchunk chunks, kuhn_totals.  The buffers are
 // released with the struct.
 struct KuhnWork {
@@ -200,7 +189,7 @@ struct KuhnWork {
 // kuhn_begin fills w.a from the handle's grid and allocates the buffers.
 int kuhn_begin(const LsmHandle* h, double level, const void* phi, const unsigned char* mask, long long max_chunks, const char* const msg[5],
                KuhnWork& w, const char** err);
-// kuhn_totals scans the three rows of w.sums into w.off (the one scan kernel, one workgroup) and reads the totals.
+// kuhn_totals scans the three rows of w.sums into w.off (scan.h's kernel, one workgroup) and reads the totals.
 int kuhn_totals(KuhnWork& w, hipStream_t stream, const char* const msg[5], const char** err);
 // device-to-device copies of the arrays the caller asked for (dst NULL or no bytes: skipped), then a synchronise
 struct KuhnCopy { void* dst; const void* src; size_t bytes; };

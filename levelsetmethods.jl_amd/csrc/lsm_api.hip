@@ -45,11 +45,12 @@ static int fail(LsmHandle* h, int code, const std::string& msg) {
     return code;
 }
 int lsm_fail(LsmHandle* h, int code, const std::string& msg) { return fail(h, code, msg); }
-#define LSM_HIP(h, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+// what a module function returned (0, 1: refused, 3: not converged, otherwise a device error) as the C ABI's code, the module's
+// message, or the caller's name where it left none, on the handle
+static int module_rc(LsmHandle* h, int r, const char* err, const char* who) {
+    if (!r) return LSM_OK;
+    return fail(h, r == 1 ? LSM_ERR_INVALID : r == 3 ? LSM_ERR_NOT_CONVERGED : LSM_ERR_HIP, err ? err : who);
+}
 // host wait for the handle's stream (lsm_host_sync: cannot be hung by a silent RCCL peer)
 #define LSM_SYNC(h) do { int rs_ = lsm_host_sync(h, __func__); if (rs_) return rs_; } while (0)
 
@@ -1638,8 +1639,7 @@ int lsm_reinitialize(LsmHandle* h, void* phi, const void* mask, void* work, int 
     const char* err = nullptr;
     const int r = reinit_run(N, h->nloc, h->goff, h->lay.stride[1], h->lay.stride[2], h->lay.origin, h->lay.total, lc, h->h, order, upsample, maxiters, xtol, ftol,
                              phi, is_f32(h), (const unsigned char*)mask, work, h->stream, counts, &err, &h->reinit_ws);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_reinitialize");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_reinitialize");
+    if (r) return module_rc(h, r, err, "lsm_reinitialize");
     if (ncandidate_cells) *ncandidate_cells = counts[0];
     if (nfail) *nfail = counts[1];
     if (nfar) *nfar = counts[2];
@@ -1681,8 +1681,7 @@ int lsm_sdf_create(LsmHandle* h, void* phi, const void* mask, int order, int ups
     long long ns = 0;
     const int r = sdf_build(N, h->nloc, h->goff, h->lay.stride[1], h->lay.stride[2], h->lay.origin, h->lay.total, lc, h->h, order, upsample, maxiters,
                             xtol, ftol, phi, is_f32(h), (const unsigned char*)mask, h->stream, &o, &ns, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_sdf_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_sdf_create");
+    if (r) return module_rc(h, r, err, "lsm_sdf_create");
     *out = new LsmSdf{h, o, N};
     if (nsamples) *nsamples = ns;
     return LSM_OK;
@@ -1725,8 +1724,7 @@ int lsm_quad_create(LsmHandle* h, void* phi, const void* mask, int interpolation
     long long c[4] = {0, 0, 0, 0};
     const int r = quad_build(N, h->nloc, h->goff, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, interpolation_order, quadrature_order,
                              surface, phi, is_f32(h), (const unsigned char*)mask, h->stream, &o, c, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_quad_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_quad_create");
+    if (r) return module_rc(h, r, err, "lsm_quad_create");
     *out = new LsmQuad{h, o};
     if (counts)
         for (int i = 0; i < 4; ++i) counts[i] = c[i];
@@ -1765,8 +1763,7 @@ int lsm_iso_create(LsmHandle* h, const void* phi, const void* mask, double level
     IsoObject* o = nullptr;
     long long c[2] = {0, 0};
     const int r = iso_build(h, level, phi, (const unsigned char*)mask, &o, c, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_iso_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_iso_create");
+    if (r) return module_rc(h, r, err, "lsm_iso_create");
     *out = new LsmIso{h, o};
     if (counts) { counts[0] = c[0]; counts[1] = c[1]; }
     return LSM_OK;
@@ -1800,8 +1797,7 @@ int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_
     long long c[3] = {0, 0, 0};
     const int r = mdist_run(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, h->h, nverts, (const double*)vertices, nelems,
                             (const long long*)elements, cutoff, phi_out, is_f32(h), stream ? (hipStream_t)stream : h->stream, c, &err, &h->mdist_ws);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_mesh_distance");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_mesh_distance");
+    if (r) return module_rc(h, r, err, "lsm_mesh_distance");
     if (stats)
         for (int i = 0; i < 3; ++i) stats[i] = c[i];
     return LSM_OK;
@@ -1827,10 +1823,7 @@ int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, doub
                               stream ? (hipStream_t)stream : h->stream, c, &err, &h->eikonal_ws);
     if (stats)
         for (int i = 0; i < 4; ++i) stats[i] = c[i];
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_eikonal");
-    if (r == 3) return fail(h, LSM_ERR_NOT_CONVERGED, err ? err : "lsm_eikonal");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_eikonal");
-    return LSM_OK;
+    return module_rc(h, r, err, "lsm_eikonal");
 }
 
 // components: the connected pieces of {phi < level} (side 0) or of its complement (side 1) over the Kuhn edges (lsm_cc.hip)
@@ -1852,8 +1845,7 @@ int lsm_cc_create(LsmHandle* h, const void* phi, double level, int side, LsmCc**
     const int r = cc_build(h, &h->cc_ws, level, side, phi, &o, c, &err);
     if (stats)
         for (int i = 0; i < 4; ++i) stats[i] = c[i];
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_cc_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_cc_create");
+    if (r) return module_rc(h, r, err, "lsm_cc_create");
     *out = new LsmCc{h, o};
     return LSM_OK;
 }
@@ -1870,9 +1862,7 @@ int lsm_cc_flip(LsmCc* s, void* phi, const void* which, int64_t* flipped) {
     long long n = 0;
     const int r = cc_flip(s->o, s->h->cc_ws, phi, (const unsigned char*)which, &n, &err);
     *flipped = n;
-    if (r == 1) return fail(s->h, LSM_ERR_INVALID, err ? err : "lsm_cc_flip");
-    if (r) return fail(s->h, LSM_ERR_HIP, err ? err : "lsm_cc_flip");
-    return LSM_OK;
+    return module_rc(s->h, r, err, "lsm_cc_flip");
 }
 void lsm_cc_destroy(LsmCc* s) {
     if (!s) return;
@@ -1900,8 +1890,7 @@ int lsm_nucleate_create(LsmHandle* h, const void* phi, const void* t, double thr
     NuObject* o = nullptr;
     long long c = 0;
     const int r = nu_build(h, &h->nu_ws, phi, t, threshold, level, clearance, spacing, &o, &c, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_nucleate_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_nucleate_create");
+    if (r) return module_rc(h, r, err, "lsm_nucleate_create");
     *count = c;
     *out = new LsmNucleate{h, o};
     return LSM_OK;
@@ -1925,9 +1914,7 @@ int lsm_nucleate_punch(LsmHandle* h, void* phi, const void* centres, int64_t cou
     long long n = 0;
     const int r = nu_punch(h, &h->nu_ws, phi, (const long long*)centres, count, level, radius, &n, &err);
     *changed = n;
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_nucleate_punch");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_nucleate_punch");
-    return LSM_OK;
+    return module_rc(h, r, err, "lsm_nucleate_punch");
 }
 
 // volume_mesh (ext/MMGVolumeExt.jl up to the remesher): build once, copy the vertices, the elements and the interface elements out
@@ -1944,8 +1931,7 @@ int lsm_vol_create(LsmHandle* h, const void* phi, const void* mask, double level
     VolObject* o = nullptr;
     long long c[3] = {0, 0, 0};
     const int r = vol_build(h, level, phi, &o, c, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_vol_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_vol_create");
+    if (r) return module_rc(h, r, err, "lsm_vol_create");
     *out = new LsmVol{h, o};
     if (counts)
         for (int i = 0; i < 3; ++i) counts[i] = c[i];
@@ -1979,8 +1965,7 @@ int lsm_render_create(LsmHandle* h, const void* phi, const void* mask, double le
     RenderObject* o = nullptr;
     const int r = render_build(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, lc, hc, h->h, level, phi, is_f32(h),
                                (const unsigned char*)mask, h->stream, &o, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_render_create");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_render_create");
+    if (r) return module_rc(h, r, err, "lsm_render_create");
     *out = new LsmRender{h, o};
     return LSM_OK;
 }
@@ -2014,9 +1999,7 @@ int lsm_render_draw(LsmRender* s, const double camera[13], int width, int height
     const char* err = nullptr;
     const int r = render_draw(s->o, camera, width, height, style, h->tune.render_skip != 0, (unsigned char*)rgba, depth_or_cls, (double*)normal,
                               stream ? (hipStream_t)stream : h->stream, &err);
-    if (r == 1) return fail(h, LSM_ERR_INVALID, err ? err : "lsm_render_draw");
-    if (r) return fail(h, LSM_ERR_HIP, err ? err : "lsm_render_draw");
-    return LSM_OK;
+    return module_rc(h, r, err, "lsm_render_draw");
 }
 int lsm_render_bricks(LsmRender* s, int64_t* dims, void* table) {
     if (!s || !dims) return LSM_ERR_INVALID;

@@ -11,7 +11,7 @@
 //              parent[I] := the global index of the local root.  Counts the set nodes and the non-finite values.
 //   cc_merge   the forward edges that leave a tile (faces, edges and the corner): a lock-free union on global memory.
 //   cc_flatten parent[I] := root(I); counts the roots of every chunk of CC_CHUNK nodes.
-//   cc_scan    exclusive scan of the chunk counts in one workgroup; K.  The host reads K and the counters here: its one read.
+//   chunk_scan exclusive scan of the chunk counts in one workgroup (scan.h); K.  The host reads K and the counters here: its one read.
 //   cc_number  labels[r] := the rank of root r among the roots;  cc_init clears the K-sized statistics.
 //   cc_label   one workgroup per tile: labels[I] := labels[parent[I]] or −1; the statistics are summed per label in an LDS hash
 //              table first (a wave that holds one label adds once), then one global atomic per statistic and per (tile, label).
@@ -36,6 +36,7 @@
 #include <memory>
 
 #include "kuhn.h"
+#include "scan.h"
 
 namespace lsm {
 
@@ -186,9 +187,7 @@ __global__ void __launch_bounds__(CcTile<N>::X * CcTile<N>::Y * CcTile<N>::Z) cc
 // parent[i] := root(i), in place.  Another thread may store parent[r] while this one walks over it: the old value and the new
 // are both ancestors of r, roots do not change in this kernel, and an aligned 4-byte word is never torn.
 __global__ void __launch_bounds__(256) cc_flatten_kernel(CcArgs a, unsigned* parent, unsigned* __restrict__ sums) {
-    __shared__ unsigned s_tot;
-    if (threadIdx.x == 0) s_tot = 0;
-    __syncthreads();
+    __shared__ unsigned wsum[4];
     const long long c0 = (long long)blockIdx.x * CC_CHUNK;
     unsigned roots = 0;
 #pragma unroll 4
@@ -201,32 +200,8 @@ __global__ void __launch_bounds__(256) cc_flatten_kernel(CcArgs a, unsigned* par
         parent[i] = r;
         roots += r == (unsigned)i;
     }
-    roots = wave_sum(roots);
-    if ((threadIdx.x & 63) == 0 && roots) atomicAdd(&s_tot, roots);
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = s_tot;
-}
-
-// off[c] := the number of roots in the chunks before c; st[CC_K] := their total.  One workgroup of 1024 threads.
-__global__ void __launch_bounds__(1024) cc_scan_kernel(const unsigned* __restrict__ sums, long long nchunk, unsigned* __restrict__ off, unsigned long long* st) {
-    __shared__ unsigned s[1024];
-    const int t = threadIdx.x;
-    unsigned run = 0;
-    for (long long base = 0; base < nchunk; base += 1024) {
-        const unsigned v = base + t < nchunk ? sums[base + t] : 0u;
-        s[t] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const unsigned x = t >= d ? s[t - d] : 0u;
-            __syncthreads();
-            s[t] += x;
-            __syncthreads();
-        }
-        if (base + t < nchunk) off[base + t] = run + s[t] - v;
-        run += s[1023];
-        __syncthreads();
-    }
-    if (t == 0) st[CC_K] = run;
+    roots = block_sum<4>(roots, wsum);
+    if (threadIdx.x == 0) sums[blockIdx.x] = roots;
 }
 
 // labels[r] := the number of roots below r, for every root r, in the chunks of cc_flatten
@@ -414,13 +389,6 @@ struct CcObject {
     hipStream_t stream = nullptr;
 };
 
-#define CC_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
-#define CC_LAUNCH(kernel, grid, block, ...)                                                     \
-    do {                                                                                        \
-        if (ndim == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel<3>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);    \
-    } while (0)
-
 // returns 0, 1 (refused: *err says why) or 2 (a HIP call failed); stats is filled whenever the counters were read
 int cc_build(const LsmHandle* h, CcWorkspace** workspace, double level, int side, const void* phi, CcObject** out, long long stats[4], const char** err) {
     const int ndim = h->grid.ndim;
@@ -448,22 +416,22 @@ int cc_build(const LsmHandle* h, CcWorkspace** workspace, double level, int side
 
     if (!*workspace) *workspace = new CcWorkspace();     // the handle's, created by its first call; the buffers only grow
     CcWorkspace& W = **workspace;
-    CC_HIP(W.parent.grow((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(parents)");
-    CC_HIP(W.sums.grow((size_t)a.nchunk * sizeof(unsigned)), "hipMalloc(chunk sums)");
-    CC_HIP(W.off.grow((size_t)a.nchunk * sizeof(unsigned)), "hipMalloc(chunk offsets)");
-    CC_HIP(W.st.grow((CC_NSTAT + 2) * sizeof(unsigned long long)), "hipMalloc(counters)");
-    CC_HIP(hipMemsetAsync(W.st.p, 0, (CC_NSTAT + 2) * sizeof(unsigned long long), stream), "components: memset");
+    MOD_HIP(W.parent.grow((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(parents)");
+    MOD_HIP(W.sums.grow((size_t)a.nchunk * sizeof(unsigned)), "hipMalloc(chunk sums)");
+    MOD_HIP(W.off.grow((size_t)a.nchunk * sizeof(unsigned)), "hipMalloc(chunk offsets)");
+    MOD_HIP(W.st.grow((CC_NSTAT + 2) * sizeof(unsigned long long)), "hipMalloc(counters)");
+    MOD_HIP(hipMemsetAsync(W.st.p, 0, (CC_NSTAT + 2) * sizeof(unsigned long long), stream), "components: memset");
     const unsigned tile_threads = ndim == 2 ? CcTile<2>::X * CcTile<2>::Y : CcTile<3>::X * CcTile<3>::Y * CcTile<3>::Z;
     const unsigned ntile = (unsigned)a.ntile, nchunk = (unsigned)a.nchunk;
 
-    CC_LAUNCH(cc_local_kernel, ntile, tile_threads, a, phi, W.parent.p, W.st.p);
-    CC_LAUNCH(cc_merge_kernel, ntile, tile_threads, a, W.parent.p, W.st.p);
+    LSM_LAUNCH_ND(ndim, cc_local_kernel, ntile, tile_threads, stream, a, phi, W.parent.p, W.st.p);
+    LSM_LAUNCH_ND(ndim, cc_merge_kernel, ntile, tile_threads, stream, a, W.parent.p, W.st.p);
     hipLaunchKernelGGL(cc_flatten_kernel, dim3(nchunk), dim3(256), 0, stream, a, W.parent.p, W.sums.p);
-    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(1024), 0, stream, (const unsigned*)W.sums.p, a.nchunk, W.off.p, W.st.p);
-    CC_HIP(hipGetLastError(), "components: launch failed");
+    chunk_scan<1, unsigned>(stream, {{{W.sums.p, W.off.p, 0}}}, a.nchunk, W.st.p + CC_K);
+    MOD_HIP(hipGetLastError(), "components: launch failed");
     unsigned long long st[CC_NSTAT] = {};
-    CC_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "components: counts");
-    CC_HIP(hipStreamSynchronize(stream), "components: device error");
+    MOD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "components: counts");
+    MOD_HIP(hipStreamSynchronize(stream), "components: device error");
     stats[0] = (long long)st[CC_K];
     stats[1] = (long long)st[CC_SET];
     stats[2] = (long long)st[CC_CROSS];
@@ -472,17 +440,17 @@ int cc_build(const LsmHandle* h, CcWorkspace** workspace, double level, int side
     const long long K = o->K = (long long)st[CC_K];
     if (K > a.nnode) { *err = "components: more roots than nodes"; return 2; }
 
-    CC_HIP(o->labels.alloc((size_t)a.nnode * sizeof(int)), "hipMalloc(labels)");
-    CC_HIP(o->nodes.alloc((size_t)std::max(K, 1LL) * sizeof(long long)), "hipMalloc(component sizes)");
-    CC_HIP(o->sums.alloc((size_t)std::max(K, 1LL) * ndim * sizeof(long long)), "hipMalloc(index sums)");
-    CC_HIP(o->bbox.alloc((size_t)std::max(K, 1LL) * 2 * ndim * sizeof(int)), "hipMalloc(bounding boxes)");
+    MOD_HIP(o->labels.alloc((size_t)a.nnode * sizeof(int)), "hipMalloc(labels)");
+    MOD_HIP(o->nodes.alloc((size_t)std::max(K, 1LL) * sizeof(long long)), "hipMalloc(component sizes)");
+    MOD_HIP(o->sums.alloc((size_t)std::max(K, 1LL) * ndim * sizeof(long long)), "hipMalloc(index sums)");
+    MOD_HIP(o->bbox.alloc((size_t)std::max(K, 1LL) * 2 * ndim * sizeof(int)), "hipMalloc(bounding boxes)");
     if (K) {
         hipLaunchKernelGGL(cc_init_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, K, ndim, o->nodes.p, o->sums.p, o->bbox.p);
         hipLaunchKernelGGL(cc_number_kernel, dim3(nchunk), dim3(256), 0, stream, a, (const unsigned*)W.parent.p, (const unsigned*)W.off.p, o->labels.p);
     }
-    CC_LAUNCH(cc_label_kernel, ntile, tile_threads, a, (const unsigned*)W.parent.p, o->labels.p, o->nodes.p, o->sums.p, o->bbox.p);
-    CC_HIP(hipGetLastError(), "components: launch failed");
-    CC_HIP(hipStreamSynchronize(stream), "components: device error");
+    LSM_LAUNCH_ND(ndim, cc_label_kernel, ntile, tile_threads, stream, a, (const unsigned*)W.parent.p, o->labels.p, o->nodes.p, o->sums.p, o->bbox.p);
+    MOD_HIP(hipGetLastError(), "components: launch failed");
+    MOD_HIP(hipStreamSynchronize(stream), "components: device error");
     *out = o.release();
     return 0;
 }
@@ -502,25 +470,23 @@ int cc_flip(CcObject* o, CcWorkspace* W, void* phi, const unsigned char* which, 
     *flipped = 0;
     if (!o->K) return 0;
     unsigned long long* cnt = W->st.p + CC_NSTAT;
-    CC_HIP(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), stream), "components flip: memset");
+    MOD_HIP(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), stream), "components flip: memset");
     const unsigned nblk = (unsigned)((a.nnode + 255) / 256);
-    CC_LAUNCH(cc_flip_count_kernel, nblk, 256, a, (const void*)phi, (const int*)o->labels.p, which, cnt);
+    LSM_LAUNCH_ND(ndim, cc_flip_count_kernel, nblk, 256, stream, a, (const void*)phi, (const int*)o->labels.p, which, cnt);
     unsigned long long c[2] = {};
-    CC_HIP(hipGetLastError(), "components flip: launch failed");
-    CC_HIP(hipMemcpyAsync(c, cnt, sizeof(c), hipMemcpyDeviceToHost, stream), "components flip: counts");
-    CC_HIP(hipStreamSynchronize(stream), "components flip: device error");
+    MOD_HIP(hipGetLastError(), "components flip: launch failed");
+    MOD_HIP(hipMemcpyAsync(c, cnt, sizeof(c), hipMemcpyDeviceToHost, stream), "components flip: counts");
+    MOD_HIP(hipStreamSynchronize(stream), "components flip: device error");
     if (c[CC_MISMATCH]) { *err = "components flip: phi has changed since the components were labelled (a flagged node is on the other side of level)"; return 1; }
     if (c[CC_FLAGGED]) {
-        CC_LAUNCH(cc_flip_write_kernel, nblk, 256, a, phi, (const int*)o->labels.p, which);
-        CC_HIP(hipGetLastError(), "components flip: launch failed");
-        CC_HIP(hipStreamSynchronize(stream), "components flip: device error");
+        LSM_LAUNCH_ND(ndim, cc_flip_write_kernel, nblk, 256, stream, a, phi, (const int*)o->labels.p, which);
+        MOD_HIP(hipGetLastError(), "components flip: launch failed");
+        MOD_HIP(hipStreamSynchronize(stream), "components flip: device error");
     }
     *flipped = (long long)c[CC_FLAGGED];
     return 0;
 }
 
 void cc_free(CcObject* o) { delete o; }
-#undef CC_LAUNCH
-#undef CC_HIP
 
 }  // namespace lsm

@@ -155,12 +155,6 @@ struct LsmComm {
 
 namespace {
 
-#define COMM_HIP(h, call)                                                                                   \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) return lsm_fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 inline size_t esize(const LsmHandle* h) { return h->dtype == LSM_DTYPE_F32 ? sizeof(float) : sizeof(double); }
 
 // geometry of the plane exchange: elements per padded plane, local plane range -> pointer
@@ -305,21 +299,21 @@ int local_enqueue(LsmHandle* h, LocalGroup* g, unsigned long long seq) {
     } guard;
     for (int r = 0; r < g->world; ++r) {
         LocalRank& me = g->ranks[r];
-        COMM_HIP(h, hipSetDevice(me.device));
-        COMM_HIP(h, hipStreamWaitEvent(me.stream, me.ev_ready[par], 0));
+        LSM_HIP(h, hipSetDevice(me.device));
+        LSM_HIP(h, hipStreamWaitEvent(me.stream, me.ev_ready[par], 0));
         if (me.dn >= 0) {
             LocalRank& n = g->ranks[me.dn];
             if (n.msg.n_send_up != me.msg.n_recv_dn) return lsm_fail(h, LSM_ERR_COMM, "exchange: message sizes of neighbouring ranks differ");
-            COMM_HIP(h, hipStreamWaitEvent(me.stream, n.ev_ready[par], 0));
-            if (me.msg.n_recv_dn) COMM_HIP(h, hipMemcpyAsync(me.msg.recv_dn, n.msg.send_up, me.msg.n_recv_dn, hipMemcpyDefault, me.stream));
+            LSM_HIP(h, hipStreamWaitEvent(me.stream, n.ev_ready[par], 0));
+            if (me.msg.n_recv_dn) LSM_HIP(h, hipMemcpyAsync(me.msg.recv_dn, n.msg.send_up, me.msg.n_recv_dn, hipMemcpyDefault, me.stream));
         }
         if (me.up >= 0) {
             LocalRank& n = g->ranks[me.up];
             if (n.msg.n_send_dn != me.msg.n_recv_up) return lsm_fail(h, LSM_ERR_COMM, "exchange: message sizes of neighbouring ranks differ");
-            COMM_HIP(h, hipStreamWaitEvent(me.stream, n.ev_ready[par], 0));
-            if (me.msg.n_recv_up) COMM_HIP(h, hipMemcpyAsync(me.msg.recv_up, n.msg.send_dn, me.msg.n_recv_up, hipMemcpyDefault, me.stream));
+            LSM_HIP(h, hipStreamWaitEvent(me.stream, n.ev_ready[par], 0));
+            if (me.msg.n_recv_up) LSM_HIP(h, hipMemcpyAsync(me.msg.recv_up, n.msg.send_dn, me.msg.n_recv_up, hipMemcpyDefault, me.stream));
         }
-        COMM_HIP(h, hipEventRecord(me.ev_done[par], me.stream));
+        LSM_HIP(h, hipEventRecord(me.ev_done[par], me.stream));
     }
     return LSM_OK;
 }
@@ -347,13 +341,13 @@ int exchange_start(LsmHandle* h, const Msg& m, ncclDataType_t ty, size_t tysize,
     if (c->pending) return lsm_fail(h, LSM_ERR_INVALID, std::string(what) + ": the previous exchange has not been waited for (lsm_halo_wait)");
     const unsigned long long seq = ++c->seq;
     const int par = (int)(seq & 1);
-    COMM_HIP(h, hipSetDevice(h->device));
-    COMM_HIP(h, hipEventRecord(c->ev_ready[par], h->stream));
+    LSM_HIP(h, hipSetDevice(h->device));
+    LSM_HIP(h, hipEventRecord(c->ev_ready[par], h->stream));
     c->pending = true;
     if (c->transport == LSM_COMM_RCCL) {
-        if (c->up < 0 && c->dn < 0) { COMM_HIP(h, hipEventRecord(c->ev_done[par], h->stream)); return LSM_OK; }
+        if (c->up < 0 && c->dn < 0) { LSM_HIP(h, hipEventRecord(c->ev_done[par], h->stream)); return LSM_OK; }
         Rccl& r = rccl();
-        COMM_HIP(h, hipStreamWaitEvent(c->stream, c->ev_ready[par], 0));
+        LSM_HIP(h, hipStreamWaitEvent(c->stream, c->ev_ready[par], 0));
         // op order [send up, recv dn, send dn, recv up]: the messages of one pair of ranks match in posting order, which
         // matters when up == dn (two ranks on a periodic ring).  A failure inside the group closes it, drops the exchange
         // and fails the communicator: nothing later waits on an event that was never recorded.
@@ -371,7 +365,7 @@ int exchange_start(LsmHandle* h, const Msg& m, ncclDataType_t ty, size_t tysize,
             c->failed.store(true);
             return lsm_fail(h, LSM_ERR_COMM, std::string(what) + ": RCCL: " + r.GetErrorString(nr));
         }
-        COMM_HIP(h, hipEventRecord(c->ev_done[par], c->stream));
+        LSM_HIP(h, hipEventRecord(c->ev_done[par], c->stream));
         return LSM_OK;
     }
     // LOCAL: post; the last rank to post enqueues the copies of the whole group
@@ -398,7 +392,7 @@ int exchange_wait(LsmHandle* h, const char* what) {
     if (!c->pending) return c->failed.load() ? comm_failed(h, c, what) : LSM_OK;
     c->pending = false;
     const int par = (int)(c->seq & 1);
-    COMM_HIP(h, hipSetDevice(h->device));
+    LSM_HIP(h, hipSetDevice(h->device));
     if (c->transport == LSM_COMM_LOCAL) {
         LocalGroup* g = c->grp;
         {
@@ -407,12 +401,12 @@ int exchange_wait(LsmHandle* h, const char* what) {
             if (rc) return rc;
         }
         // the neighbours' events belong to the group: valid even if the neighbour has been destroyed since
-        if (c->dn >= 0) COMM_HIP(h, hipStreamWaitEvent(h->stream, g->ranks[c->dn].ev_done[par], 0));
-        if (c->up >= 0) COMM_HIP(h, hipStreamWaitEvent(h->stream, g->ranks[c->up].ev_done[par], 0));
+        if (c->dn >= 0) LSM_HIP(h, hipStreamWaitEvent(h->stream, g->ranks[c->dn].ev_done[par], 0));
+        if (c->up >= 0) LSM_HIP(h, hipStreamWaitEvent(h->stream, g->ranks[c->up].ev_done[par], 0));
     } else if (c->failed.load()) {
         return comm_failed(h, c, what);
     }
-    COMM_HIP(h, hipStreamWaitEvent(h->stream, c->ev_done[par], 0));
+    LSM_HIP(h, hipStreamWaitEvent(h->stream, c->ev_done[par], 0));
     return LSM_OK;
 }
 
@@ -695,15 +689,15 @@ int lsm_allreduce_dt(LsmHandle* h, double* dt) {
     if (c->transport == LSM_COMM_RCCL) {
         // NaN encoded as -1 (any valid or invalid Δt is >= 0 or NaN; -Inf cannot occur): MIN then makes it win
         *c->h_dt = *dt != *dt ? -1.0 : *dt;
-        COMM_HIP(h, hipSetDevice(h->device));
+        LSM_HIP(h, hipSetDevice(h->device));
         // on the handle's stream, behind the stages of the previous step: one collective in flight per rank at a time
-        COMM_HIP(h, hipMemcpyAsync(c->d_dt, c->h_dt, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        LSM_HIP(h, hipMemcpyAsync(c->d_dt, c->h_dt, sizeof(double), hipMemcpyHostToDevice, h->stream));
         const ncclResult_t nr = rccl().AllReduce(c->d_dt, c->d_dt, 1, ncclDouble, ncclMin, c->nccl, h->stream);
         if (nr != ncclSuccess) {
             c->failed.store(true);
             return lsm_fail(h, LSM_ERR_COMM, std::string("lsm_allreduce_dt: RCCL: ") + rccl().GetErrorString(nr));
         }
-        COMM_HIP(h, hipMemcpyAsync(c->h_dt, c->d_dt, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        LSM_HIP(h, hipMemcpyAsync(c->h_dt, c->d_dt, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         const int rc = stream_wait(h, c, "lsm_allreduce_dt");
         if (rc) return rc;
         *dt = *c->h_dt < 0 ? __builtin_nan("") : *c->h_dt;
@@ -752,9 +746,9 @@ int lsm_band_overlap_config(LsmHandle* h, int64_t overlap) {
         return lsm_fail(h, LSM_ERR_INVALID, "lsm_band_overlap_config: the slab must hold `overlap` planes of each neighbour and at least as many of its own");
     if (c->wrap_up || c->wrap_dn) return lsm_fail(h, LSM_ERR_INVALID, "lsm_band_overlap_config: PeriodicBC is not supported on a NarrowBandMeshField");
     if (!c->d_nz_total || !c->h_nz_total) {
-        COMM_HIP(h, hipSetDevice(h->device));
-        COMM_HIP(h, c->d_nz_total.alloc(4 * sizeof(unsigned)));
-        COMM_HIP(h, c->h_nz_total.alloc(4 * sizeof(unsigned)));
+        LSM_HIP(h, hipSetDevice(h->device));
+        LSM_HIP(h, c->d_nz_total.alloc(4 * sizeof(unsigned)));
+        LSM_HIP(h, c->h_nz_total.alloc(4 * sizeof(unsigned)));
     }
     c->band_W = (int)overlap;
     for (int k = 0; k < 4; ++k) c->n_idx[k] = 0;
@@ -778,16 +772,16 @@ int lsm_band_overlap_mask(LsmHandle* h, void* mask) {
     if (rc) return rc;
     // band nodes of the four plane ranges, in index order
     const unsigned nchunks = (unsigned)((nb + NZ_CHUNK - 1) / NZ_CHUNK);
-    COMM_HIP(h, hipSetDevice(h->device));
-    if (c->d_nz_counts.cap < (size_t)4 * nchunks * sizeof(unsigned)) COMM_HIP(h, c->d_nz_counts.alloc((size_t)4 * nchunks * sizeof(unsigned)));
-    COMM_HIP(h, hipMemsetAsync(c->d_nz_total, 0, 4 * sizeof(unsigned), h->stream));
+    LSM_HIP(h, hipSetDevice(h->device));
+    if (c->d_nz_counts.cap < (size_t)4 * nchunks * sizeof(unsigned)) LSM_HIP(h, c->d_nz_counts.alloc((size_t)4 * nchunks * sizeof(unsigned)));
+    LSM_HIP(h, hipMemsetAsync(c->d_nz_total, 0, 4 * sizeof(unsigned), h->stream));
     for (int k = 0; k < 4; ++k) {
         if (first[k] < 0) continue;
         const unsigned char* base = (const unsigned char*)p.at(mask, first[k]);
         hipLaunchKernelGGL(nz_count_kernel, dim3(nchunks), dim3(256), 0, h->stream, base, nb, c->d_nz_counts + (size_t)k * nchunks);
         hipLaunchKernelGGL(nz_scan_kernel, dim3(1), dim3(1024), 0, h->stream, c->d_nz_counts + (size_t)k * nchunks, nchunks, c->d_nz_total + k);
     }
-    COMM_HIP(h, hipMemcpyAsync(c->h_nz_total, c->d_nz_total, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    LSM_HIP(h, hipMemcpyAsync(c->h_nz_total, c->d_nz_total, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     rc = stream_wait(h, c, "lsm_band_overlap_mask");      // behind the mask exchange: a peer that never posts must not hang the host
     if (rc) return rc;
     const size_t es = esize(h);
@@ -796,15 +790,15 @@ int lsm_band_overlap_mask(LsmHandle* h, void* mask) {
         if (!c->n_idx[k]) continue;
         if (c->d_idx[k].cap < (size_t)c->n_idx[k] * sizeof(unsigned) || c->d_pack[k].cap < (size_t)c->n_idx[k] * sizeof(double)) {
             const size_t cap = (size_t)c->n_idx[k] + c->n_idx[k] / 2 + 1024;
-            COMM_HIP(h, c->d_idx[k].alloc(cap * sizeof(unsigned)));
-            COMM_HIP(h, c->d_pack[k].alloc(cap * sizeof(double)));
+            LSM_HIP(h, c->d_idx[k].alloc(cap * sizeof(unsigned)));
+            LSM_HIP(h, c->d_pack[k].alloc(cap * sizeof(double)));
         }
         const unsigned char* base = (const unsigned char*)p.at(mask, first[k]);
         hipLaunchKernelGGL(nz_write_kernel, dim3(nchunks), dim3(256), 0, h->stream, base, nb, c->d_nz_counts + (size_t)k * nchunks, c->d_idx[k],
                            c->d_idx[k].cap / sizeof(unsigned));
     }
     (void)es;
-    COMM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -816,7 +810,7 @@ int lsm_band_overlap_values(LsmHandle* h, void* field) {
     const Planes p = planes_of(h, es);
     int first[4];
     band_ranges(h, c, first);
-    COMM_HIP(h, hipSetDevice(h->device));
+    LSM_HIP(h, hipSetDevice(h->device));
     for (int k : {0, 2})      // pack what this rank sends
         if (first[k] >= 0 && c->n_idx[k])
             hipLaunchKernelGGL(pack_kernel, dim3((c->n_idx[k] + 255u) / 256u), dim3(256), 0, h->stream, (const char*)p.at(field, first[k]), c->d_idx[k],
@@ -833,7 +827,7 @@ int lsm_band_overlap_values(LsmHandle* h, void* field) {
         if (first[k] >= 0 && c->n_idx[k])
             hipLaunchKernelGGL(unpack_kernel, dim3((c->n_idx[k] + 255u) / 256u), dim3(256), 0, h->stream, (char*)p.at(field, first[k]), c->d_idx[k],
                                c->n_idx[k], (int)es, c->d_pack[k]);
-    COMM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 

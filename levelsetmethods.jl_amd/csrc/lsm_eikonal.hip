@@ -284,13 +284,6 @@ struct EikonalWorkspace {
 };
 void eikonal_workspace_free(EikonalWorkspace* w) { delete w; }
 
-#define EK_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
-#define EK_LAUNCH(kernel, grid, block, ...)                                                     \
-    do {                                                                                        \
-        if (ndim == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel<3>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);    \
-    } while (0)
-
 // returns 0, 1 (invalid: *err says why), 2 (a HIP call failed) or 3 (max_iters launches did not empty the list); ϕ is written
 // only on 0
 int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double h[3], void* phi, int f32, const double* speed,
@@ -317,22 +310,22 @@ int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long 
 
     if (!*workspace) *workspace = new EikonalWorkspace();   // the handle's, created by its first call; the buffers only grow
     EikonalWorkspace& W = **workspace;
-    EK_HIP(W.T.grow((size_t)a.nnode * sizeof(double)), "hipMalloc(arrival times)");
-    EK_HIP(W.frozen.grow((size_t)a.nnode), "hipMalloc(frozen mask)");
-    EK_HIP(W.next.grow((size_t)a.ntile), "hipMalloc(tile flags)");
-    EK_HIP(W.list.grow((size_t)a.ntile * sizeof(int)), "hipMalloc(tile list)");
-    EK_HIP(W.count.grow(sizeof(unsigned)), "hipMalloc(list length)");
-    EK_HIP(W.st.grow(EK_NSTAT * sizeof(unsigned long long)), "hipMalloc(statistics)");
-    EK_HIP(hipMemsetAsync(W.st.p, 0, EK_NSTAT * sizeof(unsigned long long), stream), "eikonal: memset");
-    EK_HIP(hipMemsetAsync(W.next.p, 0, (size_t)a.ntile, stream), "eikonal: memset");
+    MOD_HIP(W.T.grow((size_t)a.nnode * sizeof(double)), "hipMalloc(arrival times)");
+    MOD_HIP(W.frozen.grow((size_t)a.nnode), "hipMalloc(frozen mask)");
+    MOD_HIP(W.next.grow((size_t)a.ntile), "hipMalloc(tile flags)");
+    MOD_HIP(W.list.grow((size_t)a.ntile * sizeof(int)), "hipMalloc(tile list)");
+    MOD_HIP(W.count.grow(sizeof(unsigned)), "hipMalloc(list length)");
+    MOD_HIP(W.st.grow(EK_NSTAT * sizeof(unsigned long long)), "hipMalloc(statistics)");
+    MOD_HIP(hipMemsetAsync(W.st.p, 0, EK_NSTAT * sizeof(unsigned long long), stream), "eikonal: memset");
+    MOD_HIP(hipMemsetAsync(W.next.p, 0, (size_t)a.ntile, stream), "eikonal: memset");
     const unsigned nblk = (unsigned)((a.nnode + 255) / 256), tblk = (unsigned)((a.ntile + 255) / 256);
     const unsigned tile_threads = ndim == 2 ? EkTile<2>::X * EkTile<2>::Y : EkTile<3>::X * EkTile<3>::Y * EkTile<3>::Z;
 
-    EK_LAUNCH(ek_seed_kernel, nblk, 256, a, (const void*)phi, f32, W.T.p, W.frozen.p, W.st.p);
+    LSM_LAUNCH_ND(ndim, ek_seed_kernel, nblk, 256, stream, a, (const void*)phi, f32, W.T.p, W.frozen.p, W.st.p);
     unsigned long long st[EK_NSTAT] = {};
-    EK_HIP(hipGetLastError(), "eikonal: launch failed");
-    EK_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "eikonal: validation");
-    EK_HIP(hipStreamSynchronize(stream), "eikonal: validation");
+    MOD_HIP(hipGetLastError(), "eikonal: launch failed");
+    MOD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "eikonal: validation");
+    MOD_HIP(hipStreamSynchronize(stream), "eikonal: validation");
     // what the data is refused for: stats = {-(reason), offending nodes, 0, 0} (include/lsm.h)
     const char* why[3] = {"eikonal: phi must be finite", "eikonal: the speed must be finite and positive at every node",
                           "eikonal: phi has no interface (no node is zero or next to a change of sign)"};
@@ -345,17 +338,17 @@ int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long 
         return 1;
     }
 
-    EK_LAUNCH(ek_mark_kernel, nblk, 256, a, (const unsigned char*)W.frozen.p, W.next.p);
+    LSM_LAUNCH_ND(ndim, ek_mark_kernel, nblk, 256, stream, a, (const unsigned char*)W.frozen.p, W.next.p);
     long long iters = 0, visits = 0;
     unsigned nlist = 0;
     for (;;) {
-        EK_HIP(hipMemsetAsync(W.count.p, 0, sizeof(unsigned), stream), "eikonal: memset");
+        MOD_HIP(hipMemsetAsync(W.count.p, 0, sizeof(unsigned), stream), "eikonal: memset");
         hipLaunchKernelGGL(ek_compact_kernel, dim3(tblk), dim3(256), 0, stream, W.next.p, a.ntile, W.list.p, W.count.p);
-        EK_HIP(hipMemcpyAsync(&nlist, W.count.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream), "eikonal: list length");
-        EK_HIP(hipStreamSynchronize(stream), "eikonal: device error");
+        MOD_HIP(hipMemcpyAsync(&nlist, W.count.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream), "eikonal: list length");
+        MOD_HIP(hipStreamSynchronize(stream), "eikonal: device error");
         if (nlist == 0 || iters >= max_iters) break;
         if ((long long)nlist > a.ntile) { *err = "eikonal: the tile list is longer than the grid has tiles"; return 2; }
-        EK_LAUNCH(ek_tile_kernel, nlist, tile_threads, a, W.T.p, (const unsigned char*)W.frozen.p, (const int*)W.list.p, nlist, W.next.p);
+        LSM_LAUNCH_ND(ndim, ek_tile_kernel, nlist, tile_threads, stream, a, W.T.p, (const unsigned char*)W.frozen.p, (const int*)W.list.p, nlist, W.next.p);
         ++iters;
         visits += nlist;
     }
@@ -364,14 +357,12 @@ int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long 
     stats[2] = visits;
     stats[3] = 0;
     if (nlist != 0) { *err = "eikonal: the active list did not empty within max_iters outer iterations"; return 3; }
-    EK_LAUNCH(ek_final_kernel, nblk, 256, a, (const double*)W.T.p, phi, f32, W.st.p);
-    EK_HIP(hipGetLastError(), "eikonal: launch failed");
-    EK_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "eikonal: statistics");
-    EK_HIP(hipStreamSynchronize(stream), "eikonal: device error");
+    LSM_LAUNCH_ND(ndim, ek_final_kernel, nblk, 256, stream, a, (const double*)W.T.p, phi, f32, W.st.p);
+    MOD_HIP(hipGetLastError(), "eikonal: launch failed");
+    MOD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "eikonal: statistics");
+    MOD_HIP(hipStreamSynchronize(stream), "eikonal: device error");
     stats[3] = (long long)st[EK_CLAMPED];
     return 0;
 }
-#undef EK_LAUNCH
-#undef EK_HIP
 
 }  // namespace lsm

@@ -490,8 +490,8 @@ static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double lev
         nd += RR + mg_ncells(N, lev[l]) + (size_t)N * (size_t)lev[l].nn * (size_t)(3 + (l ? 1 : 4));
         nb += (size_t)lev[l].nn;
     }
-    MG_HIP(h, o.buf.alloc(nd * sizeof(double)));
-    MG_HIP(h, o.fx.alloc(nb));
+    LSM_HIP(h, o.buf.alloc(nd * sizeof(double)));
+    LSM_HIP(h, o.fx.alloc(nb));
     hipStream_t s = h->stream;
     const int ra = mg_alloc_scalars(h, o, ES_NSTAT, s);
     if (ra != LSM_OK) return ra;
@@ -516,16 +516,16 @@ static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double lev
         lev[l].E = ecell[l]; lev[l].D = dg[l]; lev[l].K = kd[l]; lev[l].mask = fxl[l];
         es_k0(N, lev[l].h, lam, mu, o.k0[l]);       // o.k0 outlives the copy: it belongs to the object
         lev[l].om = std::min(ES_OMEGA, ES_SAFE / es_symbol_lambda(N, o.k0[l]));
-        MG_HIP(h, hipMemcpyAsync(kd[l], o.k0[l].data(), RR * sizeof(double), hipMemcpyHostToDevice, s));
+        LSM_HIP(h, hipMemcpyAsync(kd[l], o.k0[l].data(), RR * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    if (fixed) MG_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
-    else MG_HIP(h, hipMemsetAsync(fxl[0], 0, (size_t)nn, s));
+    if (fixed) LSM_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
+    else LSM_HIP(h, hipMemsetAsync(fxl[0], 0, (size_t)nn, s));
     MG_LAUNCH(N, es_setup_kernel, dim3(mg_blocks(nn)), MG_THREADS, s, lev[0], o.F, e_cells ? (const void*)nullptr : phi, level, e_in, e_out, hmin, e_cells,
               ecell[0], o.cnt.p);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     unsigned long long c[ES_NSTAT] = {};
-    MG_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
-    MG_HIP(h, hipStreamSynchronize(s));
+    LSM_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
+    LSM_HIP(h, hipStreamSynchronize(s));
     o.nfixed = 0;
     int unfixed = -1;
     for (int i = N - 1; i >= 0; --i) {
@@ -546,8 +546,8 @@ static int es_create(LsmHandle* h, ElasticObject& o, const void* phi, double lev
         MG_LAUNCH(N, es_coarsen_kernel, dim3(mg_blocks(lev[l].nn)), MG_THREADS, s, lev[l - 1], lev[l], o.co[l - 1][0], o.co[l - 1][1], o.co[l - 1][2], ecell[l],
                   fxl[l]);
     for (int l = 0; l < nl; ++l) MG_LAUNCH(N, es_diag_kernel, dim3(mg_blocks(lev[l].nn)), MG_THREADS, s, lev[l], dg[l]);
-    MG_HIP(h, hipGetLastError());
-    MG_HIP(h, hipStreamSynchronize(s));
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipStreamSynchronize(s));
     o.lev = lev;
     o.V.z = o.precond == LSM_PRECOND_JACOBI ? o.xa[0] : o.xb[0];
     if (stats) { stats[0] = nl; stats[1] = o.nfree; stats[2] = o.nfixed; stats[3] = 0; }
@@ -599,7 +599,7 @@ int lsm_elastic_apply(LsmElastic* s, const double* x, double* y) {
     if (!x || !y || x == y) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_apply: x and y must be two arrays");
     const EsLevel& L = s->o->lev[0];
     MG_LAUNCH(s->o->N, es_apply_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, x, y);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -608,7 +608,7 @@ int lsm_elastic_cells(LsmElastic* s, double* e_out_cells) {
     if (!e_out_cells) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_cells: null argument");
     const EsLevel& L = s->o->lev[0];
     const size_t m = mg_ncells(s->o->N, L);
-    MG_HIP(s->h, hipMemcpyAsync(e_out_cells, L.E, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
+    LSM_HIP(s->h, hipMemcpyAsync(e_out_cells, L.E, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
     return LSM_OK;
 }
 
@@ -627,7 +627,7 @@ int lsm_elastic_energy(LsmElastic* s, const void* u0, const void* u1, const void
         return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_energy: the components of u and e_out must be distinct fields");
     const EsLevel& L = s->o->lev[0];
     MG_LAUNCH(s->o->N, es_energy_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, s->o->F, U, e_out);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -639,9 +639,9 @@ int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const
     const EsLevel& L = o.lev[0];
     hipStream_t st = s->h->stream;
     MG_LAUNCH(o.N, es_compliance_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, f, U, o.partial.p, o.st.p);
-    MG_HIP(s->h, hipGetLastError());
-    MG_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
-    MG_HIP(s->h, hipStreamSynchronize(st));
+    LSM_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+    LSM_HIP(s->h, hipStreamSynchronize(st));
     double vol = 1.0;
     for (int d = 0; d < o.N; ++d) vol *= L.h[d];
     *out = vol * o.h_st.p->out;
@@ -666,7 +666,7 @@ int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* 
     const int nt = N * L.nn;
     MG_LAUNCH(N, es_load_kernel, dim3(nb), MG_THREADS, st, L, o.F, o.V, U);
     MG_LAUNCH(N, es_init_kernel, dim3(nb), MG_THREADS, st, L, o.V, (const double*)o.V.x, f, o.V.r, o.V.z, jac);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     const int r1 = mg_iterate(h, o, max_iters, st, [&](int) {
         if (!jac) mg_vcycle(o, o.V.r, st);
         hipLaunchKernelGGL(es_dir_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, nt, o.V);
@@ -678,8 +678,8 @@ int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* 
     const int r2 = mg_report(h, o, "lsm_elastic_solve", rtol, iters_out, relres_out);
     if (r2 != LSM_OK) return r2;
     MG_LAUNCH(N, es_store_kernel, dim3(nb), MG_THREADS, st, L, o.F, (const double*)o.V.x, U);
-    MG_HIP(h, hipGetLastError());
-    MG_HIP(h, hipStreamSynchronize(st));
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipStreamSynchronize(st));
     return LSM_OK;
 }
 
@@ -1115,27 +1115,27 @@ int lsm_elastic_modes_create(LsmElastic* s, const void* phi, double level, doubl
         hmin = std::min(hmin, L.h[d]);
     }
     const size_t nblk = (size_t)6 * m * (size_t)o->nt;
-    MG_HIP(h, o->buf.alloc((nblk + (size_t)L.nn + ncell + EM_OUT_N + 6 * EM_MAXM * EM_MAXM) * sizeof(double)));
-    MG_HIP(h, o->partial.alloc((size_t)std::max(32 * EM_GRAMB * EM_MAXT, 2 * EM_MAXM * MG_MAXB) * sizeof(double)));
-    MG_HIP(h, o->tickets.alloc(32 * sizeof(unsigned)));
-    MG_HIP(h, o->cnt.alloc(2 * sizeof(unsigned long long)));
-    MG_HIP(h, o->h_out.alloc(EM_OUT_N * sizeof(double)));
-    MG_HIP(h, o->h_c.alloc(6 * EM_MAXM * EM_MAXM * sizeof(double)));
+    LSM_HIP(h, o->buf.alloc((nblk + (size_t)L.nn + ncell + EM_OUT_N + 6 * EM_MAXM * EM_MAXM) * sizeof(double)));
+    LSM_HIP(h, o->partial.alloc((size_t)std::max(32 * EM_GRAMB * EM_MAXT, 2 * EM_MAXM * MG_MAXB) * sizeof(double)));
+    LSM_HIP(h, o->tickets.alloc(32 * sizeof(unsigned)));
+    LSM_HIP(h, o->cnt.alloc(2 * sizeof(unsigned long long)));
+    LSM_HIP(h, o->h_out.alloc(EM_OUT_N * sizeof(double)));
+    LSM_HIP(h, o->h_c.alloc(6 * EM_MAXM * EM_MAXM * sizeof(double)));
     o->B = EmBlocks{o->buf.p, o->nt, m, 0, 0};
     o->Mn = o->buf.p + nblk;
     o->rho = o->Mn + L.nn;
     o->gout = o->rho + ncell;
     o->cdev = o->gout + EM_OUT_N;
     hipStream_t st = h->stream;
-    MG_HIP(h, hipMemsetAsync(o->tickets.p, 0, 32 * sizeof(unsigned), st));
-    MG_HIP(h, hipMemsetAsync(o->cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    LSM_HIP(h, hipMemsetAsync(o->tickets.p, 0, 32 * sizeof(unsigned), st));
+    LSM_HIP(h, hipMemsetAsync(o->cnt.p, 0, 2 * sizeof(unsigned long long), st));
     MG_LAUNCH(N, em_rho_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, eo.F, rho_cells ? (const void*)nullptr : phi, level, rho_in, rho_out, hmin, rho_cells,
               o->rho, o->cnt.p);
     MG_LAUNCH(N, em_mass_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, (const double*)o->rho, o->Mn);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     unsigned long long c[2] = {0, 0};
-    MG_HIP(h, hipMemcpyAsync(c, o->cnt.p, sizeof(c), hipMemcpyDeviceToHost, st));
-    MG_HIP(h, hipStreamSynchronize(st));
+    LSM_HIP(h, hipMemcpyAsync(c, o->cnt.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    LSM_HIP(h, hipStreamSynchronize(st));
     if (c[0]) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_create: phi must be finite");
     if (c[1]) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_create: the cell densities must be finite and positive");
     *out = new LsmModes{s, guard.release()};
@@ -1146,7 +1146,7 @@ int lsm_elastic_modes_mass(LsmModes* md, double* node_mass) {
     if (!md) return LSM_ERR_INVALID;
     LsmHandle* h = md->e->h;
     if (!node_mass) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_mass: null argument");
-    MG_HIP(h, hipMemcpyAsync(node_mass, md->o->Mn, (size_t)md->e->o->lev[0].nn * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    LSM_HIP(h, hipMemcpyAsync(node_mass, md->o->Mn, (size_t)md->e->o->lev[0].nn * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return LSM_OK;
 }
 
@@ -1165,10 +1165,10 @@ static int em_gram_rr(LsmHandle* h, ElasticObject& eo, ModesObject& o, int na, i
     B.na = na; B.np = np;
     const unsigned nb = std::min<unsigned>(mg_blocks(o.nt), EM_GRAMB);
     hipLaunchKernelGGL(em_gram_kernel, dim3(nb, T), dim3(MG_THREADS), 0, st, B, eo.lev[0].nn, tiles, (const double*)o.Mn, o.partial.p, o.tickets.p, o.gout + EM_OUT_GRAM);
-    MG_HIP(h, hipGetLastError());
-    MG_HIP(h, hipMemcpyAsync(o.h_out.p, o.gout, (size_t)T * 32 * sizeof(double), hipMemcpyDeviceToHost, st));
-    MG_HIP(h, hipMemcpyAsync(eo.h_st, eo.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
-    MG_HIP(h, hipStreamSynchronize(st));
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipMemcpyAsync(o.h_out.p, o.gout, (size_t)T * 32 * sizeof(double), hipMemcpyDeviceToHost, st));
+    LSM_HIP(h, hipMemcpyAsync(eo.h_st, eo.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+    LSM_HIP(h, hipStreamSynchronize(st));
     std::vector<double> GA((size_t)q * q, 0.0), GM((size_t)q * q, 0.0), C;
     for (int t = 0; t < T; ++t)
         for (int a = 0; a < EM_TILE; ++a)
@@ -1192,9 +1192,9 @@ static int em_gram_rr(LsmHandle* h, ElasticObject& eo, ModesObject& o, int na, i
         if (b > 0)
             for (int j = 0; j < na; ++j) hc[(3 * EM_MAXM + row) * EM_MAXM + j] = C[(size_t)c * m + act[j]];
     }
-    MG_HIP(h, hipMemcpyAsync(o.cdev, hc, 6 * EM_MAXM * EM_MAXM * sizeof(double), hipMemcpyHostToDevice, st));
+    LSM_HIP(h, hipMemcpyAsync(o.cdev, hc, 6 * EM_MAXM * EM_MAXM * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(em_update_kernel, dim3(mg_blocks(o.nt), 2), dim3(MG_THREADS), 0, st, B, (const double*)o.cdev);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1217,10 +1217,10 @@ int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max
     double* const AX = X + (size_t)3 * m * nt;
     double* const AW = X + (size_t)4 * m * nt;
     o.solved = 0;
-    MG_HIP(h, hipMemsetAsync(eo.st, 0, sizeof(MgState), st));     // status MG_RUN: the V-cycle's kernels run
+    LSM_HIP(h, hipMemsetAsync(eo.st, 0, sizeof(MgState), st));     // status MG_RUN: the V-cycle's kernels run
     hipLaunchKernelGGL(em_init_kernel, dim3(mg_blocks((long long)m * nt)), dim3(MG_THREADS), 0, st, L, N, (long long)m * nt, x0, X);
     MG_LAUNCH(N, em_apply_kernel, dim3(nb, m), MG_THREADS, st, L, (const double*)X, AX);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     int dropped = 0, rr = 0, it = 0, na = 0, np = 0, act[EM_MAXM], why = 0;
     long long applies = 0;
     double rel[EM_MAXM];
@@ -1233,9 +1233,9 @@ int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max
         EmLam lam;
         for (int k = 0; k < EM_MAXM; ++k) lam.v[k] = o.lam[k];
         hipLaunchKernelGGL(em_resid_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, o.B, L.nn, lam, (const double*)o.Mn, o.partial.p, o.tickets.p + 31, o.gout + EM_OUT_NORM);
-        MG_HIP(h, hipGetLastError());
-        MG_HIP(h, hipMemcpyAsync(o.h_out.p + EM_OUT_NORM, o.gout + EM_OUT_NORM, 2 * EM_MAXM * sizeof(double), hipMemcpyDeviceToHost, st));
-        MG_HIP(h, hipStreamSynchronize(st));
+        LSM_HIP(h, hipGetLastError());
+        LSM_HIP(h, hipMemcpyAsync(o.h_out.p + EM_OUT_NORM, o.gout + EM_OUT_NORM, 2 * EM_MAXM * sizeof(double), hipMemcpyDeviceToHost, st));
+        LSM_HIP(h, hipStreamSynchronize(st));
         na = 0;
         for (int k = 0; k < m; ++k) {
             const double rn = std::sqrt(o.h_out.p[EM_OUT_NORM + 2 * k]), mn = std::sqrt(o.h_out.p[EM_OUT_NORM + 2 * k + 1]);
@@ -1255,14 +1255,14 @@ int lsm_elastic_modes_solve(LsmModes* md, const double* x0, double rtol, int max
         }
         applies += na;
         MG_LAUNCH(N, em_apply_kernel, dim3(nb, na), MG_THREADS, st, L, (const double*)W, AW);
-        MG_HIP(h, hipGetLastError());
+        LSM_HIP(h, hipGetLastError());
         const int r1 = em_gram_rr(h, eo, o, na, np, act, st, dropped, rr);
         if (r1 != LSM_OK) return r1;
         if (rr) { why = 2; break; }
         np = na;
         ++it;
     }
-    MG_HIP(h, hipStreamSynchronize(st));
+    LSM_HIP(h, hipStreamSynchronize(st));
     for (int k = 0; k < m; ++k) {
         if (lambda) lambda[k] = o.lam[k];
         if (relres) relres[k] = rel[k];
@@ -1285,7 +1285,7 @@ int lsm_elastic_modes_vectors(LsmModes* md, double* x_out) {
     if (!md) return LSM_ERR_INVALID;
     LsmHandle* h = md->e->h;
     if (!x_out || !md->o->solved) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_vectors: null argument, or no solve has run");
-    MG_HIP(h, hipMemcpyAsync(x_out, md->o->B.base, (size_t)md->o->m * (size_t)md->o->nt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    LSM_HIP(h, hipMemcpyAsync(x_out, md->o->B.base, (size_t)md->o->m * (size_t)md->o->nt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return LSM_OK;
 }
 
@@ -1305,7 +1305,7 @@ int lsm_elastic_modes_store(LsmModes* md, int k, void* u0, void* u1, void* u2) {
     if (!es_fields(eo.N, u0, u1, u2, U)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_modes_store: the N distinct fields of u must be given");
     const EsLevel& L = eo.lev[0];
     MG_LAUNCH(eo.N, em_store_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), U);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1318,7 +1318,7 @@ int lsm_elastic_modes_sensitivity(LsmModes* md, int k, void* g_out) {
     const EsLevel& L = eo.lev[0];
     MG_LAUNCH(eo.N, em_sens_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), o.lam[k],
               (const double*)o.rho, g_out);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1619,7 +1619,7 @@ int lsm_elastic_stress_cells(LsmElastic* s, const void* u0, const void* u1, cons
     const EsLevel& L = o.lev[0];
     const int nc = (int)mg_ncells(o.N, L);
     MG_LAUNCH(o.N, ss_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, s->h->stream, L, o.F, U, ss_mat(o), what, nc, out);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1643,7 +1643,7 @@ int lsm_elastic_stress(LsmElastic* s, const void* u0, const void* u1, const void
     double* cell = o.xa[0];      // ≤ 6·(cells) of the 6·N·nn scratch doubles
     MG_LAUNCH(o.N, ss_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, ss_mat(o), what, nc, cell);
     MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, ncomp, 1.0, O);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1659,9 +1659,9 @@ int lsm_elastic_stress_norm(LsmElastic* s, const void* u0, const void* u1, const
     (void)hipSetDevice(s->h->device);
     double* res = o.partial.p + 2 * MG_MAXB;      // the reduction uses 2·gridDim.x ≤ 2·MG_MAXB words of the 4·MG_MAXB
     MG_LAUNCH(o.N, ss_norm_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, ss_mat(o), nc, p, sref, o.partial.p, &o.st.p->ticket[3], res);
-    MG_HIP(s->h, hipGetLastError());
-    MG_HIP(s->h, hipMemcpyAsync(out, res, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    MG_HIP(s->h, hipStreamSynchronize(st));
+    LSM_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipMemcpyAsync(out, res, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    LSM_HIP(s->h, hipStreamSynchronize(st));
     return LSM_OK;
 }
 
@@ -1679,7 +1679,7 @@ int lsm_elastic_stress_load(LsmElastic* s, const void* u0, const void* u1, const
     double* cell = o.xa[0];      // 1 + N(N+1)/2 ≤ 7 cell arrays of the 6·N·nn scratch doubles
     MG_LAUNCH(o.N, ss_loadcell_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, P, nc, p, sref, cell);
     MG_LAUNCH(o.N, ss_loadnode_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, P, (const double*)cell, nc, f_out);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1700,7 +1700,7 @@ int lsm_elastic_stress_sensitivity(LsmElastic* s, const void* u0, const void* u1
     SsOut O = {{g_out, nullptr, nullptr, nullptr, nullptr, nullptr}};
     MG_LAUNCH(o.N, ss_senscell_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, A, ss_mat(o), nc, p, sref, cell);
     MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, 1, scale, O);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1762,7 +1762,7 @@ int lsm_elastic_topo_cells(LsmElastic* s, const void* u0, const void* u1, const 
     const EsLevel& L = o.lev[0];
     const int nc = (int)mg_ncells(o.N, L);
     MG_LAUNCH(o.N, td_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, s->h->stream, L, o.F, U, ss_mat(o), td_mat(o), nc, out);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -1779,6 +1779,6 @@ int lsm_elastic_topo(LsmElastic* s, const void* u0, const void* u1, const void* 
     SsOut O = {{o0, nullptr, nullptr, nullptr, nullptr, nullptr}};
     MG_LAUNCH(o.N, td_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, ss_mat(o), td_mat(o), nc, cell);
     MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, 1, 1.0, O);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }

@@ -332,8 +332,8 @@ static int el_create(LsmHandle* h, EllipticObject& o, const void* phi, double le
         nd += mg_ncells(N, lev[l]) + (size_t)lev[l].nn * (size_t)(3 + (c_nodes ? 1 : 0) + (l ? 1 : 5));
         nb += (size_t)lev[l].nn;
     }
-    MG_HIP(h, o.buf.alloc(nd * sizeof(double)));
-    if (fixed) MG_HIP(h, o.fx.alloc(nb));
+    LSM_HIP(h, o.buf.alloc(nd * sizeof(double)));
+    if (fixed) LSM_HIP(h, o.fx.alloc(nb));
     hipStream_t s = h->stream;
     const int ra = mg_alloc_scalars(h, o, EL_NSTAT, s);
     if (ra != LSM_OK) return ra;
@@ -356,14 +356,14 @@ static int el_create(LsmHandle* h, EllipticObject& o, const void* phi, double le
         if (fixed) { fxl[l] = fb; fb += m; }
         lev[l].a = acell[l]; lev[l].D = dg[l]; lev[l].cn = cn[l]; lev[l].mask = fxl[l];
     }
-    if (c_nodes) MG_HIP(h, hipMemcpyAsync(cn[0], c_nodes, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (fixed) MG_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
+    if (c_nodes) LSM_HIP(h, hipMemcpyAsync(cn[0], c_nodes, (size_t)nn * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (fixed) LSM_HIP(h, hipMemcpyAsync(fxl[0], fixed, (size_t)nn, hipMemcpyDeviceToDevice, s));
     MG_LAUNCH(N, el_setup_kernel, mg_blocks(nn), MG_THREADS, s, lev[0], o.F, a_cells ? (const void*)nullptr : phi, level, a_in, a_out, hmin, a_cells,
               acell[0], o.cnt.p);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     unsigned long long c[EL_NSTAT] = {};
-    MG_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
-    MG_HIP(h, hipStreamSynchronize(s));
+    LSM_HIP(h, hipMemcpyAsync(c, o.cnt.p, sizeof(c), hipMemcpyDeviceToHost, s));
+    LSM_HIP(h, hipStreamSynchronize(s));
     o.nfixed = (long long)c[EL_NFIXED];
     o.nfree = nn - o.nfixed;
     // what the data is refused for: stats = {-(reason), offending entries, 0, 0}
@@ -380,8 +380,8 @@ static int el_create(LsmHandle* h, EllipticObject& o, const void* phi, double le
         MG_LAUNCH(N, el_coarsen_kernel, mg_blocks(lev[l].nn), MG_THREADS, s, lev[l - 1], lev[l], o.co[l - 1][0], o.co[l - 1][1], o.co[l - 1][2], acell[l], cn[l],
                   fxl[l]);
     for (int l = 0; l < nl; ++l) MG_LAUNCH(N, el_diag_kernel, mg_blocks(lev[l].nn), MG_THREADS, s, lev[l], dg[l]);
-    MG_HIP(h, hipGetLastError());
-    MG_HIP(h, hipStreamSynchronize(s));
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipStreamSynchronize(s));
     o.lev = lev;
     o.V.z = o.precond == LSM_PRECOND_JACOBI ? o.xa[0] : o.xb[0];
     if (stats) { stats[0] = nl; stats[1] = o.nfree; stats[2] = o.nfixed; stats[3] = 0; }
@@ -422,7 +422,7 @@ int lsm_elliptic_apply(LsmElliptic* s, const double* x, double* y) {
     if (!x || !y || x == y) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elliptic_apply: x and y must be two arrays");
     const ElLevel& L = s->o->lev[0];
     MG_LAUNCH(s->o->N, el_apply_kernel, mg_blocks(L.nn), MG_THREADS, s->h->stream, L, x, y);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -431,7 +431,7 @@ int lsm_elliptic_cells(LsmElliptic* s, double* a_out_cells) {
     if (!a_out_cells) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elliptic_cells: null argument");
     const ElLevel& L = s->o->lev[0];
     const size_t m = mg_ncells(s->o->N, L);
-    MG_HIP(s->h, hipMemcpyAsync(a_out_cells, L.a, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
+    LSM_HIP(s->h, hipMemcpyAsync(a_out_cells, L.a, m * sizeof(double), hipMemcpyDeviceToDevice, s->h->stream));
     return LSM_OK;
 }
 
@@ -440,7 +440,7 @@ int lsm_elliptic_energy(LsmElliptic* s, const void* u, void* e_out) {
     if (!u || !e_out || u == e_out) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elliptic_energy: u and e_out must be two fields");
     const ElLevel& L = s->o->lev[0];
     MG_LAUNCH(s->o->N, el_energy_kernel, mg_blocks(L.nn), MG_THREADS, s->h->stream, L, s->o->F, u, e_out);
-    MG_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
@@ -451,9 +451,9 @@ int lsm_elliptic_compliance(LsmElliptic* s, const double* f, const void* u, doub
     const ElLevel& L = o.lev[0];
     hipStream_t st = s->h->stream;
     MG_LAUNCH(o.N, el_compliance_kernel, mg_blocks(L.nn), MG_THREADS, st, L, o.F, f, u, o.partial.p, o.st.p);
-    MG_HIP(s->h, hipGetLastError());
-    MG_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
-    MG_HIP(s->h, hipStreamSynchronize(st));
+    LSM_HIP(s->h, hipGetLastError());
+    LSM_HIP(s->h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+    LSM_HIP(s->h, hipStreamSynchronize(st));
     double vol = 1.0;
     for (int d = 0; d < o.N; ++d) vol *= L.h[d];
     *out = vol * o.h_st.p->out;
@@ -475,7 +475,7 @@ int lsm_elliptic_solve(LsmElliptic* s, const double* f, void* u, double rtol, in
     if (r0 != LSM_OK) return r0;
     const unsigned nb = mg_blocks(L.nn);
     MG_LAUNCH(N, el_init_kernel, nb, MG_THREADS, st, L, o.F, o.V, f, (const void*)u, jac);
-    MG_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     const int r1 = mg_iterate(h, o, max_iters, st, [&](int enq) {
         const int par = enq & 1;
         if (!jac) mg_vcycle(o, o.V.r, st);
@@ -487,8 +487,8 @@ int lsm_elliptic_solve(LsmElliptic* s, const double* f, void* u, double rtol, in
     const int r2 = mg_report(h, o, "lsm_elliptic_solve", rtol, iters_out, relres_out);
     if (r2 != LSM_OK) return r2;
     MG_LAUNCH(N, el_store_kernel, nb, MG_THREADS, st, L, o.F, (const double*)o.V.x, u);
-    MG_HIP(h, hipGetLastError());
-    MG_HIP(h, hipStreamSynchronize(st));
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipStreamSynchronize(st));
     return LSM_OK;
 }
 

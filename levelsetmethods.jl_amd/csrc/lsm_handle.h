@@ -160,6 +160,24 @@ struct LsmHandle {
 
 // shared helpers (lsm_api.hip)
 int lsm_fail(LsmHandle* h, int code, const std::string& msg);
+
+// ---- the host side's scaffolding, one definition each
+// in a function of the C ABI: a failed HIP call returns LSM_ERR_HIP with the call's text and HIP's message on the handle
+#define LSM_HIP(h, call)                                                                                          \
+    do {                                                                                                          \
+        hipError_t e_ = (call);                                                                                   \
+        if (e_ != hipSuccess) return lsm_fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+// in a module function that returns 0, 1 (refused) or 2 (device error) and has a `const char** err`: a failed HIP call returns 2
+// with *err = what.  Objects under construction are held by std::unique_ptr: nothing to release here.
+#define MOD_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
+// kernel<2> or kernel<3> by the number of dimensions
+#define LSM_LAUNCH_ND(ndim, kernel, grid, block, stream, ...)                                              \
+    do {                                                                                                   \
+        if ((ndim) == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);   \
+        else hipLaunchKernelGGL(kernel<3>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);               \
+    } while (0)
+
 // lsm_comm.hip: the attached communicator wants boundary-first stages (lsm_comm_set_overlap; LSM_SLAB_OVERLAP=0 at attach time)
 bool lsm_comm_overlap(const LsmHandle* h);
 int lsm_host_sync(LsmHandle* h, const char* what);   // host wait for h->stream that an RCCL peer's silence cannot hang (lsm_comm.hip)

@@ -311,12 +311,6 @@ void i2oe_workspace_free(I2oeWorkspace* w) { delete w; }
 
 using namespace lsm;
 
-#define I2_HIP(h, call)                                                                                       \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) return lsm_fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static const char* i2_bc_name(const LsmBc& b) {
     if (b.kind == LSM_BC_SYMMETRY) return "SymmetryBC";
     if (b.kind == LSM_BC_NONE) return "a slab interface";
@@ -409,12 +403,12 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
     I2oeWorkspace& W = *h->i2oe_ws;
     const size_t need = 9 * (size_t)nn + (size_t)nf_total;
     if (W.buf.cap < need * sizeof(double)) {
-        if (W.buf) I2_HIP(h, hipStreamSynchronize(h->stream));
-        I2_HIP(h, W.buf.alloc(need * sizeof(double)));
+        if (W.buf) LSM_HIP(h, hipStreamSynchronize(h->stream));
+        LSM_HIP(h, W.buf.alloc(need * sizeof(double)));
     }
-    if (!W.partial) I2_HIP(h, W.partial.alloc(3 * I2_MAXB * sizeof(double)));
-    if (!W.st) I2_HIP(h, W.st.alloc(sizeof(I2State)));
-    if (!W.h_st) I2_HIP(h, W.h_st.alloc(sizeof(I2State)));
+    if (!W.partial) LSM_HIP(h, W.partial.alloc(3 * I2_MAXB * sizeof(double)));
+    if (!W.st) LSM_HIP(h, W.st.alloc(sizeof(I2State)));
+    if (!W.h_st) LSM_HIP(h, W.h_st.alloc(sizeof(I2State)));
     double* b = W.buf;
     a.x = b; a.r = b + nn; a.rh = b + 2 * nn; a.s = b + 3 * nn; a.t = b + 4 * nn;
     a.p[0] = b + 5 * nn; a.p[1] = b + 6 * nn; a.v[0] = b + 7 * nn; a.v[1] = b + 8 * nn;
@@ -427,7 +421,7 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
     s0.rtol2 = rtol * rtol;
     s0.max_iters = max_iters;
     hipStream_t st = h->stream;
-    I2_HIP(h, hipMemcpyAsync(W.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+    LSM_HIP(h, hipMemcpyAsync(W.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
     const unsigned nb = (unsigned)std::min<unsigned long long>((nn + I2_THREADS - 1) / I2_THREADS, I2_MAXB);
     for (int d = 0; d < N; ++d) {
         const unsigned long long nf = nn / a.n[d] * (a.n[d] + 1);
@@ -435,7 +429,7 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
         hipLaunchKernelGGL(i2oe_faces_kernel, dim3(fb), dim3(I2_THREADS), 0, st, a, d);
     }
     hipLaunchKernelGGL(i2oe_init_kernel, dim3(nb), dim3(I2_THREADS), 0, st, a);
-    I2_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
 
     // iterations in chunks: the first chunk is as long as the last solve took, then doubling
     int enq = 0;
@@ -448,9 +442,9 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
             hipLaunchKernelGGL(i2oe_k2_kernel, dim3(nb), dim3(I2_THREADS), 0, st, a, par);
             hipLaunchKernelGGL(i2oe_k3_kernel, dim3(nb), dim3(I2_THREADS), 0, st, a, par);
         }
-        I2_HIP(h, hipGetLastError());
-        I2_HIP(h, hipMemcpyAsync(W.h_st, W.st, sizeof(I2State), hipMemcpyDeviceToHost, st));
-        I2_HIP(h, hipStreamSynchronize(st));
+        LSM_HIP(h, hipGetLastError());
+        LSM_HIP(h, hipMemcpyAsync(W.h_st, W.st, sizeof(I2State), hipMemcpyDeviceToHost, st));
+        LSM_HIP(h, hipStreamSynchronize(st));
         if (W.h_st.p->status != I2_RUN || enq >= max_iters) break;
         chunk = std::min(2 * chunk, 64);
     }
@@ -471,6 +465,6 @@ int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, do
         return lsm_fail(h, LSM_ERR_NOT_CONVERGED, msg);
     }
     hipLaunchKernelGGL(i2oe_store_kernel, dim3(nb), dim3(I2_THREADS), 0, st, a);
-    I2_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipGetLastError());
     return LSM_OK;
 }

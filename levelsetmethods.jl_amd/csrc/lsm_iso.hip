@@ -6,15 +6,16 @@
 //   * an edge carries a vertex only if an active cell contains it (dense: every cell; band: the cells whose 2^N corners are
 //     band nodes — only band values decide); vertices are numbered by ascending node (axis 0 fastest), then ascending d;
 //   * the elements are those of the active cells, ascending.
-// Kernels: kuhn.h's classify sweep with the band's cover test (sums per chunk: vertices, elements, nodes that own any), the scan
-// of the chunk sums, an ordered compaction of the nodes that own a vertex or an element (with their vertex and element offsets;
+// Kernels: kuhn.h's classify sweep with the band's cover test (sums per chunk: vertices, elements, nodes that own any), scan.h's
+// scan of the chunk sums, an ordered compaction of the nodes that own a vertex or an element (with their vertex and element offsets;
 // the vertex offset also goes into a node-indexed array that is written and read at those nodes only), and one thread per
 // listed node for the vertices and for the elements.  No atomic decides an output position.  The host side of kuhn.h (the front
-// half of a build, the scan kernel, the read-out) is defined here.
+// half of a build, the read-out) is defined here.
 #include <algorithm>
 #include <memory>
 
 #include "kuhn.h"
+#include "scan.h"
 
 namespace lsm {
 
@@ -86,56 +87,11 @@ __global__ void __launch_bounds__(256) iso_classify_kernel(KuhnArgs a, unsigned 
     kuhn_chunk_sums(nv, ne, nl, sums, nchunk);
 }
 
-// exclusive scans of the three rows of `in` (n values each) in one workgroup of 1024 threads, 8 consecutive values per thread per
-// round; the totals into tot[0..2]
-__global__ void __launch_bounds__(1024) kuhn_scan_kernel(const unsigned* in, long long n, long long* out, long long* tot) {
-    __shared__ long long s[3][1024];
-    long long carry[3] = {0, 0, 0};
-    const int t = threadIdx.x;
-    for (long long base = 0; base < n; base += 8 * 1024) {
-        unsigned v[3][8];
-        long long acc[3] = {0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const long long i = base + 8LL * t + e;
-                v[r][e] = i < n ? in[r * n + i] : 0u;
-                acc[r] += v[r][e];
-            }
-#pragma unroll
-        for (int r = 0; r < 3; ++r) s[r][t] = acc[r];
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {     // Hillis–Steele inclusive scan of the thread sums
-            long long x[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) x[r] = t >= d ? s[r][t - d] : 0;
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 3; ++r) s[r][t] += x[r];
-            __syncthreads();
-        }
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            long long e0 = carry[r] + s[r][t] - acc[r];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const long long i = base + 8LL * t + e;
-                if (i < n) out[r * n + i] = e0;
-                e0 += v[r][e];
-            }
-            carry[r] += s[r][1023];
-        }
-        __syncthreads();
-    }
-    if (t < 3) tot[t] = carry[t];
-}
-
 // the nodes of every chunk that own a vertex or an element, ascending, at the chunk's scanned offset: node, vertex offset,
 // element offset; vbase[node] := vertex offset where the node owns a vertex
 __global__ void __launch_bounds__(256) iso_compact_kernel(const unsigned char* emask, const unsigned char* ecnt, long long nnode, const long long* off,
                                                           long long nchunk, long long* list, long long* list_v, long long* list_e, unsigned* vbase) {
-    __shared__ unsigned s[3][256];
+    __shared__ unsigned wsum[3][4];
     const int t = threadIdx.x;
     const long long c0 = (long long)blockIdx.x * KUHN_CHUNK + (long long)t * KUHN_PER;
     const uint4 em4 = *reinterpret_cast<const uint4*>(emask + c0), ec4 = *reinterpret_cast<const uint4*>(ecnt + c0);
@@ -148,17 +104,9 @@ __global__ void __launch_bounds__(256) iso_compact_kernel(const unsigned char* e
         m[1] += ec;
         m[2] += (em | ec) != 0;
     }
-    for (int r = 0; r < 3; ++r) s[r][t] = m[r];
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        unsigned x[3];
-        for (int r = 0; r < 3; ++r) x[r] = t >= d ? s[r][t - d] : 0;
-        __syncthreads();
-        for (int r = 0; r < 3; ++r) s[r][t] += x[r];
-        __syncthreads();
-    }
-    long long pv = off[blockIdx.x] + s[0][t] - m[0], pe = off[nchunk + blockIdx.x] + s[1][t] - m[1],
-              pl = off[2 * nchunk + blockIdx.x] + s[2][t] - m[2];
+    unsigned total;
+    long long pv = off[blockIdx.x] + block_excl_scan<4>(m[0], wsum[0], total), pe = off[nchunk + blockIdx.x] + block_excl_scan<4>(m[1], wsum[1], total),
+              pl = off[2 * nchunk + blockIdx.x] + block_excl_scan<4>(m[2], wsum[2], total);
 #pragma unroll
     for (int e = 0; e < KUHN_PER; ++e) {
         const unsigned em = (emw[e / 4] >> (8 * (e % 4))) & 255u, ec = (ecw[e / 4] >> (8 * (e % 4))) & 255u;
@@ -210,8 +158,6 @@ __global__ void __launch_bounds__(256) iso_element_kernel(KuhnArgs a, const unsi
 }
 
 // ---- host side: kuhn.h's
-#define TRY_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
-
 int kuhn_begin(const LsmHandle* h, double level, const void* phi, const unsigned char* mask, long long max_chunks, const char* const msg[5],
                KuhnWork& w, const char** err) {
     const int ndim = h->grid.ndim;
@@ -229,26 +175,27 @@ int kuhn_begin(const LsmHandle* h, double level, const void* phi, const unsigned
     a.level = level; a.phi = phi; a.f32 = h->dtype == LSM_DTYPE_F32; a.mask = mask;
     w.nchunk = (a.nnode + KUHN_CHUNK - 1) / KUHN_CHUNK;
     if (w.nchunk > max_chunks) { *err = msg[2]; return 1; }
-    TRY_HIP(w.emask.alloc((size_t)w.nchunk * KUHN_CHUNK), "hipMalloc(edge masks)");
-    TRY_HIP(w.ecnt.alloc((size_t)w.nchunk * KUHN_CHUNK), "hipMalloc(element counts)");
-    TRY_HIP(w.sums.alloc(3 * (size_t)w.nchunk * sizeof(unsigned)), "hipMalloc(chunk sums)");
-    TRY_HIP(w.off.alloc(3 * (size_t)w.nchunk * sizeof(long long)), "hipMalloc(chunk offsets)");
-    TRY_HIP(w.tot.alloc(3 * sizeof(long long)), "hipMalloc(totals)");
+    MOD_HIP(w.emask.alloc((size_t)w.nchunk * KUHN_CHUNK), "hipMalloc(edge masks)");
+    MOD_HIP(w.ecnt.alloc((size_t)w.nchunk * KUHN_CHUNK), "hipMalloc(element counts)");
+    MOD_HIP(w.sums.alloc(3 * (size_t)w.nchunk * sizeof(unsigned)), "hipMalloc(chunk sums)");
+    MOD_HIP(w.off.alloc(3 * (size_t)w.nchunk * sizeof(long long)), "hipMalloc(chunk offsets)");
+    MOD_HIP(w.tot.alloc(3 * sizeof(long long)), "hipMalloc(totals)");
     return 0;
 }
 
 int kuhn_totals(KuhnWork& w, hipStream_t stream, const char* const msg[5], const char** err) {
-    hipLaunchKernelGGL(kuhn_scan_kernel, dim3(1), dim3(1024), 0, stream, w.sums.p, w.nchunk, w.off.p, w.tot.p);
-    TRY_HIP(hipMemcpyAsync(w.total, w.tot, 3 * sizeof(long long), hipMemcpyDeviceToHost, stream), msg[3]);
-    TRY_HIP(hipStreamSynchronize(stream), msg[3]);
+    const long long n = w.nchunk;
+    chunk_scan<3, long long>(stream, {{{w.sums.p, w.off.p, 0}, {w.sums.p + n, w.off.p + n, 0}, {w.sums.p + 2 * n, w.off.p + 2 * n, 0}}}, n, w.tot.p);
+    MOD_HIP(hipMemcpyAsync(w.total, w.tot, 3 * sizeof(long long), hipMemcpyDeviceToHost, stream), msg[3]);
+    MOD_HIP(hipStreamSynchronize(stream), msg[3]);
     if (w.total[0] > 0xffffffffLL) { *err = msg[4]; return 1; }
     return 0;
 }
 
 int kuhn_read(hipStream_t stream, std::initializer_list<KuhnCopy> copies, const char* what, const char** err) {
     for (const KuhnCopy& c : copies)
-        if (c.dst && c.bytes) TRY_HIP(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, stream), what);
-    TRY_HIP(hipStreamSynchronize(stream), what);
+        if (c.dst && c.bytes) MOD_HIP(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, stream), what);
+    MOD_HIP(hipStreamSynchronize(stream), what);
     return 0;
 }
 
@@ -268,7 +215,7 @@ int iso_build(const LsmHandle* h, double level, const void* phi, const unsigned 
     const int ndim = h->grid.ndim;
     KuhnWork w;
     if (const int r = kuhn_begin(h, level, phi, mask, 1LL << 23, msg, w, err)) return r;     // 256 threads per chunk in one launch
-    KUHN_LAUNCH(ndim, iso_classify_kernel, (unsigned)w.nchunk, stream, w.a, w.emask.p, w.ecnt.p, w.sums.p, w.nchunk);
+    LSM_LAUNCH_ND(ndim, iso_classify_kernel, (unsigned)w.nchunk, 256, stream, w.a, w.emask.p, w.ecnt.p, w.sums.p, w.nchunk);
     if (const int r = kuhn_totals(w, stream, msg, err)) return r;
     const KuhnArgs& a = w.a;
     std::unique_ptr<IsoObject> o(new IsoObject());
@@ -280,20 +227,20 @@ int iso_build(const LsmHandle* h, double level, const void* phi, const unsigned 
     if (nlist) {
         DevBuf<unsigned> vbase;          // vertex offset of a node that owns a vertex
         DevBuf<long long> list, list_v, list_e;
-        TRY_HIP(vbase.alloc((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(vertex offsets)");
-        TRY_HIP(list.alloc((size_t)nlist * sizeof(long long)), "hipMalloc(node list)");
-        TRY_HIP(list_v.alloc((size_t)nlist * sizeof(long long)), "hipMalloc(node list)");
-        TRY_HIP(list_e.alloc((size_t)nlist * sizeof(long long)), "hipMalloc(node list)");
-        TRY_HIP(o->verts.alloc((size_t)std::max(o->nv, 1LL) * ndim * sizeof(double)), "hipMalloc(vertices)");
-        TRY_HIP(o->elems.alloc((size_t)std::max(o->ne, 1LL) * ndim * sizeof(long long)), "hipMalloc(elements)");
+        MOD_HIP(vbase.alloc((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(vertex offsets)");
+        MOD_HIP(list.alloc((size_t)nlist * sizeof(long long)), "hipMalloc(node list)");
+        MOD_HIP(list_v.alloc((size_t)nlist * sizeof(long long)), "hipMalloc(node list)");
+        MOD_HIP(list_e.alloc((size_t)nlist * sizeof(long long)), "hipMalloc(node list)");
+        MOD_HIP(o->verts.alloc((size_t)std::max(o->nv, 1LL) * ndim * sizeof(double)), "hipMalloc(vertices)");
+        MOD_HIP(o->elems.alloc((size_t)std::max(o->ne, 1LL) * ndim * sizeof(long long)), "hipMalloc(elements)");
         hipLaunchKernelGGL(iso_compact_kernel, dim3((unsigned)w.nchunk), dim3(256), 0, stream, w.emask.p, w.ecnt.p, a.nnode, w.off.p, w.nchunk, list.p,
                            list_v.p, list_e.p, vbase.p);
         const unsigned glist = (unsigned)((nlist + 255) / 256);
-        KUHN_LAUNCH(ndim, iso_vertex_kernel, glist, stream, a, w.emask.p, list.p, list_v.p, nlist, o->verts.p);
-        KUHN_LAUNCH(ndim, iso_element_kernel, glist, stream, a, w.emask.p, w.ecnt.p, vbase.p, list.p, list_e.p, nlist, o->elems.p);
+        LSM_LAUNCH_ND(ndim, iso_vertex_kernel, glist, 256, stream, a, w.emask.p, list.p, list_v.p, nlist, o->verts.p);
+        LSM_LAUNCH_ND(ndim, iso_element_kernel, glist, 256, stream, a, w.emask.p, w.ecnt.p, vbase.p, list.p, list_e.p, nlist, o->elems.p);
     }
-    TRY_HIP(hipGetLastError(), "isosurface: launch failed");
-    TRY_HIP(hipStreamSynchronize(stream), "isosurface: device error");     // the work buffers are released on return
+    MOD_HIP(hipGetLastError(), "isosurface: launch failed");
+    MOD_HIP(hipStreamSynchronize(stream), "isosurface: device error");     // the work buffers are released on return
     counts_out[0] = o->nv;
     counts_out[1] = o->ne;
     *out = o.release();
@@ -306,6 +253,5 @@ int iso_read(IsoObject* o, double* verts, long long* elems, const char** err) {
 }
 
 void iso_free(IsoObject* o) { delete o; }
-#undef TRY_HIP
 
 }  // namespace lsm

@@ -344,13 +344,6 @@ struct MdistWorkspace {
 };
 void mdist_workspace_free(MdistWorkspace* w) { delete w; }
 
-#define MD_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
-#define MD_LAUNCH(kernel, grid, block, ...)                                                     \
-    do {                                                                                        \
-        if (ndim == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel<3>, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);    \
-    } while (0)
-
 int mdist_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3], long long nv,
               const double* verts, long long ne, const long long* elems, double cutoff, void* phi, int f32, hipStream_t stream, long long stats[3],
               const char** err, MdistWorkspace** workspace) {
@@ -379,18 +372,18 @@ int mdist_run(int ndim, const int n[3], long long s1, long long s2, long long or
     if (!*workspace) *workspace = new MdistWorkspace();     // the handle's, created by its first call; the buffers only grow
     MdistWorkspace& W = **workspace;
     const size_t nflip = (size_t)a.nrow * ((size_t)a.n[0] + 1);
-    MD_HIP(W.d2.grow((size_t)a.nnode * sizeof(unsigned long long)), "hipMalloc(squared distances)");
-    MD_HIP(W.flips.grow(nflip * sizeof(int)), "hipMalloc(flip counters)");
-    MD_HIP(W.st.grow(MD_NSTAT * sizeof(unsigned long long)), "hipMalloc(statistics)");
-    MD_HIP(hipMemsetAsync(W.st.p, 0, MD_NSTAT * sizeof(unsigned long long), stream), "mesh_distance: memset");
-    MD_HIP(hipMemsetAsync(W.flips.p, 0, nflip * sizeof(int), stream), "mesh_distance: memset");
+    MOD_HIP(W.d2.grow((size_t)a.nnode * sizeof(unsigned long long)), "hipMalloc(squared distances)");
+    MOD_HIP(W.flips.grow(nflip * sizeof(int)), "hipMalloc(flip counters)");
+    MOD_HIP(W.st.grow(MD_NSTAT * sizeof(unsigned long long)), "hipMalloc(statistics)");
+    MOD_HIP(hipMemsetAsync(W.st.p, 0, MD_NSTAT * sizeof(unsigned long long), stream), "mesh_distance: memset");
+    MOD_HIP(hipMemsetAsync(W.flips.p, 0, nflip * sizeof(int), stream), "mesh_distance: memset");
     hipLaunchKernelGGL(md_init_kernel, dim3((unsigned)((a.nnode + 255) / 256)), dim3(256), 0, stream, W.d2.p, a.nnode, a.c2bits);
     unsigned long long st[MD_NSTAT] = {};
     if (ne > 0 || nv > 0) {
         const long long nt = std::max(ne, nv);
-        MD_LAUNCH(md_prep_kernel, (unsigned)((nt + 255) / 256), 256, a, W.st.p);
-        MD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "mesh_distance: validation");
-        MD_HIP(hipStreamSynchronize(stream), "mesh_distance: validation");
+        LSM_LAUNCH_ND(ndim, md_prep_kernel, (unsigned)((nt + 255) / 256), 256, stream, a, W.st.p);
+        MOD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "mesh_distance: validation");
+        MOD_HIP(hipStreamSynchronize(stream), "mesh_distance: validation");
         if (st[MD_BAD_INDEX]) { *err = "mesh_distance: an element refers to a vertex number outside 0..nverts-1"; return 1; }
         if (st[MD_NONFINITE]) { *err = "mesh_distance: the vertices must be finite"; return 1; }
     }
@@ -399,20 +392,18 @@ int mdist_run(int ndim, const int n[3], long long s1, long long s2, long long or
         const long long per = std::max(1LL, MD_MAX_BLOCKS / maxp);      // elements per launch
         for (long long e0 = 0; e0 < ne; e0 += per) {
             const long long cnt = std::min(per, ne - e0);
-            MD_LAUNCH(md_dist_kernel, (unsigned)(cnt * maxp), 64, a, W.d2.p, e0, (unsigned)maxp);
+            LSM_LAUNCH_ND(ndim, md_dist_kernel, (unsigned)(cnt * maxp), 64, stream, a, W.d2.p, e0, (unsigned)maxp);
         }
     }
-    if (ne > 0) MD_LAUNCH(md_sign_kernel, (unsigned)((ne * MD_SUB + 255) / 256), 256, a, W.flips.p, W.st.p);
-    MD_LAUNCH(md_final_kernel, (unsigned)((a.nrow + 3) / 4), 256, a, W.d2.p, W.flips.p, phi, f32, W.st.p);
-    MD_HIP(hipGetLastError(), "mesh_distance: launch failed");
-    MD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "mesh_distance: statistics");
-    MD_HIP(hipStreamSynchronize(stream), "mesh_distance: device error");
+    if (ne > 0) LSM_LAUNCH_ND(ndim, md_sign_kernel, (unsigned)((ne * MD_SUB + 255) / 256), 256, stream, a, W.flips.p, W.st.p);
+    LSM_LAUNCH_ND(ndim, md_final_kernel, (unsigned)((a.nrow + 3) / 4), 256, stream, a, W.d2.p, W.flips.p, phi, f32, W.st.p);
+    MOD_HIP(hipGetLastError(), "mesh_distance: launch failed");
+    MOD_HIP(hipMemcpyAsync(st, W.st.p, sizeof(st), hipMemcpyDeviceToHost, stream), "mesh_distance: statistics");
+    MOD_HIP(hipStreamSynchronize(stream), "mesh_distance: device error");
     stats[0] = (long long)st[MD_NEAR];
     stats[1] = (long long)st[MD_UNBALANCED];
     stats[2] = (long long)st[MD_SKIPPED];
     return 0;
 }
-#undef MD_LAUNCH
-#undef MD_HIP
 
 }  // namespace lsm

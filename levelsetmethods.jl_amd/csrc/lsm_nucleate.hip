@@ -11,8 +11,8 @@
 //                 the way in), every thread the minimum of its 2w + 1 entries;
 //   nu_pass_col   the same along y or z: a tile of 64 columns (x-contiguous: every global access is a run of 64 values) by 16
 //                 lines, staged with its w-halo in dynamic LDS, (16 + 2w)·64 pairs of 12 bytes: 13.5 KB at w = 1, 60 KB at w = 32;
-//   nu_count      the centres of every chunk of 4096 nodes;  nu_scan  their exclusive scan in one workgroup and the total, which
-//                 is the host's one read;  nu_write  (index, value) in ascending index at the scanned positions — no append whose
+//   nu_count      the centres of every chunk of 4096 nodes;  chunk_scan (scan.h)  their exclusive scan in one workgroup and the
+//                 total, which is the host's one read;  nu_write  (index, value) in ascending index at the scanned positions — no append whose
 //                 order depends on the schedule;
 //   nu_punch_mark one workgroup per centre over its clipped box: an integer atomic max of the order-preserving image of v into
 //                 one 64-bit word per node;  nu_punch_apply  one thread per node: the compare with ϕ, the one store, the count.
@@ -25,6 +25,7 @@
 #include <memory>
 
 #include "kuhn.h"
+#include "scan.h"
 
 namespace lsm {
 
@@ -173,26 +174,8 @@ __global__ void __launch_bounds__(256) nu_count_kernel(NuArgs a, const unsigned 
         const long long i = c0 + 256 * q + threadIdx.x;
         if (i < a.nnode && nu_centre(k, idx, i)) ++c;
     }
-    unsigned total;
-    block_excl_scan<4>(c, wsum, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// off[c] := the centres in the chunks before c; *total := their number.  One workgroup.
-__global__ void __launch_bounds__(256) nu_scan_kernel(const unsigned* __restrict__ sums, long long nchunk, unsigned long long* __restrict__ off,
-                                                      unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long wsum[4];
-    unsigned long long run = 0;
-    for (long long base = 0; base < nchunk; base += 256) {      // uniform over the workgroup
-        const bool in = base + threadIdx.x < nchunk;
-        const unsigned long long v = in ? sums[base + threadIdx.x] : 0ull;
-        unsigned long long tot;
-        const unsigned long long ex = block_excl_scan<4>(v, wsum, tot);
-        if (in) off[base + threadIdx.x] = run + ex;
-        run += tot;
-        __syncthreads();      // wsum is written again
-    }
-    if (threadIdx.x == 0) *total = run;
+    c = block_sum<4>(c, wsum);
+    if (threadIdx.x == 0) sums[blockIdx.x] = c;
 }
 
 template <int N>
@@ -314,8 +297,6 @@ struct NuObject {
     hipStream_t stream = nullptr;
 };
 
-#define NU_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
-
 static int nu_args(const LsmHandle* h, NuArgs& a, const char** err) {
     const int ndim = h->grid.ndim;
     if (ndim != 2 && ndim != 3) { *err = "nucleate: 2-D and 3-D fields only"; return 1; }
@@ -337,14 +318,14 @@ static int nu_args(const LsmHandle* h, NuArgs& a, const char** err) {
 static int nu_grow(NuWorkspace** workspace, const NuArgs& a, bool search, const char** err) {
     if (!*workspace) *workspace = new NuWorkspace();      // the handle's, created by its first call; the buffers only grow
     NuWorkspace& W = **workspace;
-    NU_HIP(W.ka.grow((size_t)a.nnode * sizeof(unsigned long long)), "hipMalloc(keys)");
-    NU_HIP(W.cnt.grow(3 * sizeof(unsigned long long)), "hipMalloc(counters)");
+    MOD_HIP(W.ka.grow((size_t)a.nnode * sizeof(unsigned long long)), "hipMalloc(keys)");
+    MOD_HIP(W.cnt.grow(3 * sizeof(unsigned long long)), "hipMalloc(counters)");
     if (search) {
-        NU_HIP(W.kb.grow((size_t)a.nnode * sizeof(unsigned long long)), "hipMalloc(keys)");
-        NU_HIP(W.ia.grow((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(key indices)");
-        NU_HIP(W.ib.grow((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(key indices)");
-        NU_HIP(W.sums.grow((size_t)a.nchunk * sizeof(unsigned)), "hipMalloc(chunk sums)");
-        NU_HIP(W.off.grow((size_t)a.nchunk * sizeof(unsigned long long)), "hipMalloc(chunk offsets)");
+        MOD_HIP(W.kb.grow((size_t)a.nnode * sizeof(unsigned long long)), "hipMalloc(keys)");
+        MOD_HIP(W.ia.grow((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(key indices)");
+        MOD_HIP(W.ib.grow((size_t)a.nnode * sizeof(unsigned)), "hipMalloc(key indices)");
+        MOD_HIP(W.sums.grow((size_t)a.nchunk * sizeof(unsigned)), "hipMalloc(chunk sums)");
+        MOD_HIP(W.off.grow((size_t)a.nchunk * sizeof(unsigned long long)), "hipMalloc(chunk offsets)");
     }
     return 0;
 }
@@ -395,20 +376,19 @@ int nu_build(const LsmHandle* h, NuWorkspace** workspace, const void* phi, const
     const unsigned* xf = ndim == 2 ? W.ib.p : W.ia.p;
     const unsigned nchunk = (unsigned)a.nchunk;
     hipLaunchKernelGGL(nu_count_kernel, dim3(nchunk), dim3(256), 0, stream, a, kf, xf, W.sums.p);
-    hipLaunchKernelGGL(nu_scan_kernel, dim3(1), dim3(256), 0, stream, (const unsigned*)W.sums.p, a.nchunk, W.off.p, W.cnt.p);
-    NU_HIP(hipGetLastError(), "nucleate: launch failed");
+    chunk_scan<1, unsigned long long>(stream, {{{W.sums.p, W.off.p, 0}}}, a.nchunk, W.cnt.p);
+    MOD_HIP(hipGetLastError(), "nucleate: launch failed");
     unsigned long long total = 0;
-    NU_HIP(hipMemcpyAsync(&total, W.cnt.p, sizeof(total), hipMemcpyDeviceToHost, stream), "nucleate: count");
-    NU_HIP(hipStreamSynchronize(stream), "nucleate: device error");
+    MOD_HIP(hipMemcpyAsync(&total, W.cnt.p, sizeof(total), hipMemcpyDeviceToHost, stream), "nucleate: count");
+    MOD_HIP(hipStreamSynchronize(stream), "nucleate: device error");
     if (total > (unsigned long long)a.nnode) { *err = "nucleate: more centres than nodes"; return 2; }
     o->count = (long long)total;
-    NU_HIP(o->idx.alloc((size_t)std::max(o->count, 1LL) * sizeof(long long)), "hipMalloc(centres)");
-    NU_HIP(o->val.alloc((size_t)std::max(o->count, 1LL) * sizeof(double)), "hipMalloc(centre values)");
+    MOD_HIP(o->idx.alloc((size_t)std::max(o->count, 1LL) * sizeof(long long)), "hipMalloc(centres)");
+    MOD_HIP(o->val.alloc((size_t)std::max(o->count, 1LL) * sizeof(double)), "hipMalloc(centre values)");
     if (o->count) {
-        if (ndim == 2) hipLaunchKernelGGL(nu_write_kernel<2>, dim3(nchunk), dim3(256), 0, stream, a, kf, xf, t, (const unsigned long long*)W.off.p, o->idx.p, o->val.p);
-        else hipLaunchKernelGGL(nu_write_kernel<3>, dim3(nchunk), dim3(256), 0, stream, a, kf, xf, t, (const unsigned long long*)W.off.p, o->idx.p, o->val.p);
-        NU_HIP(hipGetLastError(), "nucleate: launch failed");
-        NU_HIP(hipStreamSynchronize(stream), "nucleate: device error");
+        LSM_LAUNCH_ND(ndim, nu_write_kernel, nchunk, 256, stream, a, kf, xf, t, (const unsigned long long*)W.off.p, o->idx.p, o->val.p);
+        MOD_HIP(hipGetLastError(), "nucleate: launch failed");
+        MOD_HIP(hipStreamSynchronize(stream), "nucleate: device error");
     }
     *count = o->count;
     *out = o.release();
@@ -443,24 +423,21 @@ int nu_punch(const LsmHandle* h, NuWorkspace** workspace, void* phi, const long 
     if (const int r = nu_grow(workspace, a, false, err)) return r;
     NuWorkspace& W = **workspace;
     unsigned long long* cnt = W.cnt.p + 1;
-    NU_HIP(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), stream), "nucleate punch: memset");
-    NU_HIP(hipMemsetAsync(W.ka.p, 0, (size_t)a.nnode * sizeof(unsigned long long), stream), "nucleate punch: memset");
-    if (ndim == 2) hipLaunchKernelGGL(nu_punch_mark_kernel<2>, dim3((unsigned)count), dim3(256), 0, stream, a, b, centres, W.ka.p, cnt);
-    else hipLaunchKernelGGL(nu_punch_mark_kernel<3>, dim3((unsigned)count), dim3(256), 0, stream, a, b, centres, W.ka.p, cnt);
-    NU_HIP(hipGetLastError(), "nucleate punch: launch failed");
+    MOD_HIP(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), stream), "nucleate punch: memset");
+    MOD_HIP(hipMemsetAsync(W.ka.p, 0, (size_t)a.nnode * sizeof(unsigned long long), stream), "nucleate punch: memset");
+    LSM_LAUNCH_ND(ndim, nu_punch_mark_kernel, (unsigned)count, 256, stream, a, b, centres, W.ka.p, cnt);
+    MOD_HIP(hipGetLastError(), "nucleate punch: launch failed");
     unsigned long long c[2] = {};
-    NU_HIP(hipMemcpyAsync(c, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "nucleate punch: counts");
-    NU_HIP(hipStreamSynchronize(stream), "nucleate punch: device error");
+    MOD_HIP(hipMemcpyAsync(c, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "nucleate punch: counts");
+    MOD_HIP(hipStreamSynchronize(stream), "nucleate punch: device error");
     if (c[0]) { *err = "nucleate punch: a centre is not a node index of the grid"; return 1; }
     const unsigned nblk = (unsigned)((a.nnode + 255) / 256);
-    if (ndim == 2) hipLaunchKernelGGL(nu_punch_apply_kernel<2>, dim3(nblk), dim3(256), 0, stream, a, phi, (const unsigned long long*)W.ka.p, cnt);
-    else hipLaunchKernelGGL(nu_punch_apply_kernel<3>, dim3(nblk), dim3(256), 0, stream, a, phi, (const unsigned long long*)W.ka.p, cnt);
-    NU_HIP(hipGetLastError(), "nucleate punch: launch failed");
-    NU_HIP(hipMemcpyAsync(c, cnt, sizeof(c), hipMemcpyDeviceToHost, stream), "nucleate punch: counts");
-    NU_HIP(hipStreamSynchronize(stream), "nucleate punch: device error");
+    LSM_LAUNCH_ND(ndim, nu_punch_apply_kernel, nblk, 256, stream, a, phi, (const unsigned long long*)W.ka.p, cnt);
+    MOD_HIP(hipGetLastError(), "nucleate punch: launch failed");
+    MOD_HIP(hipMemcpyAsync(c, cnt, sizeof(c), hipMemcpyDeviceToHost, stream), "nucleate punch: counts");
+    MOD_HIP(hipStreamSynchronize(stream), "nucleate punch: device error");
     *changed = (long long)c[1];
     return 0;
 }
-#undef NU_HIP
 
 }  // namespace lsm

@@ -685,9 +685,7 @@ template <int NV, int NC, int NDIM>   // NV = 0: the general version
 __global__ void __launch_bounds__(256) quad_classify_kernel(QuadArgs qa, long long ncell, unsigned char* cls, unsigned* ncut_chunk,
                                                             unsigned* nfull_chunk) {
     const ReinitArgs& a = qa.a;
-    __shared__ unsigned nc_cut, nc_full;
-    if (threadIdx.x == 0) nc_cut = nc_full = 0;
-    __syncthreads();
+    __shared__ unsigned wsum[2][4];
     unsigned mc = 0, mf = 0;
     const long long c0 = (long long)blockIdx.x * QUAD_CHUNK;
     for (int r = threadIdx.x; r < QUAD_CHUNK; r += blockDim.x) {
@@ -714,54 +712,16 @@ __global__ void __launch_bounds__(256) quad_classify_kernel(QuadArgs qa, long lo
         mc += k == 1;
         mf += k == 2;
     }
-    if (mc) atomicAdd(&nc_cut, mc);
-    if (mf) atomicAdd(&nc_full, mf);
-    __syncthreads();
-    if (threadIdx.x == 0) { ncut_chunk[blockIdx.x] = nc_cut; nfull_chunk[blockIdx.x] = nc_full; }
-}
-
-// exclusive scans of in0 and of in1 (in1 == NULL: of in0 != 0) in one workgroup of 1024 threads, 8 consecutive values per thread
-// per round; the totals into tot[0], tot[1]
-__global__ void __launch_bounds__(1024) quad_scan_kernel(const unsigned* in0, const unsigned* in1, long long n, long long* out0, long long* out1,
-                                                         long long* tot) {
-    __shared__ long long s0[1024], s1[1024];
-    long long carry0 = 0, carry1 = 0;
-    const int t = threadIdx.x;
-    for (long long base = 0; base < n; base += 8 * 1024) {
-        long long v0[8], v1[8], a0 = 0, a1 = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const long long i = base + 8LL * t + e;
-            v0[e] = i < n ? in0[i] : 0;
-            v1[e] = i < n ? (in1 ? in1[i] : (in0[i] != 0)) : 0;
-            a0 += v0[e]; a1 += v1[e];
-        }
-        s0[t] = a0; s1[t] = a1;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {     // Hillis–Steele inclusive scan of the thread sums
-            const long long x0 = t >= d ? s0[t - d] : 0, x1 = t >= d ? s1[t - d] : 0;
-            __syncthreads();
-            s0[t] += x0; s1[t] += x1;
-            __syncthreads();
-        }
-        long long e0 = carry0 + s0[t] - a0, e1 = carry1 + s1[t] - a1;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const long long i = base + 8LL * t + e;
-            if (i < n) { out0[i] = e0; out1[i] = e1; }
-            e0 += v0[e]; e1 += v1[e];
-        }
-        carry0 += s0[1023]; carry1 += s1[1023];
-        __syncthreads();
-    }
-    if (t == 0) { tot[0] = carry0; tot[1] = carry1; }
+    mc = block_sum<4>(mc, wsum[0]);
+    mf = block_sum<4>(mf, wsum[1]);
+    if (threadIdx.x == 0) { ncut_chunk[blockIdx.x] = mc; nfull_chunk[blockIdx.x] = mf; }
 }
 
 // the cut and the full cells of every chunk, in ascending order, at the chunk's scanned offsets
 __global__ void __launch_bounds__(256) quad_compact_kernel(const unsigned char* cls, long long ncell, const long long* off_cut,
                                                            const long long* off_full, long long* cand, long long* full) {
     constexpr int PER = QUAD_CHUNK / 256;
-    __shared__ unsigned sc[256], sf[256];
+    __shared__ unsigned wsum[2][4];
     const long long c0 = (long long)blockIdx.x * QUAD_CHUNK + (long long)threadIdx.x * PER;
     unsigned mc = 0, mf = 0;
     for (int e = 0; e < PER; ++e) {
@@ -769,15 +729,8 @@ __global__ void __launch_bounds__(256) quad_compact_kernel(const unsigned char* 
         const unsigned char k = c < ncell ? cls[c] : 0;
         mc += k == 1; mf += k == 2;
     }
-    sc[threadIdx.x] = mc; sf[threadIdx.x] = mf;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const unsigned xc = threadIdx.x >= d ? sc[threadIdx.x - d] : 0, xf = threadIdx.x >= d ? sf[threadIdx.x - d] : 0;
-        __syncthreads();
-        sc[threadIdx.x] += xc; sf[threadIdx.x] += xf;
-        __syncthreads();
-    }
-    long long pc = off_cut[blockIdx.x] + sc[threadIdx.x] - mc, pf = off_full[blockIdx.x] + sf[threadIdx.x] - mf;
+    unsigned total;
+    long long pc = off_cut[blockIdx.x] + block_excl_scan<4>(mc, wsum[0], total), pf = off_full[blockIdx.x] + block_excl_scan<4>(mf, wsum[1], total);
     for (int e = 0; e < PER; ++e) {
         const long long c = c0 + e;
         if (c >= ncell) break;
@@ -833,8 +786,6 @@ static void quad_gauss(int q, double* x, double* w) {
     }
 }
 
-#define QUAD_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; delete o; return 2; } } while (0)
-
 template <int N, int NC>
 static void quad_launch_cells(bool emit, const QuadArgs& qa, unsigned grid, hipStream_t st, const long long* cand, long long ncand, unsigned* counts,
                               const long long* node_off, const long long* pos, double* coords, double* weights, long long* cells, long long* offs,
@@ -870,7 +821,7 @@ int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long l
     for (int d = 0; d < ndim; ++d) ncell *= n[d] - 1;
     const long long nchunk = (ncell + QUAD_CHUNK - 1) / QUAD_CHUNK;
 
-    QuadObject* o = new QuadObject();
+    std::unique_ptr<QuadObject> o(new QuadObject());
     o->ndim = ndim;
     o->stream = stream;
     for (int d = 0; d < ndim; ++d) o->cell_volume *= h[d];
@@ -879,12 +830,12 @@ int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long l
     DevBuf<long long> off, tot;      // scanned offsets; totals {cut, full, nodes, cut cells with nodes}
     DevBuf<long long> cand, node_off, pos;
     DevBuf<unsigned> nfb;
-    QUAD_HIP(cls.alloc((size_t)ncell), "hipMalloc(cell classes)");
-    QUAD_HIP(cnt.alloc(2 * (size_t)nchunk * sizeof(unsigned)), "hipMalloc(chunk counts)");
-    QUAD_HIP(off.alloc(2 * (size_t)nchunk * sizeof(long long)), "hipMalloc(chunk offsets)");
-    QUAD_HIP(tot.alloc(4 * sizeof(long long)), "hipMalloc(totals)");
-    QUAD_HIP(nfb.alloc(sizeof(unsigned)), "hipMalloc(fallback count)");
-    QUAD_HIP(hipMemsetAsync(nfb, 0, sizeof(unsigned), stream), "fallback count");
+    MOD_HIP(cls.alloc((size_t)ncell), "hipMalloc(cell classes)");
+    MOD_HIP(cnt.alloc(2 * (size_t)nchunk * sizeof(unsigned)), "hipMalloc(chunk counts)");
+    MOD_HIP(off.alloc(2 * (size_t)nchunk * sizeof(long long)), "hipMalloc(chunk offsets)");
+    MOD_HIP(tot.alloc(4 * sizeof(long long)), "hipMalloc(totals)");
+    MOD_HIP(nfb.alloc(sizeof(unsigned)), "hipMalloc(fallback count)");
+    MOD_HIP(hipMemsetAsync(nfb, 0, sizeof(unsigned), stream), "fallback count");
     // 1. classify, scan of the chunk counts
     const unsigned gchunk = (unsigned)nchunk;
 #define QUAD_CLS(NV_, NC_, ND_) hipLaunchKernelGGL((quad_classify_kernel<NV_, NC_, ND_>), dim3(gchunk), dim3(256), 0, stream, qa, ncell, cls.p, cnt.p, cnt.p + nchunk)
@@ -896,45 +847,45 @@ int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long l
         if (ndim == 1) QUAD_CLS(0, 0, 1); else if (ndim == 2) QUAD_CLS(0, 0, 2); else QUAD_CLS(0, 0, 3);
     }
 #undef QUAD_CLS
-    hipLaunchKernelGGL(quad_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt.p, cnt.p + nchunk, nchunk, off.p, off.p + nchunk, tot.p);
+    chunk_scan<2, long long>(stream, {{{cnt.p, off.p, 0}, {cnt.p + nchunk, off.p + nchunk, 0}}}, nchunk, tot.p);
     long long th[4] = {0, 0, 0, 0};
-    QUAD_HIP(hipMemcpyAsync(th, tot, 2 * sizeof(long long), hipMemcpyDeviceToHost, stream), "cell counts");
-    QUAD_HIP(hipStreamSynchronize(stream), "cell counts");
+    MOD_HIP(hipMemcpyAsync(th, tot, 2 * sizeof(long long), hipMemcpyDeviceToHost, stream), "cell counts");
+    MOD_HIP(hipStreamSynchronize(stream), "cell counts");
     const long long ncand = th[0];
     o->nfull = th[1];
     // 2. the ordered lists of candidate cut cells and of full cells
-    QUAD_HIP(cand.alloc((size_t)std::max(ncand, 1LL) * sizeof(long long)), "hipMalloc(cut cells)");
-    QUAD_HIP(o->full.alloc((size_t)std::max(o->nfull, 1LL) * sizeof(long long)), "hipMalloc(full cells)");
+    MOD_HIP(cand.alloc((size_t)std::max(ncand, 1LL) * sizeof(long long)), "hipMalloc(cut cells)");
+    MOD_HIP(o->full.alloc((size_t)std::max(o->nfull, 1LL) * sizeof(long long)), "hipMalloc(full cells)");
     hipLaunchKernelGGL(quad_compact_kernel, dim3(gchunk), dim3(256), 0, stream, cls.p, ncell, off.p, off.p + nchunk, cand.p, o->full.p);
     // 3. nodes per cut cell, scanned: node offsets and the slots of the cells that have nodes
-    QUAD_HIP(cnt.grow((size_t)std::max(ncand, 1LL) * sizeof(unsigned)), "hipMalloc(node counts)");
-    QUAD_HIP(node_off.alloc((size_t)std::max(ncand, 1LL) * sizeof(long long)), "hipMalloc(node offsets)");
-    QUAD_HIP(pos.alloc((size_t)std::max(ncand, 1LL) * sizeof(long long)), "hipMalloc(cell slots)");
+    MOD_HIP(cnt.grow((size_t)std::max(ncand, 1LL) * sizeof(unsigned)), "hipMalloc(node counts)");
+    MOD_HIP(node_off.alloc((size_t)std::max(ncand, 1LL) * sizeof(long long)), "hipMalloc(node offsets)");
+    MOD_HIP(pos.alloc((size_t)std::max(ncand, 1LL) * sizeof(long long)), "hipMalloc(cell slots)");
     const unsigned gcell = (unsigned)std::min<long long>(std::max(ncand, 1LL), 1LL << 20);
 #define QUAD_CELLS(EMIT_, ...) do { \
         if (ndim == 1) quad_launch_cells_n<1>(nc, EMIT_, qa, gcell, stream, cand, ncand, cnt, node_off, pos, __VA_ARGS__, nfb); \
         else if (ndim == 2) quad_launch_cells_n<2>(nc, EMIT_, qa, gcell, stream, cand, ncand, cnt, node_off, pos, __VA_ARGS__, nfb); \
         else quad_launch_cells_n<3>(nc, EMIT_, qa, gcell, stream, cand, ncand, cnt, node_off, pos, __VA_ARGS__, nfb); } while (0)
     if (ncand) QUAD_CELLS(false, nullptr, nullptr, nullptr, nullptr);
-    hipLaunchKernelGGL(quad_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt.p, (const unsigned*)nullptr, ncand, node_off.p, pos.p, tot.p + 2);
+    chunk_scan<2, long long>(stream, {{{cnt.p, node_off.p, 0}, {cnt.p, pos.p, 1}}}, ncand, tot.p + 2);      // pos: the scan of count != 0
     unsigned hfb = 0;
-    QUAD_HIP(hipMemcpyAsync(th + 2, tot.p + 2, 2 * sizeof(long long), hipMemcpyDeviceToHost, stream), "node counts");
-    QUAD_HIP(hipMemcpyAsync(&hfb, nfb, sizeof(unsigned), hipMemcpyDeviceToHost, stream), "node counts");
-    QUAD_HIP(hipStreamSynchronize(stream), "node counts");
+    MOD_HIP(hipMemcpyAsync(th + 2, tot.p + 2, 2 * sizeof(long long), hipMemcpyDeviceToHost, stream), "node counts");
+    MOD_HIP(hipMemcpyAsync(&hfb, nfb, sizeof(unsigned), hipMemcpyDeviceToHost, stream), "node counts");
+    MOD_HIP(hipStreamSynchronize(stream), "node counts");
     o->nnodes = th[2];
     o->ncut = th[3];
     o->nfallback = hfb;
     // 4. the nodes
-    QUAD_HIP(o->cells.alloc((size_t)std::max(o->ncut, 1LL) * sizeof(long long)), "hipMalloc(cells)");
-    QUAD_HIP(o->offsets.alloc((size_t)(o->ncut + 1) * sizeof(long long)), "hipMalloc(offsets)");
-    QUAD_HIP(o->coords.alloc((size_t)std::max(o->nnodes, 1LL) * ndim * sizeof(double)), "hipMalloc(coords)");
-    QUAD_HIP(o->weights.alloc((size_t)std::max(o->nnodes, 1LL) * sizeof(double)), "hipMalloc(weights)");
-    QUAD_HIP(o->sum.alloc(sizeof(double)), "hipMalloc(sum)");
+    MOD_HIP(o->cells.alloc((size_t)std::max(o->ncut, 1LL) * sizeof(long long)), "hipMalloc(cells)");
+    MOD_HIP(o->offsets.alloc((size_t)(o->ncut + 1) * sizeof(long long)), "hipMalloc(offsets)");
+    MOD_HIP(o->coords.alloc((size_t)std::max(o->nnodes, 1LL) * ndim * sizeof(double)), "hipMalloc(coords)");
+    MOD_HIP(o->weights.alloc((size_t)std::max(o->nnodes, 1LL) * sizeof(double)), "hipMalloc(weights)");
+    MOD_HIP(o->sum.alloc(sizeof(double)), "hipMalloc(sum)");
     if (o->ncut) QUAD_CELLS(true, o->coords.p, o->weights.p, o->cells.p, o->offsets.p);
 #undef QUAD_CELLS
-    QUAD_HIP(hipMemcpyAsync(o->offsets.p + o->ncut, &o->nnodes, sizeof(long long), hipMemcpyHostToDevice, stream), "offsets");
-    QUAD_HIP(hipGetLastError(), "quadrature: launch failed");
-    QUAD_HIP(hipStreamSynchronize(stream), "quadrature: device error");
+    MOD_HIP(hipMemcpyAsync(o->offsets.p + o->ncut, &o->nnodes, sizeof(long long), hipMemcpyHostToDevice, stream), "offsets");
+    MOD_HIP(hipGetLastError(), "quadrature: launch failed");
+    MOD_HIP(hipStreamSynchronize(stream), "quadrature: device error");
     // the tensor rule of a full cell on [0, 1]^N, in the order and with the products of the device's tensor rule
     int m = 1;
     for (int d = 0; d < ndim; ++d) m *= q;
@@ -953,10 +904,9 @@ int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long l
         o->rule_w[p] = w;
     }
     counts_out[0] = o->ncut; counts_out[1] = o->nnodes; counts_out[2] = o->nfull; counts_out[3] = o->nfallback;
-    *out = o;
+    *out = o.release();
     return 0;
 }
-#undef QUAD_HIP
 
 int quad_read(QuadObject* o, long long* cells, long long* offsets, double* coords, double* weights, long long* full, double* rule_x, double* rule_w,
               const char** err) {

@@ -25,9 +25,11 @@
 // contracts to fma.
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "lsm_handle.h"
+#include "scan.h"     // lsm_quad.hip's scans of chunk and node counts
 #include "wave.h"
 
 namespace lsm {

@@ -237,8 +237,6 @@ __global__ void __launch_bounds__(256) vol_element_kernel(KuhnArgs a, const unsi
 }
 
 // ---- host side
-#define VOL_HIP(call, what) do { if ((call) != hipSuccess) { *err = what; return 2; } } while (0)
-
 struct VolObject {
     DevBuf<double> verts;
     DevBuf<long long> elems, iface;
@@ -255,8 +253,8 @@ int vol_build(const LsmHandle* h, double level, const void* phi, VolObject** out
     KuhnWork w;
     DevBuf<unsigned char> icnt;     // whole chunks
     if (const int r = kuhn_begin(h, level, phi, nullptr, 1LL << 19, msg, w, err)) return r;     // 2^31 nodes: one vertex kernel launch
-    VOL_HIP(icnt.alloc((size_t)w.nchunk * KUHN_CHUNK), "hipMalloc(interface counts)");
-    KUHN_LAUNCH(ndim, vol_classify_kernel, (unsigned)w.nchunk, stream, w.a, w.emask.p, w.ecnt.p, icnt.p, w.sums.p, w.nchunk);
+    MOD_HIP(icnt.alloc((size_t)w.nchunk * KUHN_CHUNK), "hipMalloc(interface counts)");
+    LSM_LAUNCH_ND(ndim, vol_classify_kernel, (unsigned)w.nchunk, 256, stream, w.a, w.emask.p, w.ecnt.p, icnt.p, w.sums.p, w.nchunk);
     if (const int r = kuhn_totals(w, stream, msg, err)) return r;
     const KuhnArgs& a = w.a;
     std::unique_ptr<VolObject> o(new VolObject());
@@ -268,17 +266,17 @@ int vol_build(const LsmHandle* h, double level, const void* phi, VolObject** out
     if (o->nv) {
         const unsigned gchunk = (unsigned)w.nchunk;
         DevBuf<unsigned> vbase;     // first vertex of every node
-        VOL_HIP(vbase.alloc((size_t)w.nchunk * KUHN_CHUNK * sizeof(unsigned)), "hipMalloc(vertex offsets)");
-        VOL_HIP(o->verts.alloc((size_t)o->nv * ndim * sizeof(double)), "hipMalloc(vertices)");
-        VOL_HIP(o->elems.alloc((size_t)std::max(o->ne, 1LL) * (ndim + 1) * sizeof(long long)), "hipMalloc(elements)");
-        VOL_HIP(o->iface.alloc((size_t)std::max(o->ni, 1LL) * ndim * sizeof(long long)), "hipMalloc(interface elements)");
+        MOD_HIP(vbase.alloc((size_t)w.nchunk * KUHN_CHUNK * sizeof(unsigned)), "hipMalloc(vertex offsets)");
+        MOD_HIP(o->verts.alloc((size_t)o->nv * ndim * sizeof(double)), "hipMalloc(vertices)");
+        MOD_HIP(o->elems.alloc((size_t)std::max(o->ne, 1LL) * (ndim + 1) * sizeof(long long)), "hipMalloc(elements)");
+        MOD_HIP(o->iface.alloc((size_t)std::max(o->ni, 1LL) * ndim * sizeof(long long)), "hipMalloc(interface elements)");
         hipLaunchKernelGGL(vol_offset_kernel, dim3(gchunk), dim3(256), 0, stream, w.emask.p, w.off.p, vbase.p);
         const unsigned gnode = (unsigned)((a.nnode + 255) / 256);
-        KUHN_LAUNCH(ndim, vol_vertex_kernel, gnode, stream, a, w.emask.p, vbase.p, o->verts.p);
-        KUHN_LAUNCH(ndim, vol_element_kernel, gchunk, stream, a, w.emask.p, w.ecnt.p, icnt.p, vbase.p, w.off.p, w.nchunk, o->elems.p, o->iface.p);
+        LSM_LAUNCH_ND(ndim, vol_vertex_kernel, gnode, 256, stream, a, w.emask.p, vbase.p, o->verts.p);
+        LSM_LAUNCH_ND(ndim, vol_element_kernel, gchunk, 256, stream, a, w.emask.p, w.ecnt.p, icnt.p, vbase.p, w.off.p, w.nchunk, o->elems.p, o->iface.p);
     }
-    VOL_HIP(hipGetLastError(), "volume_mesh: launch failed");
-    VOL_HIP(hipStreamSynchronize(stream), "volume_mesh: device error");     // the work buffers are released on return
+    MOD_HIP(hipGetLastError(), "volume_mesh: launch failed");
+    MOD_HIP(hipStreamSynchronize(stream), "volume_mesh: device error");     // the work buffers are released on return
     counts_out[0] = o->nv;
     counts_out[1] = o->ne;
     counts_out[2] = o->ni;
@@ -293,6 +291,5 @@ int vol_read(VolObject* o, double* verts, long long* elems, long long* iface, co
 }
 
 void vol_free(VolObject* o) { delete o; }
-#undef VOL_HIP
 
 }  // namespace lsm

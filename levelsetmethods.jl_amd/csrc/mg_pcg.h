@@ -379,12 +379,6 @@ static unsigned mg_blocks(long long n) { return (unsigned)std::min<long long>((n
 #define MG_LAUNCH2(N, kernel, A, ...) MG_LAUNCH_AS(N, (kernel<2, A>), (kernel<3, A>), __VA_ARGS__)
 #define MG_LAUNCH3(N, kernel, A, B, ...) MG_LAUNCH_AS(N, (kernel<2, A, B>), (kernel<3, A, B>), __VA_ARGS__)
 
-#define MG_HIP(h, call)                                                                                       \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) return lsm_fail(h, LSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 template <class Level>
 struct MgSolver {
     int N = 0, precond = 0, last_iters = 0;
@@ -450,12 +444,12 @@ static size_t mg_ncells(int N, const Level& L) {
 // the reduction partials, the device state with its pinned copy and nstat setup counters, all zero
 template <class Level>
 static int mg_alloc_scalars(LsmHandle* h, MgSolver<Level>& o, int nstat, hipStream_t s) {
-    MG_HIP(h, o.partial.alloc(4 * MG_MAXB * sizeof(double)));
-    MG_HIP(h, o.st.alloc(sizeof(MgState)));
-    MG_HIP(h, o.cnt.alloc(nstat * sizeof(unsigned long long)));
-    MG_HIP(h, o.h_st.alloc(sizeof(MgState)));
-    MG_HIP(h, hipMemsetAsync(o.cnt.p, 0, nstat * sizeof(unsigned long long), s));
-    MG_HIP(h, hipMemsetAsync(o.st.p, 0, sizeof(MgState), s));
+    LSM_HIP(h, o.partial.alloc(4 * MG_MAXB * sizeof(double)));
+    LSM_HIP(h, o.st.alloc(sizeof(MgState)));
+    LSM_HIP(h, o.cnt.alloc(nstat * sizeof(unsigned long long)));
+    LSM_HIP(h, o.h_st.alloc(sizeof(MgState)));
+    LSM_HIP(h, hipMemsetAsync(o.cnt.p, 0, nstat * sizeof(unsigned long long), s));
+    LSM_HIP(h, hipMemsetAsync(o.st.p, 0, sizeof(MgState), s));
     o.V.partial = o.partial;
     o.V.st = o.st;
     return LSM_OK;
@@ -502,7 +496,7 @@ static int mg_reset(LsmHandle* h, MgSolver<Level>& o, double rtol, int max_iters
     memset(&s0, 0, sizeof(s0));
     s0.rtol2 = rtol * rtol;
     s0.max_iters = max_iters;
-    MG_HIP(h, hipMemcpyAsync(o.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+    LSM_HIP(h, hipMemcpyAsync(o.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
     return LSM_OK;
 }
 
@@ -515,9 +509,9 @@ static int mg_iterate(LsmHandle* h, MgSolver<Level>& o, int max_iters, hipStream
     for (;;) {
         const int k = std::min(chunk, max_iters - enq);
         for (int it = 0; it < k; ++it, ++enq) enqueue(enq);
-        MG_HIP(h, hipGetLastError());
-        MG_HIP(h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
-        MG_HIP(h, hipStreamSynchronize(st));
+        LSM_HIP(h, hipGetLastError());
+        LSM_HIP(h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+        LSM_HIP(h, hipStreamSynchronize(st));
         if (o.h_st.p->status != MG_RUN || enq >= max_iters) break;
         chunk = std::min(2 * chunk, 64);
     }

@@ -1,6 +1,7 @@
 // wave.h — the cross-lane building blocks of the device modules, one definition each: wave reductions and scan, the wave- and
-// workgroup-aggregated append, the workgroup scan and the ordered (deterministic) fp64 grid reduction.  Wave64, one-dimensional
-// workgroups of whole waves.  The stage kernels keep their own code and do not include this file.
+// workgroup-aggregated append, the workgroup sum and scan and the ordered (deterministic) fp64 grid reduction.  Wave64,
+// one-dimensional workgroups of whole waves.  scan.h builds the one-workgroup scan of the chunk sums on the workgroup scan.  The
+// stage kernels keep their own code and do not include this file; lsm_comm.hip keeps its own sum and scan of chunk counts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,8 +51,21 @@ __device__ __forceinline__ T wave_incl_scan(T v) {
     return v;
 }
 
-// exclusive prefix sum of v over a workgroup of NWAVES waves, and its total in every thread.  wsum: NWAVES words of LDS, which the
+// the sum of v over a workgroup of NWAVES waves, in every thread: one barrier, no atomics.  wsum: NWAVES words of LDS, which the
 // caller leaves alone until the workgroup's next barrier.  Every thread of the workgroup calls this.
+template <int NWAVES, class T>
+__device__ __forceinline__ T block_sum(T v, T* wsum) {
+    const T s = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    T total = 0;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) total += wsum[w];
+    return total;
+}
+
+// exclusive prefix sum of v over a workgroup of NWAVES waves, and its total in every thread.  wsum as for block_sum.  Every
+// thread of the workgroup calls this.
 template <int NWAVES, class T>
 __device__ __forceinline__ T block_excl_scan(T v, T* wsum, T& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -208,6 +208,30 @@ def test_workspace_reuse_small_after_large():
     _check(lsm.components(_field(lsm, vals2, lc2, hc2)), reference("one_tile_3d"), vals2 < 0)
 
 
+def test_root_counts_of_more_than_8192_chunks():
+    """(4097, 8194) nodes, 8197 numbering chunks: the scan of the roots per chunk (csrc/scan.h with 32-bit offsets, the total
+    into the counters) runs a second round, which receives a carry.  ϕ = 1 but for 90 single nodes of ϕ = −1, no two of them Kuhn
+    neighbours, half in the first chunks and half in rows 8191..8193: K, the labels (ascending by node index), the sizes, the
+    index sums and the bounding boxes follow from the positions.  A dropped carry numbers the roots of chunk 8192 and beyond from
+    0 again, or loses them from K."""
+    import _chunk_carry as CC
+    lsm = _lsm()
+    I, J, lin = CC.isolated_nodes()
+    vals = np.ones(CC.N, dtype=np.float32, order="F")
+    vals[I, J] = -1.0
+    c = lsm.components(_field(lsm, vals, (0.0, 0.0), tuple(float(m - 1) for m in CC.N), dtype=np.float32))
+    K = len(lin)
+    print(f"K {c.count}, stats {c.stats}")
+    assert c.count == K and c.stats == (K, K, 0, 0)
+    lab = c.labels()
+    assert lab.shape == CC.N and int(np.count_nonzero(lab != -1)) == K and np.array_equal(lab[I, J], np.arange(K))
+    far = lin // CC.CHUNK >= CC.SCAN
+    assert far.any() and (lab[I[far], J[far]] == np.flatnonzero(far)).all() and np.flatnonzero(far)[0] == int((~far).sum()) > 0
+    pos = np.stack([I, J], axis=1)
+    assert np.array_equal(c.nodes, np.ones(K, dtype=np.int64)) and np.array_equal(c.index_sums, pos)
+    assert np.array_equal(c.bbox, np.stack([pos, pos], axis=1))
+
+
 # ----------------------------------------------------------------------------- remove_components_ and prune_
 
 @pytest.mark.parametrize("dtype", (np.float64, np.float32), ids=("f64", "f32"))

@@ -183,6 +183,58 @@ def test_disk_1030_by_515_independent_checks():
     assert np.array_equal(again.vertices, m.vertices) and np.array_equal(again.elements, m.elements)
 
 
+def _loops(elems):
+    """the number of cycles of the map start vertex -> end vertex of the segments (a closed curve: a permutation)"""
+    nxt = np.empty(len(elems), dtype=np.int64)
+    nxt[elems[:, 0]] = elems[:, 1]
+    seen, count = np.zeros(len(elems), dtype=bool), 0
+    for v in range(len(elems)):
+        if not seen[v]:
+            count += 1
+            while not seen[v]:
+                seen[v] = True
+                v = nxt[v]
+    return count
+
+
+def test_chunk_sums_of_more_than_8192_chunks():
+    """(4097, 8194) nodes, 8197 chunks: the scan of the three rows of chunk sums (csrc/scan.h; volume_mesh shares it) runs a second
+    round, which receives a carry.  Two circles of radius 8.48 nodes, one in rows 1..18 and one in rows 8175..8192, on a
+    field that is 3 elsewhere (h = 1, float32 storage).  Checked without the restatement: every vertex is the start of one segment
+    and the end of one, the segments form two loops, the elements come ascending by their cell, and the length is that of the two
+    circles to second order: h/r is the 33-grid's of test_disk_1030_by_515_independent_checks (h = 2/32, r = 0.53), whose 7.0e-4
+    with its margin of 1.5 is the bound.  A dropped carry puts the vertices, elements and list entries of chunk 8192 and beyond on
+    top of the first circle's, or loses them from the totals."""
+    import _chunk_carry as CC
+    lsm = _lsm()
+    n, r = CC.N, DISK_R / (2 / 32)
+    vals = np.full(n, 3.0, dtype=np.float32, order="F")
+    windows = []
+    for cx, cy in ((1500.3, 9.6), (2901.6, n[1] - 1 - 9.3)):
+        i0, i1, j0, j1 = int(cx) - 13, int(cx) + 15, max(int(cy) - 13, 0), min(int(cy) + 15, n[1])
+        X, Y = np.meshgrid(np.arange(i0, i1), np.arange(j0, j1), indexing="ij")
+        vals[i0:i1, j0:j1] = np.minimum(3.0, np.hypot(X - cx, Y - cy) - r)
+        windows.append((i0, i1, j0, j1))
+    assert all((vals[a:b, c:d] != 0.0).all() for a, b, c, d in windows)
+    m = lsm.isosurface(_device(lsm, vals, (0.0, 0.0), tuple(float(k - 1) for k in n), dtype=np.float32))
+    v, e = m.vertices, m.elements
+    assert len(v) == sum(count_sign_changes(vals[a:b, c:d]) for a, b, c, d in windows) and len(e) == len(v) > 0
+    assert e.min() == 0 and e.max() == len(v) - 1
+    assert_closed_curve(v, e)
+    assert _loops(e) == 2
+    assert R.enclosed(v, e) > 0
+    mid = 0.5 * (v[e[:, 0]] + v[e[:, 1]])                 # inside the segment's cell: h = 1, the lower corner at 0
+    cell = np.floor(mid).astype(np.int64)
+    owner = cell[:, 0] + n[0] * cell[:, 1]
+    assert (np.diff(owner) >= 0).all()
+    chunk = owner // CC.CHUNK
+    print(f"{len(v)} vertices; {int((chunk < 20).sum())} elements in chunks below 20, {int((chunk >= CC.SCAN).sum())} in chunks from {CC.SCAN}")
+    assert (chunk < 20).any() and (chunk >= CC.SCAN).any()
+    err = m.measure() / (2 * 2 * math.pi * r) - 1
+    print(f"relative length error of the two circles: {err:.3e}")
+    assert -7.0e-4 * 1.5 <= err < 0
+
+
 # ----------------------------------------------------------------------------- through the API
 
 def test_equation_after_steps_and_stale_ghosts():

@@ -4,7 +4,8 @@ closed form of the stripes1 fixture, and row against row on the stripes3 fixture
 fixtures' conditions on the CPU).  Tolerances are _compare's: 1e-12 on coordinates, 1e-12·max(1, max |w|) on weights.
 
   A  classify / compaction: several chunks of 4096 cells, a partial last chunk, a chunk with nothing in it
-  B  quad_scan_kernel: a second round of 8192 values in the node-offset scan and in the scan of count != 0 (in1 == NULL)
+  B  chunk_scan_kernel (csrc/scan.h): a second round of 8192 values in the node-offset scan and in the scan of count != 0 (the
+     row with `nonzero` set)
   C  quad_cells_kernel: more than 2^20 candidates, so a workgroup takes a second cell (an empty candidate on either trip)
   D  more than 8192 chunks: the scan of the chunk counts carries into chunk 8192
   E  subdivision to the depth limit and the fallback in 3-D and with h_x != h_y (the first longest side is not a tie)
@@ -23,7 +24,7 @@ from test_quadrature_host import KINKS, kink, restated, row_pattern, stripes1, s
 
 pytestmark = pytest.mark.gpu
 
-CHUNK, SCAN, GRID = 4096, 8192, 1 << 20     # QUAD_CHUNK, values per round of quad_scan_kernel, the cell kernel's launch cap
+CHUNK, SCAN, GRID = 4096, 8192, 1 << 20     # QUAD_CHUNK, values per round of chunk_scan_kernel, the cell kernel's launch cap
 
 
 def _quad(lsm, phi, k, q, surface):

@@ -183,6 +183,28 @@ def test_the_centre_list_is_the_restatements(name):
     assert np.array_equal(T._bits(p.values()), T._bits(phi))      # the search writes nothing
 
 
+def test_the_centre_counts_of_more_than_8192_chunks():
+    """(4097, 8194) nodes, 8197 chunks: the scan of the centres per chunk (csrc/scan.h with 64-bit offsets) runs a second round,
+    which receives a carry.  ϕ = −1 (material, a clearance of 1 to the level), t = 1 but for 90 nodes below the threshold, any
+    two farther apart than the window of 3 nodes (spacing 2.5, h = 1): each is the only candidate of its window, so a centre.
+    Half lie in the first chunks, half in rows 8191..8193.  A dropped carry writes the centres of chunk 8192 and beyond over the
+    first ones, or loses them from the count."""
+    import _chunk_carry as CC
+    lsm = T._lsm()
+    cs = _grid_case(CC.N, tuple(float(m - 1) for m in CC.N), np.float32)
+    I, J, lin = CC.isolated_nodes()
+    t = np.ones(CC.N, dtype=np.float32, order="F")
+    values = (-(1.0 + np.arange(len(lin))[::-1] / 128.0)).astype(np.float32)      # exact in float32, descending along the list
+    t[I, J] = values
+    spacing = 2.5
+    assert TR.window(spacing, cs["h"]) == (3, 3)
+    p, q = _fields(lsm, cs, np.full(CC.N, -1.0, dtype=np.float32, order="F"), t)
+    idx, val = p.backend.nucleate_find(p.buf, q.buf, 0.5, 0.0, 0.25, spacing)
+    print(f"{idx.size} centres, {int((idx // CC.CHUNK >= CC.SCAN).sum())} of them in chunks >= {CC.SCAN}")
+    assert idx.dtype == np.int64 and np.array_equal(idx, lin) and np.array_equal(T._bits(val), T._bits(values.astype(np.float64)))
+    assert (idx // CC.CHUNK >= CC.SCAN).any() and (idx // CC.CHUNK < 20).any()
+
+
 def _padded_bits(f):
     t = f.backend.torch
     return f.buf.view(t.int64 if f.buf.dtype == t.float64 else t.int32).clone()

@@ -131,7 +131,7 @@ def kernel_stats(dirname):
     f = glob.glob(dirname + "/**/*kernel_stats.csv", recursive=True)[0]
     out = {}
     for r in csv.DictReader(open(f)):
-        m = re.search(r"\bcc_\w+_kernel", r["Name"].split("(")[0])
+        m = re.search(r"\b(cc_\w+|chunk_scan)_kernel", r["Name"].split("(")[0])      # chunk_scan: the shared scan (csrc/scan.h)
         if not m:
             continue
         e = out.setdefault(m.group(0), {"dispatches": 0, "total_ms": 0.0})

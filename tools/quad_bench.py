@@ -77,7 +77,7 @@ def trace(dirname, name):
     out = {}
     for r in csv.DictReader(open(f)):
         kname = r["Name"].split("(")[0]
-        if "quad" not in kname:
+        if "quad" not in kname and "chunk_scan_kernel" not in kname:      # chunk_scan: the shared scan (csrc/scan.h)
             continue
         e = out.setdefault(kname.replace("void ", ""), {"dispatches": 0, "total_ms": 0.0})
         e["dispatches"] += int(r["Calls"])

@@ -90,7 +90,7 @@ def kernel_stats(dirname):
     out = {}
     for r in csv.DictReader(open(f)):
         kname = r["Name"].split("(")[0].replace("void ", "")
-        if "vol_" not in kname and "kuhn_" not in kname:     # kuhn_: the scan of the chunk sums, shared with isosurface
+        if "vol_" not in kname and "kuhn_" not in kname and "chunk_scan_kernel" not in kname:     # the scan of the chunk sums is shared (csrc/scan.h)
             continue
         e = out.setdefault(kname, {"dispatches": 0, "total_ms": 0.0})
         e["dispatches"] += int(r["Calls"])
