@@ -656,6 +656,68 @@ int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const
 int lsm_elastic_cells(LsmElastic* s, double* e_out_cells);
 void lsm_elastic_destroy(LsmElastic* s);
 
+/* ---- homogenize: the effective elasticity tensor C^H of the periodic material whose cell is the box of a dense 2-D or 3-D grid,
+ *      and its sensitivity (csrc/lsm_homog.hip; tests/_homog_ref.py restates every operation).  Shapes, ownership,
+ *      streams and failures are lsm_elastic_*'s unless stated.
+ *      The torus.  m_d = n_d − 1 cells per axis; the period is m_d cells, node n_d − 1 is node 0 (the reference's periodic
+ *      convention, src/boundaryconditions.jl:107-119).  The unknowns live on the nn = m_0·m_1(·m_2) nodes of the torus, id = I0 +
+ *      m0·(I1 + m1·I2); cell C (lowest corner C) has the same linear index.  Every node has all 2^N cells around it: cell index
+ *      I_d − 1 wraps to m_d − 1, corner C_d + 1 wraps to 0.  The handle's boundary conditions are not read: only phi's cells are.
+ *      Cell moduli, the material, plane and K0: lsm_elastic's, the same code and the same bits; the cell array is n − 1-shaped.
+ *      Operator: lsm_elastic's sums in lsm_elastic's order over the wrapped cells and nodes; no cell is missing.  Diagonal likewise.
+ *      Unit strains, M = N(N+1)/2, in Voigt order: 2-D (00, 11, 01); 3-D (00, 11, 22, 12, 02, 01); shears are engineering shears
+ *      gamma = 1.  The cell-local affine field chi0^k at a cell's corners (corner a at x_d = bit_d(a)·h_d): normal strain ii:
+ *      component i = x_i; shear ij: component i = x_j/2, component j = x_i/2; all else zero.  g^k = K0·chi0^k, each row summed from
+ *      +0 ascending, on the host.  Load: f^k_{I,i} = −(sum over the cells C around I, ascending as in the operator, from +0, of
+ *      E_C·g^k[(a, i)]), a = I's corner in C.  lsm_homog_load writes all N·nn entries, node 0's included.
+ *      Correctors: chi^k is periodic with its N components zero at node 0 (the pin) and solves A chi^k = f^k on the others, by
+ *      lsm_elastic's PCG (b = f^k: no node mass on a torus).  w^k_C = chi0^k + chi^k at the corners of C;
+ *      t^{pq}_C = E_C·(sum_r w^p_r·(sum_s K0[r,s]·w^q_s)), both sums from +0 ascending; C^H_pq = (sum_C t^{pq}_C)/ncells (K0 carries
+ *      1/prod h: the mean energy density).  lsm_homog_tensor forms K0·w^q once per q and the sums for p ≤ q in one pass, reduced in
+ *      workgroup order, and mirrors them: C is M·M doubles on the host, exactly symmetric, and two calls give the same bits.
+ *      Hierarchy: axis d coarsens while m_d is even and m_d > 4, to m_d/2 with 2h; it ends when no axis coarsens.  A coarse cell is
+ *      the mean of cells 2J and 2J+1 per coarsened axis (lsm_elastic's average).  Restriction r_c[J] = 2^−k·sum_o w_o·res[(2J + o)
+ *      mod m], w = 1 at o = 0 and 1/2 at o = ±1 per coarsened axis; prolongation its transpose without the 2^−k.  Node 0 is pinned
+ *      on every level.  omega_l = min(0.6, 1.9/lambda_l) as in lsm_elastic.  Smoother 2 + 2 sweeps; the coarsest level runs 16
+ *      sweeps from zero: in one workgroup with at most 128 nodes, else (an odd m_d on a large axis) as 16 launches of the smoother,
+ *      the same arithmetic.  No shape is refused but an axis with m_d < 2.
+ *      stats[4] (may be NULL) := {levels, free components, nodes of the torus, 0}; after the setup kernel refused the data
+ *      {−reason, offending entries, 0, 0}: a non-finite phi (1, counted over all n nodes), a cell modulus not finite and
+ *      positive (2).  LSM_ERR_INVALID without running anything: a 1-D grid, a slab handle or one with a communicator, fewer than 3
+ *      nodes in a dimension, bad e_in / e_out / level / nu / plane / precond.
+ *      lsm_homog_apply: y = A x over N·nn device doubles, component-major, no pin.  lsm_homog_cells: the cell moduli, device.
+ *      lsm_homog_solve: all M correctors from chi_guess (M·N·nn fp64, host or device; node 0's entries are taken as zero; NULL:
+ *      from zero); iters[M] and relres[M] (may be NULL) per corrector.  The stored correctors change only when all M solves have
+ *      converged: LSM_ERR_NOT_CONVERGED or a non-finite guess (LSM_ERR_INVALID) leaves them untouched, with iters and relres set up
+ *      to the solve that failed.  A new object holds zero correctors.  lsm_homog_set_correctors / lsm_homog_correctors copy all of
+ *      them from / to fp64 memory of the caller (host or device), shape (M, N) + m.
+ *      lsm_homog_solve_rhs: the same PCG for a caller's right-hand side, A x = f away from the pin (f, x: N·nn device doubles; x in:
+ *      the guess, node 0's entries taken as zero; out: the solution); the stored correctors are not touched, and a failure leaves x
+ *      untouched.  For diagnostics and tests of the V-cycle.
+ *      lsm_homog_energy_cells: t^{pq}_C of every cell into ncells device doubles, from the stored correctors.
+ *      lsm_homog_corrector: chi^k into N distinct dense fields of the handle, image nodes n − 1 from node 0, rounded once.
+ *      lsm_homog_sensitivity: W is M·M host doubles, finite and symmetric.  cell_C = sum_q sum_{p ≤ q} c·W[p·M + q]·t^{pq}_C, c = 2
+ *      for p < q and 1 for p = q (the tensor's own pairs: t^{qp} is t^{pq}), q ascending and within it p ascending, from +0, the
+ *      product as (c·W)·t (K0·w^q once per q); g_I = (sum over the cells C around I, ascending,
+ *      from +0, of cell_C)·2^−N at every node of the handle's grid (node n − 1 is node 0), rounded once into a dense field: the
+ *      integrand of d(W:C^H)/dOmega in lsm_elastic_energy's node-mean convention. */
+typedef struct LsmHomog LsmHomog;
+int lsm_homog_create(LsmHandle* h, const void* phi, double level, double e_in, double e_out, const double* e_cells, double nu, int plane,
+                     int precond, LsmHomog** out, int64_t stats[4]);
+int lsm_homog_stiffness(LsmHomog* s, int level, double* k0_host);
+int lsm_homog_cells(LsmHomog* s, double* e_out_cells);
+int lsm_homog_apply(LsmHomog* s, const double* x, double* y);
+int lsm_homog_load(LsmHomog* s, int k, double* f_out);
+int lsm_homog_solve(LsmHomog* s, const double* chi_guess, double rtol, int max_iters, int* iters, double* relres);
+int lsm_homog_solve_rhs(LsmHomog* s, const double* f, double* x, double rtol, int max_iters, int* iters, double* relres);
+int lsm_homog_set_correctors(LsmHomog* s, const double* chi);
+int lsm_homog_correctors(LsmHomog* s, double* chi_out);
+int lsm_homog_energy_cells(LsmHomog* s, int p, int q, double* out);
+int lsm_homog_tensor(LsmHomog* s, double* C);
+int lsm_homog_corrector(LsmHomog* s, int k, void* u0, void* u1, void* u2);
+int lsm_homog_sensitivity(LsmHomog* s, const double* W, void* g_out);
+void lsm_homog_destroy(LsmHomog* s);
+
 /* ---- elasticity_modes: the m smallest eigenpairs of A x = lambda·M x for the ersatz-material structure of an LsmElastic — its
  *      vibration modes, lambda = omega² — by a locally optimal block preconditioned CG (LOBPCG) whose preconditioner T is the
  *      object's V-cycle, or 1/D for LSM_PRECOND_JACOBI (csrc/lsm_elastic.hip; tests/_modes_ref.py restates it).

@@ -669,6 +669,65 @@ elasticity_cells!(a, K) = _check(K.h.ptr, ccall((:lsm_elastic_cells, libhiplsm),
 
 destroy_elasticity(K) = ccall((:lsm_elastic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), K.op)
 
+# homogenize: the effective elasticity tensor of the periodic material whose cell is the box of ϕ (include/lsm.h, lsm_homog_*).  The torus
+# has m = n .- 1 nodes per axis; M = N(N+1)/2 unit strains in Voigt order.  Release the object with destroy_homogenization.
+function homogenization(ϕ::ROCMeshField; level = 0.0, E_in = 1.0, E_out = 1e-3, E = nothing, nu = 0.3, plane = :stress, precond = :mg)
+    out, stats = Ref{Ptr{Cvoid}}(), zeros(Int64, 4)
+    _check(ϕ.h.ptr, ccall((:lsm_homog_create, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Float64}, Float64, Cint, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), level, E_in, E_out, E === nothing ? C_NULL : pointer(E), nu, plane === :strain ? 1 : 0,
+        precond === :jacobi ? 1 : 0, out, stats), "lsm_homog_create")
+    return (; op = out[], h = ϕ.h, levels = stats[1], free = stats[2], nodes = stats[3])
+end
+
+function homogenization_stiffness(H, level, N)
+    R = (1 << N) * N
+    k0 = zeros(Float64, R, R)
+    _check(H.h.ptr, ccall((:lsm_homog_stiffness, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), H.op, level, k0), "lsm_homog_stiffness")
+    return k0
+end
+
+# the cell moduli into a ROCArray{Float64} of size n .- 1; y = A x and the load of unit strain k (0-based) over ROCArray{Float64}s of N·nn values
+homogenization_cells!(a, H) = _check(H.h.ptr, ccall((:lsm_homog_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, pointer(a)), "lsm_homog_cells")
+homogenization_apply!(y, H, x) = _check(H.h.ptr, ccall((:lsm_homog_apply, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), H.op, pointer(x), pointer(y)), "lsm_homog_apply")
+homogenization_load!(f, H, k) = _check(H.h.ptr, ccall((:lsm_homog_load, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), H.op, k, pointer(f)), "lsm_homog_load")
+
+# all M correctors, from `guess` (a Float64 array of M·N·nn values, host or device) or from zero; a failure leaves the stored ones untouched
+function homogenization_solve!(H, M; guess = nothing, rtol = 1e-8, max_iters = 500)
+    iters, relres = zeros(Cint, M), zeros(Float64, M)
+    _check(H.h.ptr, ccall((:lsm_homog_solve, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64, Cint, Ptr{Cint}, Ptr{Float64}),
+        H.op, guess === nothing ? C_NULL : pointer(guess), rtol, max_iters, iters, relres), "lsm_homog_solve")
+    return (; iterations = iters, relres = relres)
+end
+
+# A x = f away from the pinned node for a right-hand side of the caller's (x, f: ROCArray{Float64} of N·nn values; x holds the guess, then the solution)
+function homogenization_solve_rhs!(x, H, f; rtol = 1e-8, max_iters = 500)
+    iters, relres = Ref{Cint}(0), Ref{Float64}(0.0)
+    _check(H.h.ptr, ccall((:lsm_homog_solve_rhs, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Cint, Ref{Cint}, Ref{Float64}),
+        H.op, pointer(f), pointer(x), rtol, max_iters, iters, relres), "lsm_homog_solve_rhs")
+    return (; iterations = iters[], relres = relres[])
+end
+
+homogenization_set_correctors!(H, chi) = _check(H.h.ptr, ccall((:lsm_homog_set_correctors, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, pointer(chi)), "lsm_homog_set_correctors")
+homogenization_correctors!(chi, H) = _check(H.h.ptr, ccall((:lsm_homog_correctors, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, pointer(chi)), "lsm_homog_correctors")
+homogenization_energy_cells!(t, H, p, q) = _check(H.h.ptr, ccall((:lsm_homog_energy_cells, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}), H.op, p, q, pointer(t)), "lsm_homog_energy_cells")
+
+# C^H, an M×M host matrix (symmetric)
+function homogenization_tensor(H, M)
+    C = zeros(Float64, M, M)
+    _check(H.h.ptr, ccall((:lsm_homog_tensor, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, C), "lsm_homog_tensor")
+    return C
+end
+
+# corrector k (0-based) into the N fields u; the integrand of d(W:C^H)/dΩ into the field g: the normal speed of a descent on W:C^H
+function homogenization_corrector!(u, H, k)
+    p = _u3(u)
+    _check(H.h.ptr, ccall((:lsm_homog_corrector, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), H.op, k, p[1], p[2], p[3]), "lsm_homog_corrector")
+end
+homogenization_sensitivity!(g::ROCMeshField, H, W::Matrix{Float64}) = _check(H.h.ptr, ccall((:lsm_homog_sensitivity, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), H.op, W, pointer(g.buf)), "lsm_homog_sensitivity")
+
+destroy_homogenization(H) = ccall((:lsm_homog_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), H.op)
+
 # elasticity_modes: the m ≤ 8 lowest vibration modes K u = λ M u of an elasticity_operator K (include/lsm.h, lsm_elastic_modes_*).  The
 # density of a cell is rho_out + (rho_in − rho_out)·θ(ϕ), or `rho` (a ROCArray{Float64} of size n .- 1, required when K was built from
 # `E`).  The object borrows K, which must outlive it; release it with destroy_modes.

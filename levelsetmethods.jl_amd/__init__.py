@@ -18,7 +18,8 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
                   components, remove_components_, prune_, Components, nucleate_, find_nucleation_sites, Nucleation,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
-                  elasticity_solve, ElasticityOperator, ElasticitySolution, elasticity_modes, ElasticityModes, StressSensitivity)
+                  elasticity_solve, ElasticityOperator, ElasticitySolution, elasticity_modes, ElasticityModes, StressSensitivity,
+                  homogenize, Homogenization)
 
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
@@ -34,4 +35,5 @@ __all__ = [
     "components", "remove_components_", "prune_", "Components", "nucleate_", "find_nucleation_sites", "Nucleation",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
     "elasticity_solve", "ElasticityOperator", "ElasticitySolution", "elasticity_modes", "ElasticityModes", "StressSensitivity",
+    "homogenize", "Homogenization",
 ]

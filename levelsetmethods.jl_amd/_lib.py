@@ -171,6 +171,21 @@ _SIGS = [
     ("lsm_elastic_compliance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("lsm_elastic_cells", C.c_int, [C.c_void_p, C.c_void_p]),
     ("lsm_elastic_destroy", None, [C.c_void_p]),
+    ("lsm_homog_create", C.c_int, [_H, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_int64)]),
+    ("lsm_homog_stiffness", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    ("lsm_homog_cells", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_homog_apply", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_homog_load", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_homog_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lsm_homog_solve_rhs", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lsm_homog_set_correctors", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_homog_correctors", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_homog_energy_cells", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("lsm_homog_tensor", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("lsm_homog_corrector", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_homog_sensitivity", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    ("lsm_homog_destroy", None, [C.c_void_p]),
     ("lsm_elastic_modes_create", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("lsm_elastic_modes_mass", C.c_int, [C.c_void_p, C.c_void_p]),
     ("lsm_elastic_modes_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),

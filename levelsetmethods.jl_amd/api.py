@@ -3190,6 +3190,204 @@ def elasticity_solve(phi_or_eq, f, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plan
         raise
 
 
+# ----------------------------------------------------------------------------- homogenisation (ϕ as one cell of a periodic material)
+
+class Homogenization:
+    """homogenize's result and its operator, kept on the device (DESIGN.md §7.23).  The torus has m = n − 1 nodes (and cells) per axis;
+    M = N(N+1)/2 unit strains in Voigt order: 2-D (00, 11, 01), 3-D (00, 11, 22, 12, 02, 01), engineering shears.
+    `tensor` ((M, M) numpy, exactly symmetric), `iterations` and `relres` (one entry per corrector), `levels`, `free_dofs`;
+    corrector(k) → N ROCMeshFields (image nodes n − 1 from node 0); correctors() → host (M, N) + m; sensitivity(W) → the ROCMeshField
+    of the integrand of d(W:C^H)/dΩ, a normal speed (coeff.set_values takes it device to device); cells(), apply(x), load(k),
+    energy_cells(p, q), stiffness(level) show the operator; solve(chi0=None, rtol, max_iters) solves again (a warm start);
+    with_correctors(chi) sets the correctors without a solve; close() releases the device memory.  ϕ is read once, at construction:
+    after ϕ has moved, build a new object and pass the old correctors() as chi0."""
+
+    def __init__(self, phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", level=0.0, precond="mg"):
+        what = "homogenize"
+        self._h = None
+        if precond not in _PRECONDS:
+            raise ValueError(f'{what}: precond must be "mg" or "jacobi", not {precond!r}')
+        if plane not in _PLANES:
+            raise ValueError(f'{what}: plane must be "stress" or "strain", not {plane!r}')
+        nu = float(nu)
+        if not (math.isfinite(nu) and -1.0 < nu < 0.5):
+            raise ValueError(f"{what}: nu must be finite with -1 < nu < 0.5")
+        E_host = None if E is None or hasattr(E, "is_cuda") else np.asarray(E, dtype=np.float64)
+        if E is None:
+            if not (_finite_positive(float(E_in)) and _finite_positive(float(E_out))):
+                raise ValueError(f"{what}: E_in and E_out must be finite and positive")
+            if not math.isfinite(float(level)):
+                raise ValueError(f"{what}: level must be finite")
+        elif E_host is not None and not _finite_positive(E_host):
+            raise ValueError(f"{what}: the cell moduli `E` must be finite and positive")
+        phi = phi_or_eq.current_state() if isinstance(phi_or_eq, LevelSetEquation) else phi_or_eq
+        if not isinstance(phi, ROCMeshField):
+            raise TypeError(f"{what} takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
+        if isinstance(phi, ROCNarrowBandMeshField):
+            raise ValueError(f"{what} is not supported on NarrowBandMeshField: the cell problems are solved over the whole box. Use a full MeshField.")
+        if phi.mesh.ndim == 1:
+            raise ValueError(f"{what} of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+        if getattr(phi.backend, "slab", None) is not None:
+            raise ValueError(f"{what} of a slab-decomposed field (a field with a comm) is not supported")
+        n = tuple(int(m) for m in phi.mesh.n)
+        if any(m < 3 for m in n):
+            raise ValueError(f"{what} needs at least 2 cells (3 nodes) in every dimension")
+        N = len(n)
+        self.cells_shape = cells = tuple(m - 1 for m in n)
+        if E_host is not None and E_host.ndim and E_host.shape != cells:
+            raise ValueError(f"{what}: `E` has shape {E_host.shape}, the grid has {cells} cells")
+        b = self.backend = phi.backend
+        self.mesh, self.bcs, self.precond, self.ndim, self.nstrains = phi.mesh, phi.bcs, precond, N, N * (N + 1) // 2
+        E_dev = None if E is None else b.node_array(E if E_host is None else E_host, "E", cells)
+        try:
+            self._h, stats = b.homog_create(None if E is not None else phi.buf, level, E_in, E_out, E_dev, nu, _PLANES[plane], _PRECONDS[precond])
+        except L.LsmError as e:
+            why = {1: "phi must be finite", 2: "the cell moduli must be finite and positive"}.get(getattr(e, "reason", 0))
+            if why is None:
+                raise
+            raise ValueError(f"{what}: {why} ({getattr(e, 'detail', 0)} entries are not)") from None
+        self.levels, self.free_dofs = stats[0], stats[1]
+        self.iterations, self.relres, self._tensor = [0] * self.nstrains, [0.0] * self.nstrains, None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the Homogenization is closed")
+        return self._h
+
+    def _chi_dev(self, chi, what):
+        """(M, N) + m host values (or a device tensor of as many) as one flat float64 device array"""
+        b = self.backend
+        shape = (self.nstrains, self.ndim) + self.cells_shape
+        if b.torch.is_tensor(chi):
+            return b.node_array(chi, what, shape)
+        a = np.asarray(chi, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{what} has shape {a.shape}, expected {shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{what} must be finite")
+        flat = np.concatenate([a[k, i].reshape(-1, order="F") for k in range(shape[0]) for i in range(shape[1])])
+        return b.torch.from_numpy(flat).to(b.device)
+
+    def _unflat(self, t, lead):
+        """a flat device tensor as a host array of shape lead + m"""
+        m = self.cells_shape
+        nn = int(np.prod(m))
+        v = t.cpu().numpy().reshape((-1, nn))
+        return np.stack([r.reshape(m, order="F") for r in v]).reshape(tuple(lead) + m)
+
+    def solve(self, chi0=None, rtol=1e-8, max_iters=500):
+        """all M correctors by PCG from chi0 ((M, N) + m; zero without one).  A failure raises and leaves the stored correctors as they were."""
+        h = self._handle()
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("homogenize: rtol must be positive and finite, max_iters at least 1")
+        guess = None if chi0 is None else self._chi_dev(chi0, "homogenize: chi0")
+        self.iterations, self.relres = self.backend.homog_solve(h, guess, rtol, int(max_iters))
+        self._tensor = None
+        return self
+
+    def solve_rhs(self, f, x0=None, rtol=1e-8, max_iters=500):
+        """the same PCG for a right-hand side of the caller's, A x = f away from the pinned node 0: f and x0 host arrays of shape
+        (N,) + m.  Returns (x, iterations, relres); the correctors are not touched (for diagnostics and tests of the V-cycle)."""
+        b, N = self.backend, self.ndim
+        shape = (N,) + self.cells_shape
+
+        def dev(a, what):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError(f"homogenize: {what} has shape {a.shape}, expected {shape}")
+            return b.torch.from_numpy(np.concatenate([a[i].reshape(-1, order="F") for i in range(N)])).to(b.device)
+        fd = dev(f, "f")
+        xd = dev(np.zeros(shape) if x0 is None else x0, "x0")
+        it, rel = b.homog_solve_rhs(self._handle(), fd, xd, float(rtol), int(max_iters))
+        return self._unflat(xd, (N,)), it, rel
+
+    def with_correctors(self, chi):
+        """take correctors from elsewhere ((M, N) + m), without a solve"""
+        self.backend.homog_set_correctors(self._handle(), self._chi_dev(chi, "with_correctors: chi"))
+        self._tensor = None
+        return self
+
+    @property
+    def tensor(self):
+        if self._tensor is None:
+            self._tensor = self.backend.homog_tensor(self._handle())
+        return self._tensor
+
+    def correctors(self):
+        return self._unflat(self.backend.homog_correctors(self._handle()), (self.nstrains, self.ndim))
+
+    def _strain(self, k, what="the unit strain"):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"homogenize: {what} must be an integer, not {type(k).__name__}")
+        if not 0 <= int(k) < self.nstrains:
+            raise ValueError(f"homogenize: {what} {k} of {self.nstrains}")
+        return int(k)
+
+    def corrector(self, k):
+        h = self._handle()
+        u = [ROCMeshField(self.backend, self.mesh, self.bcs) for _ in range(self.ndim)]
+        self.backend.homog_corrector(h, self._strain(k), [c.buf for c in u])
+        return tuple(u)
+
+    def sensitivity(self, W):
+        W = np.asarray(W, dtype=np.float64)
+        M = self.nstrains
+        if W.shape != (M, M) or not np.all(np.isfinite(W)) or not np.array_equal(W, W.T):
+            raise ValueError(f"homogenize: W must be a finite symmetric {M}×{M} matrix")
+        g = ROCMeshField(self.backend, self.mesh, self.bcs)
+        self.backend.homog_sensitivity(self._handle(), W, g.buf)
+        return g
+
+    def cells(self):
+        return self._unflat(self.backend.homog_cells(self._handle()), ())
+
+    def apply(self, x):
+        """A x on all components, no pin: x a host array of shape (N,) + m; returns one"""
+        b, N = self.backend, self.ndim
+        a = np.asarray(x, dtype=np.float64)
+        if a.shape != (N,) + self.cells_shape:
+            raise ValueError(f"homogenize: x has shape {a.shape}, expected {(N,) + self.cells_shape}")
+        xd = b.torch.from_numpy(np.concatenate([a[i].reshape(-1, order="F") for i in range(N)])).to(b.device)
+        return self._unflat(b.homog_apply(self._handle(), xd), (N,))
+
+    def load(self, k):
+        return self._unflat(self.backend.homog_load(self._handle(), self._strain(k)), (self.ndim,))
+
+    def energy_cells(self, p, q):
+        return self._unflat(self.backend.homog_energy_cells(self._handle(), self._strain(p), self._strain(q)), ())
+
+    def stiffness(self, level=0):
+        return self.backend.homog_stiffness(self._handle(), level)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.homog_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def homogenize(phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", level=0.0, rtol=1e-8, max_iters=500, precond="mg", chi0=None):
+    """The effective elasticity tensor C^H of the periodic material whose cell is the box of ϕ's grid, on the device:
+    elasticity_solve's Q1 discretisation, cell moduli, material and `plane`, on the torus of the grid's n − 1 cells per axis (node n − 1
+    is node 0; ϕ needs no PeriodicBC, only its cells are read).  For each of the M = N(N+1)/2 unit strains a periodic corrector χ^k
+    (zero at node 0) is found by conjugate gradients, from `chi0` ((M, N) + (n − 1); zero without one) until ‖r‖₂ ≤ rtol·‖f^k‖₂,
+    preconditioned by one wrapping multigrid V-cycle (precond="mg") or the diagonal ("jacobi").  Returns a Homogenization: `tensor`,
+    `sensitivity(W)` and the rest.  Raises ValueError / TypeError for what is refused (1-D, a band field, a slab, fewer than 2 cells in
+    a dimension, moduli that are not finite and positive, ν outside (−1, 0.5), an unknown plane, non-finite data) and
+    LsmNotConvergedError when max_iters does not suffice."""
+    hom = Homogenization(phi_or_eq, E_in=E_in, E_out=E_out, E=E, nu=nu, plane=plane, level=level, precond=precond)
+    try:
+        return hom.solve(chi0=chi0, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        hom.close()
+        raise
+
+
 # ----------------------------------------------------------------------------- vibration modes (the eigenfrequency objective of a structural optimisation)
 
 def _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, from_phi):

@@ -556,6 +556,91 @@ class HipBackend:
     def elastic_destroy(self, obj):
         self.lib.lsm_elastic_destroy(obj)
 
+    # ---- homogenisation (lsm_homog_*): vectors are flat float64 device tensors over the torus of n − 1 nodes per axis
+    def _homog_sizes(self):
+        N = self.ndim
+        return N, N * (N + 1) // 2, int(np.prod([m - 1 for m in self.local_shape()]))
+
+    def homog_create(self, phi, level, e_in, e_out, e_cells, nu, plane, precond):
+        """returns (object, (levels, free components, nodes of the torus, 0)); an LsmError raised for the data carries `reason` and `detail`"""
+        if self.slab is not None:
+            raise L.LsmError("homog_create: this backend holds a slab of a decomposed grid; lsm_homog_create works on the whole grid of one device")
+        out, stats = C.c_void_p(), (C.c_int64 * 4)()
+        code = self.lib.lsm_homog_create(self.h, self.ptr(phi), float(level), float(e_in), float(e_out), self.ptr(e_cells), float(nu), int(plane), int(precond),
+                                         C.byref(out), stats)
+        try:
+            L.check(self.h, code, "lsm_homog_create")
+        except L.LsmError as e:
+            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0
+            e.detail = int(stats[1])
+            raise
+        return out, tuple(int(v) for v in stats)
+
+    def homog_stiffness(self, obj, level):
+        R = (1 << self.ndim) * self.ndim
+        out = np.zeros((R, R), dtype=np.float64)
+        L.check(self.h, self.lib.lsm_homog_stiffness(obj, int(level), out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_homog_stiffness")
+        return out
+
+    def homog_cells(self, obj):
+        out = self.torch.empty(self._homog_sizes()[2], dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_homog_cells(obj, self.ptr(out)), "lsm_homog_cells")
+        return out
+
+    def homog_apply(self, obj, x):
+        y = self.torch.empty_like(x)
+        L.check(self.h, self.lib.lsm_homog_apply(obj, self.ptr(x), self.ptr(y)), "lsm_homog_apply")
+        return y
+
+    def homog_load(self, obj, k):
+        N, _, nn = self._homog_sizes()
+        out = self.torch.empty(N * nn, dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_homog_load(obj, int(k), self.ptr(out)), "lsm_homog_load")
+        return out
+
+    def homog_solve(self, obj, guess, rtol, max_iters):
+        """guess: a flat float64 device tensor of M·N·nn values or None; returns (iterations, relres), one entry per corrector"""
+        M = self._homog_sizes()[1]
+        it, rel = (C.c_int * M)(), (C.c_double * M)()
+        L.check(self.h, self.lib.lsm_homog_solve(obj, self.ptr(guess), float(rtol), int(max_iters), it, rel), "lsm_homog_solve")
+        return [int(v) for v in it], [float(v) for v in rel]
+
+    def homog_solve_rhs(self, obj, f, x, rtol, max_iters):
+        """x (in: the guess, out: the solution) and f are flat float64 device tensors of N·nn values; returns (iterations, relres)"""
+        it, rel = C.c_int(0), C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_homog_solve_rhs(obj, self.ptr(f), self.ptr(x), float(rtol), int(max_iters), C.byref(it), C.byref(rel)), "lsm_homog_solve_rhs")
+        return it.value, rel.value
+
+    def homog_set_correctors(self, obj, chi):
+        L.check(self.h, self.lib.lsm_homog_set_correctors(obj, self.ptr(chi)), "lsm_homog_set_correctors")
+
+    def homog_correctors(self, obj):
+        N, M, nn = self._homog_sizes()
+        out = self.torch.empty(M * N * nn, dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_homog_correctors(obj, self.ptr(out)), "lsm_homog_correctors")
+        return out
+
+    def homog_energy_cells(self, obj, p, q):
+        out = self.torch.empty(self._homog_sizes()[2], dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_homog_energy_cells(obj, int(p), int(q), self.ptr(out)), "lsm_homog_energy_cells")
+        return out
+
+    def homog_tensor(self, obj):
+        M = self._homog_sizes()[1]
+        out = np.zeros((M, M), dtype=np.float64)
+        L.check(self.h, self.lib.lsm_homog_tensor(obj, out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_homog_tensor")
+        return out
+
+    def homog_corrector(self, obj, k, u):
+        L.check(self.h, self.lib.lsm_homog_corrector(obj, int(k), *self._u3(u)), "lsm_homog_corrector")
+
+    def homog_sensitivity(self, obj, W, g):
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        L.check(self.h, self.lib.lsm_homog_sensitivity(obj, W.ctypes.data_as(C.POINTER(C.c_double)), self.ptr(g)), "lsm_homog_sensitivity")
+
+    def homog_destroy(self, obj):
+        self.lib.lsm_homog_destroy(obj)
+
     # ---- stress recovery (lsm_elastic_stress_*): `what` is L.STRESS_STRAIN, L.STRESS_STRESS or L.STRESS_VON_MISES
     def elastic_stress_cells(self, obj, u, what):
         """the component-major fp64 cell arrays as one flat device tensor"""

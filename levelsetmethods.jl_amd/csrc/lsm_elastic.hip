@@ -22,6 +22,7 @@
 #include <memory>
 
 #include "el_cell.h"
+#include "el_k0.h"
 #include "mg_pcg.h"
 
 namespace lsm {
@@ -396,7 +397,7 @@ struct ElasticObject : MgSolver<EsLevel> {
 
 // the unit element matrix of a box cell with sides h, scaled by 1/∏h (include/lsm.h states the formula): a product over the axes
 // of the 1-D factors mass h/3 | h/6, stiffness ±1/h, mixed ±½ (the sign of the differentiated corner)
-static void es_k0(int N, const double h[3], double lam, double mu, std::vector<double>& K) {
+void es_k0(int N, const double h[3], double lam, double mu, std::vector<double>& K) {
     const int NC = 1 << N, R = NC * N;
     std::vector<double> G((size_t)NC * NC * N * N);
     auto g_at = [&](int a, int b, int i, int j) -> double& { return G[(((size_t)a * NC + b) * N + i) * N + j]; };
@@ -434,7 +435,7 @@ static void es_k0(int N, const double h[3], double lam, double mu, std::vector<d
 // frequencies θ ∈ {0, π}^N of the N×N symbol D^−½·Â(θ)·D^−½, Â_ij(θ) = Σ_a Σ_b ±K0[(a,i),(b,j)] (minus where a and b differ on an odd
 // number of the axes with θ_d = π), D_i = Σ_a K0[(a,i),(a,i)].  Stretched cells — an axis that stopped coarsening while the others go
 // on — push it past 2/ES_OMEGA, where damped Jacobi amplifies and the V-cycle is no longer positive definite.
-static double es_symbol_lambda(int N, const std::vector<double>& K) {
+double es_symbol_lambda(int N, const std::vector<double>& K) {
     const int NC = 1 << N, R = NC * N;
     double D[3] = {0, 0, 0}, best = 0.0;
     for (int i = 0; i < N; ++i)

@@ -27,6 +27,7 @@
 //   static launch_resid(N, nb, stream, L, r, x, res, st)   launches the level's residual kernel: mg_resid_kernel, or its own
 //   apply<N, MASK>(id, I, x, stride, out)  the comps(N) rows of the eliminated operator at node id from x[j·stride + q].  MASK: x may
 //                                          hold anything on fixed components (they are not read); without it x holds zero there.
+//   optional: static constexpr bool wraps = true, with launch_gather and launch_prolong (see mg_wraps below): a grid that wraps
 #pragma once
 
 #include <algorithm>
@@ -34,6 +35,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lsm_handle.h"
@@ -455,6 +457,14 @@ static int mg_alloc_scalars(LsmHandle* h, MgSolver<Level>& o, int nstat, hipStre
     return LSM_OK;
 }
 
+// A Level whose grid wraps (lsm_homog.hip) declares `static constexpr bool wraps = true` and brings its own transfers,
+//   static launch_gather(N, stream, Lf, Lc, co, res, rc, st),  static launch_prolong(N, stream, Lf, Lc, co, xc, x, st);
+// every other Level takes mg_gather_kernel and mg_prolong_kernel, as before.
+template <class Level, class = void>
+struct mg_wraps : std::false_type {};
+template <class Level>
+struct mg_wraps<Level, std::void_t<decltype(Level::wraps)>> : std::true_type {};
+
 // z = M r0 for M = one V-cycle, into xb[0]; the last kernel leaves ρ and β
 template <class Level>
 static void mg_vcycle(MgSolver<Level>& o, const double* r0, hipStream_t s) {
@@ -468,21 +478,39 @@ static void mg_vcycle(MgSolver<Level>& o, const double* r0, hipStream_t s) {
                      (const MgState*)st);
         MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
         Level::launch_resid(N, nb, s, L, r, o.xb[l], o.xa[l], st);      // xa is free until the post-smoothing
-        MG_LAUNCH2(N, mg_gather_kernel, Level, dim3(mg_blocks(o.lev[l + 1].nn), nc), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2],
-                   (const double*)o.xa[l], o.rhs[l + 1], (const MgState*)st);
+        if constexpr (mg_wraps<Level>::value) Level::launch_gather(N, s, L, o.lev[l + 1], o.co[l], (const double*)o.xa[l], o.rhs[l + 1], (const MgState*)st);
+        else
+            MG_LAUNCH2(N, mg_gather_kernel, Level, dim3(mg_blocks(o.lev[l + 1].nn), nc), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2],
+                       (const double*)o.xa[l], o.rhs[l + 1], (const MgState*)st);
     }
     {
         const int l = nl - 1;
+        const Level& L = o.lev[l];
         const double* r = l == 0 ? r0 : o.rhs[l];
-        if (l == 0) MG_LAUNCH3(N, mg_coarsest_kernel, 1, Level, 1, 128, s, o.lev[l], r, o.xb[l], st);
-        else MG_LAUNCH3(N, mg_coarsest_kernel, 0, Level, 1, 128, s, o.lev[l], r, o.xb[l], st);
+        if (L.nn > 128) {
+            // a coarsest level too large for one workgroup (a wrapping grid with an odd axis; the other Levels refuse it when they
+            // are created): the same MG_NCOARSE sweeps, the same arithmetic, as launches of the smoother; the last one lands in xb
+            static_assert(MG_NCOARSE % 2 == 0, "the sweeps alternate xa, xb and end in xb");
+            const unsigned nb = mg_blocks(L.nn);
+            MG_LAUNCH_AS(N, (mg_smooth0_kernel<Level::comps(2), Level>), (mg_smooth0_kernel<Level::comps(3), Level>), nb, MG_THREADS, s, L, r, o.xa[l],
+                         (const MgState*)st);
+            for (int k = 1; k < MG_NCOARSE; ++k) {
+                const double* from = (k & 1) ? o.xa[l] : o.xb[l];
+                double* to = (k & 1) ? o.xb[l] : o.xa[l];
+                if (l == 0 && k == MG_NCOARSE - 1) MG_LAUNCH3(N, mg_smooth_kernel, 1, Level, nb, MG_THREADS, s, L, r, from, to, o.partial.p, st);
+                else MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, from, to, o.partial.p, st);
+            }
+        } else if (l == 0) MG_LAUNCH3(N, mg_coarsest_kernel, 1, Level, 1, 128, s, L, r, o.xb[l], st);
+        else MG_LAUNCH3(N, mg_coarsest_kernel, 0, Level, 1, 128, s, L, r, o.xb[l], st);
     }
     for (int l = nl - 2; l >= 0; --l) {
         const Level& L = o.lev[l];
         const double* r = l == 0 ? r0 : o.rhs[l];
         const unsigned nb = mg_blocks(L.nn);
-        MG_LAUNCH2(N, mg_prolong_kernel, Level, dim3(nb, nc), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2], (const double*)o.xb[l + 1], o.xb[l],
-                   (const MgState*)st);
+        if constexpr (mg_wraps<Level>::value) Level::launch_prolong(N, s, L, o.lev[l + 1], o.co[l], (const double*)o.xb[l + 1], o.xb[l], (const MgState*)st);
+        else
+            MG_LAUNCH2(N, mg_prolong_kernel, Level, dim3(nb, nc), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2], (const double*)o.xb[l + 1],
+                       o.xb[l], (const MgState*)st);
         MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], o.partial.p, st);
         if (l == 0) MG_LAUNCH3(N, mg_smooth_kernel, 1, Level, nb, MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
         else MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
