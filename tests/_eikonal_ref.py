@@ -2,6 +2,8 @@
 form shifted by the smallest neighbour, the two seedings, and three solvers over the same G and the same strict `G < T` rule —
 Jacobi passes (what the tile kernel runs in LDS), Gauss–Seidel sweeps in all 2^N directions, heap fast marching.  No device.
 Every operation is spelled in the kernel's order (the library is built with -ffp-contract=off: the device rounds as numpy does).
+Further down: the device's tile schedule run one tile after the other, what must hold of any of its fixed points (`unsatisfied`,
+`residual`), and the fixtures the host and the device tests share — spheres, checkerboards, plane fronts, seed fields.
 Arrays are n-shaped, axis 0 fastest in memory (order="F"), as a MeshField's."""
 import heapq
 import itertools
@@ -26,14 +28,12 @@ def tol(n, tmax):
 
 # ---- the update
 
-def G(a, s, h):
-    """G of one node, scalars: a[d] = min of the two neighbours' T along axis d (+inf where none exists or none is finite),
-    s the node's slowness, h the mesh sizes"""
+def _G_and_stage(a, s, h):
     ax = sorted(range(len(a)), key=lambda d: (a[d], d))
     a0 = a[ax[0]]
     if a0 == INF:
-        return INF
-    tau = s * h[ax[0]]
+        return INF, 0
+    tau, stage = s * h[ax[0]], 1
     for k in range(2, len(a) + 1):
         if not a0 + tau > a[ax[k - 1]]:
             break
@@ -48,8 +48,23 @@ def G(a, s, h):
         disc = B * B - A * C
         if disc < 0.0:
             break
-        tau = (B + math.sqrt(disc)) / A
-    return a0 + tau
+        tau, stage = (B + math.sqrt(disc)) / A, k
+    return a0 + tau, stage
+
+
+def G(a, s, h):
+    """G of one node, scalars: a[d] = min of the two neighbours' T along axis d (+inf where none exists or none is finite),
+    s the node's slowness, h the mesh sizes"""
+    return _G_and_stage(a, s, h)[0]
+
+
+def G_stage(a, s, h):
+    """which stage of G produced τ: 1 (τ = s·h of the smallest axis: a0 + τ <= a1, or there is no second axis), 2 (the quadratic
+    over the two smallest axes) or 3 (over all three); 0 where every a_d is +inf.  The two `disc < 0` guards are not counted as
+    a stage of their own because exact arithmetic cannot reach them: stage k is entered only when a0 + τ > a_k with τ the
+    solution over the first k − 1 axes, and then the quadratic over k axes has a root >= a_k − a0 (for k = 2: δ1 = a1 − a0 < s·h0
+    gives disc = w1·(s² − w0·δ1²) + w0·s² > w0·s² > 0).  No fixture tries to reach them."""
+    return _G_and_stage(a, s, h)[1]
 
 
 def G_vec(a, s, h):
@@ -316,6 +331,18 @@ def residual(T, frozen, h, slowness=None):
     return float(np.abs(g[free] - T[free]).max()) if free.any() else 0.0
 
 
+def unsatisfied(T, frozen, h, slowness=None, where=None):
+    """the number of free nodes (of `where`, if given) with G(T's neighbours) < T: 0 at any fixed point of the strict `G < T`
+    rule, whatever the visiting order, because the comparison is the solver's own and G here is the solver's G bit for bit.
+    Rounding cannot leave such a node; a tile that was not woken after its neighbour's layer fell does."""
+    s = np.broadcast_to(np.asarray(1.0 if slowness is None else slowness, dtype=np.float64), T.shape)
+    g = G_vec(_neighbour_min(T).reshape(T.ndim, -1), s.reshape(-1), h).reshape(T.shape)
+    bad = ~frozen & (g < T)
+    if where is not None:
+        bad &= where
+    return int(bad.sum())
+
+
 def eikonal(phi, h, speed=None, width=None, cutoff=None, T=None):
     """what eikonal_ writes: copysign(min(T, cutoff), ϕ), T the Jacobi fixed point (or the one given)"""
     phi = np.asarray(phi, dtype=np.float64)
@@ -364,9 +391,158 @@ FIXTURES = {
 }
 
 
+# the sizes at which the tile schedule shows: 8·7·6 = 336 tiles of 8×8×8 (the last ones 1, 2 and 3 nodes thick), 10·30 = 300 of
+# 32×8; two compaction workgroups.  Kept out of FIXTURES: the host parametrisations over those run pure-Python sweeps and a heap.
+LARGE = {
+    "many_tiles_3d": ((57, 50, 43), (-1.0, -1.1, -0.9), (1.0, 1.2, 1.1), [((-0.4, -0.4, -0.3), 0.4), ((0.5, 0.5, 0.4), 0.3)], None),
+    "many_tiles_3d_speed": ((57, 50, 43), (-1.0, -1.1, -0.9), (1.0, 1.2, 1.1), [((-0.4, -0.4, -0.3), 0.4), ((0.5, 0.5, 0.4), 0.3)], "random"),
+    "many_tiles_2d": ((290, 235), (-1.0, -1.0), (1.1, 1.0), [((-0.45, -0.3), 0.3), ((0.5, 0.35), 0.22)], None),
+}
+
+
 def fixture(name):
     """(phi, n, lc, hc, h, speed)"""
-    n, lc, hc, balls, sp = FIXTURES[name]
+    n, lc, hc, balls, sp = FIXTURES[name] if name in FIXTURES else LARGE[name]
     phi = spheres(n, lc, hc, balls)
     speed = random_speed(n) if sp == "random" else None
     return phi, n, lc, hc, meshsize(n, lc, hc), speed
+
+
+def ntiles(n):
+    return int(np.prod([-(-int(k) // e) for k, e in zip(n, TILES[len(n)])]))
+
+
+# ---- checkerboards: every free node's neighbours are frozen, so its result is G of chosen inputs after one pass, whatever the
+# schedule — the update and the launch bookkeeping bit for bit at any number of tiles
+
+# name: (n, nominal h).  The 2-node grids are the smallest lsm_eikonal takes, the 4-node ones the smallest a device handle has
+CHECKERBOARDS = {
+    "cb_336_tiles": ((57, 50, 43), (0.3, 0.02, 0.11)),
+    "cb_300_tiles": ((290, 235), (0.3, 0.02)),
+    "cb_one_tile": ((7, 6, 5), (0.3, 0.02, 0.11)),
+    "cb_4x4x4": ((4, 4, 4), (0.3, 0.02, 0.11)),
+    "cb_4x4": ((4, 4), (0.3, 0.02)),
+    "cb_2x2x2": ((2, 2, 2), (0.3, 0.02, 0.11)),
+    "cb_2x2": ((2, 2), (0.3, 0.02)),
+}
+CB_FREE = 1000.0        # |ϕ| of the free nodes: beyond any width
+_CB_KINDS = {3: ("tie_small", "tie_large") * 3 + ("dominated",) * 2 + ("close",) * 2, 2: ("tie",) * 6 + ("dominated",) * 2 + ("close",) * 2}
+
+
+def checkerboard(name, sign=1.0, f32=False):
+    """(phi, n, lc, hc, h, speed, w) with one sign of ϕ over the grid, for the width seeding with w = 3·h_max: node I is free iff
+    Σ I_d is odd and holds |ϕ| = CB_FREE; every other node holds a value in (0, 0.99·w] and is frozen at it.  The values are
+    uniform, except around the free nodes of the lattice 3·J + 1 (no two of them share a neighbour), whose neighbour minima a_d
+    are planted in turn: the two smallest equal (`tie_small`), the two largest equal with a0 up to 2·s·h below them
+    (`tie_large`: stage 1 or stage 3), the smallest so far below the rest that a0 + s·h <= a1 (`dominated`), all within
+    0.2·s·h_min (`close`: stage 3); the minimum sits at the lower or the upper neighbour at random, the other one is equal to
+    it one time in four.  f32: the values rounded to float32 (ties stay ties).  The speed is random_speed's."""
+    n, hn = CHECKERBOARDS[name]
+    N = len(n)
+    lc, hc = (0.0,) * N, tuple(hn[d] * (n[d] - 1) for d in range(N))
+    h = meshsize(n, lc, hc)
+    w = 3.0 * float(h.max())
+    rng = np.random.default_rng(11)
+    speed = random_speed(n)
+    idx = np.indices(n)
+    free = idx.sum(axis=0) % 2 == 1
+    vals = 0.99 * w * (1.0 - rng.random(n))
+    sites = [I for I in itertools.product(*[range(1, n[d] - 1, 3) for d in range(N)]) if sum(I) % 2 == 1]
+    kinds = _CB_KINDS[N]
+    top = 0.99 * w
+    for k, at in enumerate(rng.permutation(len(sites))):
+        I = sites[at]
+        s = 1.0 / float(speed[I])
+        p = [int(x) for x in rng.permutation(N)]
+        u = rng.random(4)
+        a = [0.0] * N
+        kind = kinds[k % len(kinds)]
+        if kind in ("tie_small", "tie"):
+            v = w * (0.01 + 0.89 * u[0])
+            a[p[0]] = a[p[1]] = v
+            if N > 2:
+                a[p[2]] = v + (top - v) * u[1]
+        elif kind == "tie_large":
+            v = w * (0.3 + 0.69 * u[0])
+            a[p[1]] = a[p[2]] = v
+            a[p[0]] = v - u[1] * min(2.0 * s * float(h[p[0]]), 0.9 * v)
+        elif kind == "dominated":
+            if 1.01 * s * float(h[p[0]]) + 0.01 * w >= 0.98 * w:
+                p.remove(int(np.argmin(h)))
+                p.insert(0, int(np.argmin(h)))
+            a[p[0]] = 0.01 * w * (1.0 - u[0])
+            lo = a[p[0]] + 1.01 * s * float(h[p[0]])
+            for j in range(1, N):
+                a[p[j]] = lo + (top - lo) * u[j]
+        else:
+            a[p[0]] = w * (0.01 + 0.7 * u[0])
+            for j in range(1, N):
+                a[p[j]] = a[p[0]] + 0.2 * u[j] * s * float(h.min())
+        for d in range(N):
+            side = 1 if rng.random() < 0.5 else -1
+            other = a[d] if rng.random() < 0.25 else a[d] + (top - a[d]) * rng.random()
+            vals[I[:d] + (I[d] + side,) + I[d + 1:]] = a[d]
+            vals[I[:d] + (I[d] - side,) + I[d + 1:]] = other
+    if f32:
+        vals = vals.astype(np.float32).astype(np.float64)
+    phi = np.asfortranarray(float(sign) * np.where(free, CB_FREE, vals))
+    return phi, n, lc, hc, h, speed, w
+
+
+def checkerboard_census(phi, h, speed, w):
+    """(free, g, stage, ties of the two smallest a_d, ties of the two largest): at every free node of a checkerboard the scalar
+    G and G_stage of its neighbour minima (g and stage are n-shaped, 0 at the frozen nodes), and the numbers of free nodes
+    whose two smallest, and whose two largest, a_d are exactly equal"""
+    T0, frozen = seed(phi, h, 1.0 / speed, w)
+    a = _neighbour_min(T0)
+    hh = [float(x) for x in h]
+    g = np.zeros(phi.shape, order="F")
+    stage = np.zeros(phi.shape, dtype=np.int64, order="F")
+    for I in zip(*np.nonzero(~frozen)):
+        g[I], stage[I] = _G_and_stage([float(x) for x in a[(slice(None),) + I]], 1.0 / float(speed[I]), hh)
+    srt = np.sort(a[:, ~frozen], axis=0)
+    return ~frozen, g, stage, int((srt[0] == srt[1]).sum()), int((srt[-1] == srt[-2]).sum())
+
+
+# ---- plane fronts: with s ≡ 1 a front that leaves a face of zeros moves along one axis only.  A node's lateral neighbours hold
+# either +inf or exactly fl(a0 + h_d), its own stage-1 value, so stage 2 is never entered and every node is a0 + h_d whatever a
+# tile read of its neighbours' layers: values, launches and visits do not depend on the schedule, and the tiles of layer b + 1
+# along the axis are reached through the face flag of layer b alone (a lateral wake-up comes one launch later and shows in both
+# counts).
+
+def plane(name, axis, end):
+    """(phi, n, lc, hc, h) on the grid of LARGE[name]: ϕ = x_axis − its value at the first (end 0: ϕ >= 0) or the last node
+    (end 1: ϕ <= 0, the zeros −0.0) of the axis; the crossing seed freezes the face of zeros and the layer next to it"""
+    n, lc, hc = LARGE[name][:3]
+    h = meshsize(n, lc, hc)
+    k = np.indices(n)[axis].astype(np.float64)
+    phi = h[axis] * (k - (0 if end == 0 else n[axis] - 1))
+    return np.asfortranarray(np.where(phi == 0, -0.0, phi) if end else phi), n, lc, hc, h
+
+
+# ---- the seeding's edge cases as fields (test_eikonal_host.test_seeding_edge_cases states the rules on the same 2-D ones)
+
+def seed_fields():
+    """name → (phi, lc, hc, is a distance): 2-D fields on (5, 4) with h = (0.5, 0.25), 3-D ones on (5, 4, 6) with
+    h = (0.5, 0.25, 0.125), and the smallest grids of a device handle with one node of the other sign"""
+    lc2, hc2 = (0.0, 0.0), (2.0, 0.75)
+    lc3, hc3 = (0.0, 0.0, 0.0), (2.0, 0.75, 0.625)
+    line = np.array([[-1.0, -0.5, 0.0, 0.5, 1.0]] * 4).T
+    i2, j2 = np.indices((5, 4)).astype(np.float64)
+    i3, j3, k3 = np.indices((5, 4, 6)).astype(np.float64)
+    out = {
+        "zero_line": (line, lc2, hc2, True),                                              # ϕ = 0 on a node, zero neighbours beside it
+        "negative_zero_line": (np.where(line == 0, -0.0, line), lc2, hc2, True),          # the sign bit comes back
+        "one_zero_node": ((i2 - 2.0) * 0.5 + (j2 - 1.0) * 0.125, lc2, hc2, False),        # ϕ_J = 0 next to ϕ_I != 0, along both axes
+        "sliver": (np.array([[1.0, 0.75, -0.05, 0.2, 1.0]] * 4).T, lc2, hc2, False),      # one node thick: crossings on both sides
+        "leaves_through_a_face": (i2 * 0.5 - 1.6 + 0.0 * j2, lc2, hc2, True),             # seeded from the neighbours that exist
+        "zero_plane": ((i3 - 2.0) * 0.5 + 0.0 * j3, lc3, hc3, True),
+        "face_node_one_axis": (k3 * 0.125 - 0.55 + 0.0 * i3, lc3, hc3, True),             # the face k = 5 crosses along axis 2 only
+        "corner_4x4": (np.where(i2[:4] + j2[:4] == 0, -0.3, 0.2 + 0.01 * i2[:4] + 0.03 * j2[:4]), lc2, (1.5, 0.75), False),
+        "corner_4x4x4": (np.where(i3[:4, :, :4] + j3[:4, :, :4] + k3[:4, :, :4] == 0, -0.3, 0.2 + 0.01 * i3[:4, :, :4] + 0.03 * j3[:4, :, :4] + 0.02 * k3[:4, :, :4]),
+                         lc3, (1.5, 0.75, 0.375), False),
+        "corner_2x2": (np.array([[-0.3, 0.2], [0.25, 0.4]]), lc2, (0.5, 0.25), False),
+        "corner_2x2x2": (np.where(i3[:2, :2, :2] + j3[:2, :2, :2] + k3[:2, :2, :2] == 0, -0.3, 0.2 + 0.05 * i3[:2, :2, :2] + 0.03 * j3[:2, :2, :2] + 0.02 * k3[:2, :2, :2]),
+                         lc3, (0.5, 0.25, 0.125), False),
+    }
+    return {k: (np.asfortranarray(v[0]), v[1], v[2], v[3]) for k, v in out.items()}
