@@ -718,6 +718,67 @@ int lsm_homog_corrector(LsmHomog* s, int k, void* u0, void* u1, void* u2);
 int lsm_homog_sensitivity(LsmHomog* s, const double* W, void* g_out);
 void lsm_homog_destroy(LsmHomog* s);
 
+/* ---- homogenize_conductivity: the effective conductivity tensor K^H of −div(a grad u) for the periodic material whose cell is the
+ *      box of a dense 2-D or 3-D grid, and its sensitivity (csrc/lsm_hcond.hip; tests/_hcond_ref.py restates every
+ *      operation).  Shapes, ownership, streams and failures are lsm_homog_*'s unless stated; every sum below starts from +0.
+ *      The torus: lsm_homog's.  m_d = n_d − 1 nodes and cells per axis, node n_d − 1 is node 0, id = I0 + m0·(I1 + m1·I2) for node I
+ *      and for cell I (lowest corner I); cell index I_d − 1 wraps to m_d − 1, node I_d + 1 wraps to 0.  The handle's boundary
+ *      conditions are not read: only phi's cells are.  Cell coefficients: lsm_elliptic's formula, code and bits (a_cells != NULL:
+ *      the caller's n − 1-shaped device array, phi may be NULL).
+ *      Operator: lsm_elliptic's edge form with wrapping neighbours and c = 0.  The 2^N cells around node I are numbered m = 0 …
+ *      2^N − 1, bit d of m set: cell I_d along d, clear: cell I_d − 1.  The edge from I towards I ± e_d has kbar = (sum of the
+ *      2^(N−1) cells whose bit d is 1 (plus) or 0 (minus), m ascending)·(1/2 in 2-D, 1/4 in 3-D), and w = kbar·ih2_d, ih2_d =
+ *      1/(h_d·h_d).  (A x)_I = sum over d ascending, the minus side before the plus side, of w·(x_I − x_J).  There is no node mass,
+ *      no missing cell and no face.  The diagonal D_I: the sum of the w in the same order.
+ *      Cell problems, p = 0 … N−1 (the unit gradient e_p): the load f^p_I = kbar(I → I + e_p)/h_p − kbar(I − e_p → I)/h_p;
+ *      chi^p is periodic, zero at node 0 (the pin), and solves A chi^p = f^p on the other nodes by lsm_elliptic's PCG (b = f^p).
+ *      lsm_hcond_load writes all nn entries, node 0's included.
+ *      Cell integrand, for cell C with corners a = 0 … 2^N − 1 (corner a at C + bits(a), wrapped): on the edge along d that starts
+ *      at a corner a whose bit d is clear, g^p_{d,a} = delta_dp + (chi^p[a + e_d] − chi^p[a])/h_d (delta is 1.0 or 0.0, added
+ *      first).  t^{pq}_C = (a_C·2^−(N−1))·(sum over d ascending, within it a ascending, of g^p_{d,a}·g^q_{d,a}).
+ *      K^H_pq = (sum_C t^{pq}_C)/ncells.  lsm_hcond_tensor forms the N(N+1)/2 sums for p ≤ q in one pass over the cells, reduced in
+ *      workgroup order, and mirrors them: K is N·N doubles on the host, exactly symmetric, and two calls give the same bits.
+ *      Hierarchy and transfers: lsm_homog's (axis d coarsens while m_d is even and m_d > 4; a coarse cell is the mean of cells 2J
+ *      and 2J+1 per coarsened axis; the wrapping restriction and prolongation; node 0 pinned on every level), with ih2 from the
+ *      level's own h.  omega = 0.8, lsm_elliptic's.  Smoother 2 + 2 sweeps; the coarsest level runs 16 sweeps from zero: in one
+ *      workgroup with at most 128 nodes, else as 16 launches of the smoother, the same arithmetic.  No shape is refused but an axis
+ *      with m_d < 2.
+ *      stats[4] (may be NULL) := {levels, free nodes (nn − 1), nodes of the torus, 0}; after the setup kernel refused the data
+ *      {−reason, offending entries, 0, 0}: a non-finite phi (1, counted over all n nodes), a cell coefficient not finite and
+ *      positive (2).  LSM_ERR_INVALID without running anything: a 1-D grid, a slab handle or one with a communicator, fewer than 3
+ *      nodes in a dimension, bad a_in / a_out / level / precond.
+ *      lsm_hcond_apply: y = A x over nn device doubles, no pin.  lsm_hcond_cells: the cell coefficients, device.
+ *      lsm_hcond_solve: all N correctors from chi_guess (N·nn fp64, host or device; node 0's entries are taken as zero; NULL: from
+ *      zero); iters[N] and relres[N] (may be NULL) per corrector.  The correctors are fp64 on the device on a float32 handle too,
+ *      and change only when all N solves have converged: LSM_ERR_NOT_CONVERGED or a non-finite guess (LSM_ERR_INVALID) leaves them
+ *      untouched, with iters and relres set up to the solve that failed.  A new object holds zero correctors.
+ *      lsm_hcond_set_correctors / lsm_hcond_correctors copy all of them from / to fp64 memory of the caller (host or device),
+ *      shape (N,) + m.
+ *      lsm_hcond_solve_rhs: the same PCG for a caller's right-hand side, A x = f away from the pin (f, x: nn device doubles; x in:
+ *      the guess, node 0's entry taken as zero; out: the solution); the stored correctors are not touched, and a failure leaves x
+ *      untouched.  For diagnostics and tests of the V-cycle.
+ *      lsm_hcond_energy_cells: t^{pq}_C of every cell into ncells device doubles, from the stored correctors.
+ *      lsm_hcond_corrector: chi^k into a dense field of the handle, image nodes n − 1 from node 0, rounded once.
+ *      lsm_hcond_sensitivity: W is N·N host doubles, finite and symmetric.  cell_C = sum_q sum_{p ≤ q} (c·W[p·N + q])·t^{pq}_C,
+ *      c = 2 for p < q and 1 for p = q, q ascending and within it p ascending; g_I = (sum over the 2^N cells around I, m
+ *      ascending, of cell_C)·2^−N at every node of the handle's grid (node n − 1 is node 0), rounded once into a dense field: the
+ *      integrand of d(W:K^H)/dOmega in lsm_homog_sensitivity's node-mean convention. */
+typedef struct LsmHcond LsmHcond;
+int lsm_hcond_create(LsmHandle* h, const void* phi, double level, double a_in, double a_out, const double* a_cells, int precond, LsmHcond** out,
+                     int64_t stats[4]);
+int lsm_hcond_cells(LsmHcond* s, double* a_out_cells);
+int lsm_hcond_apply(LsmHcond* s, const double* x, double* y);
+int lsm_hcond_load(LsmHcond* s, int k, double* f_out);
+int lsm_hcond_solve(LsmHcond* s, const double* chi_guess, double rtol, int max_iters, int* iters, double* relres);
+int lsm_hcond_solve_rhs(LsmHcond* s, const double* f, double* x, double rtol, int max_iters, int* iters, double* relres);
+int lsm_hcond_set_correctors(LsmHcond* s, const double* chi);
+int lsm_hcond_correctors(LsmHcond* s, double* chi_out);
+int lsm_hcond_energy_cells(LsmHcond* s, int p, int q, double* out);
+int lsm_hcond_tensor(LsmHcond* s, double* K);
+int lsm_hcond_corrector(LsmHcond* s, int k, void* u);
+int lsm_hcond_sensitivity(LsmHcond* s, const double* W, void* g_out);
+void lsm_hcond_destroy(LsmHcond* s);
+
 /* ---- elasticity_modes: the m smallest eigenpairs of A x = lambda·M x for the ersatz-material structure of an LsmElastic — its
  *      vibration modes, lambda = omega² — by a locally optimal block preconditioned CG (LOBPCG) whose preconditioner T is the
  *      object's V-cycle, or 1/D for LSM_PRECOND_JACOBI (csrc/lsm_elastic.hip; tests/_modes_ref.py restates it).

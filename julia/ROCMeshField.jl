@@ -728,6 +728,54 @@ homogenization_sensitivity!(g::ROCMeshField, H, W::Matrix{Float64}) = _check(H.h
 
 destroy_homogenization(H) = ccall((:lsm_homog_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), H.op)
 
+# homogenize_conductivity: the effective conductivity tensor of −∇·(a∇u) for the periodic material whose cell is the box of ϕ (include/lsm.h,
+# lsm_hcond_*).  The torus has m = n .- 1 nodes per axis; N unit gradients.  Release the object with destroy_conductivity_homogenization.
+function conductivity_homogenization(ϕ::ROCMeshField; level = 0.0, a_in = 1.0, a_out = 1e-3, a = nothing, precond = :mg)
+    out, stats = Ref{Ptr{Cvoid}}(), zeros(Int64, 4)
+    _check(ϕ.h.ptr, ccall((:lsm_hcond_create, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+        ϕ.h.ptr, pointer(ϕ.buf), level, a_in, a_out, a === nothing ? C_NULL : pointer(a), precond === :jacobi ? 1 : 0, out, stats), "lsm_hcond_create")
+    return (; op = out[], h = ϕ.h, levels = stats[1], free = stats[2], nodes = stats[3])
+end
+
+# the cell coefficients into a ROCArray{Float64} of size n .- 1; y = A x and the load of unit gradient k (0-based) over ROCArray{Float64}s of nn values
+conductivity_homogenization_cells!(a, H) = _check(H.h.ptr, ccall((:lsm_hcond_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, pointer(a)), "lsm_hcond_cells")
+conductivity_homogenization_apply!(y, H, x) = _check(H.h.ptr, ccall((:lsm_hcond_apply, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), H.op, pointer(x), pointer(y)), "lsm_hcond_apply")
+conductivity_homogenization_load!(f, H, k) = _check(H.h.ptr, ccall((:lsm_hcond_load, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), H.op, k, pointer(f)), "lsm_hcond_load")
+
+# all N correctors, from `guess` (a Float64 array of N·nn values, host or device) or from zero; a failure leaves the stored ones untouched
+function conductivity_homogenization_solve!(H, N; guess = nothing, rtol = 1e-8, max_iters = 500)
+    iters, relres = zeros(Cint, N), zeros(Float64, N)
+    _check(H.h.ptr, ccall((:lsm_hcond_solve, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64, Cint, Ptr{Cint}, Ptr{Float64}),
+        H.op, guess === nothing ? C_NULL : pointer(guess), rtol, max_iters, iters, relres), "lsm_hcond_solve")
+    return (; iterations = iters, relres = relres)
+end
+
+# A x = f away from the pinned node for a right-hand side of the caller's (x, f: ROCArray{Float64} of nn values; x holds the guess, then the solution)
+function conductivity_homogenization_solve_rhs!(x, H, f; rtol = 1e-8, max_iters = 500)
+    iters, relres = Ref{Cint}(0), Ref{Float64}(0.0)
+    _check(H.h.ptr, ccall((:lsm_hcond_solve_rhs, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Cint, Ref{Cint}, Ref{Float64}),
+        H.op, pointer(f), pointer(x), rtol, max_iters, iters, relres), "lsm_hcond_solve_rhs")
+    return (; iterations = iters[], relres = relres[])
+end
+
+conductivity_homogenization_set_correctors!(H, chi) = _check(H.h.ptr, ccall((:lsm_hcond_set_correctors, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, pointer(chi)), "lsm_hcond_set_correctors")
+conductivity_homogenization_correctors!(chi, H) = _check(H.h.ptr, ccall((:lsm_hcond_correctors, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, pointer(chi)), "lsm_hcond_correctors")
+conductivity_homogenization_energy_cells!(t, H, p, q) = _check(H.h.ptr, ccall((:lsm_hcond_energy_cells, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}), H.op, p, q, pointer(t)), "lsm_hcond_energy_cells")
+
+# K^H, an N×N host matrix (symmetric)
+function conductivity_homogenization_tensor(H, N)
+    K = zeros(Float64, N, N)
+    _check(H.h.ptr, ccall((:lsm_hcond_tensor, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), H.op, K), "lsm_hcond_tensor")
+    return K
+end
+
+# corrector k (0-based) into the field u; the integrand of d(W:K^H)/dΩ into the field g: the normal speed of a descent on W:K^H
+conductivity_homogenization_corrector!(u::ROCMeshField, H, k) = _check(H.h.ptr, ccall((:lsm_hcond_corrector, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), H.op, k, pointer(u.buf)), "lsm_hcond_corrector")
+conductivity_homogenization_sensitivity!(g::ROCMeshField, H, W::Matrix{Float64}) = _check(H.h.ptr, ccall((:lsm_hcond_sensitivity, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), H.op, W, pointer(g.buf)), "lsm_hcond_sensitivity")
+
+destroy_conductivity_homogenization(H) = ccall((:lsm_hcond_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), H.op)
+
 # elasticity_modes: the m ≤ 8 lowest vibration modes K u = λ M u of an elasticity_operator K (include/lsm.h, lsm_elastic_modes_*).  The
 # density of a cell is rho_out + (rho_in − rho_out)·θ(ϕ), or `rho` (a ROCArray{Float64} of size n .- 1, required when K was built from
 # `E`).  The object borrows K, which must outlive it; release it with destroy_modes.

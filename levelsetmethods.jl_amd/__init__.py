@@ -19,7 +19,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   components, remove_components_, prune_, Components, nucleate_, find_nucleation_sites, Nucleation,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
                   elasticity_solve, ElasticityOperator, ElasticitySolution, elasticity_modes, ElasticityModes, StressSensitivity,
-                  homogenize, Homogenization)
+                  homogenize, Homogenization, homogenize_conductivity, ConductivityHomogenization)
 
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
@@ -35,5 +35,5 @@ __all__ = [
     "components", "remove_components_", "prune_", "Components", "nucleate_", "find_nucleation_sites", "Nucleation",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
     "elasticity_solve", "ElasticityOperator", "ElasticitySolution", "elasticity_modes", "ElasticityModes", "StressSensitivity",
-    "homogenize", "Homogenization",
+    "homogenize", "Homogenization", "homogenize_conductivity", "ConductivityHomogenization",
 ]

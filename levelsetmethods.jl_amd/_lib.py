@@ -186,6 +186,19 @@ _SIGS = [
     ("lsm_homog_corrector", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_homog_sensitivity", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     ("lsm_homog_destroy", None, [C.c_void_p]),
+    ("lsm_hcond_create", C.c_int, [_H, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    ("lsm_hcond_cells", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_hcond_apply", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_hcond_load", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_hcond_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lsm_hcond_solve_rhs", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lsm_hcond_set_correctors", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_hcond_correctors", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_hcond_energy_cells", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("lsm_hcond_tensor", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("lsm_hcond_corrector", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_hcond_sensitivity", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    ("lsm_hcond_destroy", None, [C.c_void_p]),
     ("lsm_elastic_modes_create", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("lsm_elastic_modes_mass", C.c_int, [C.c_void_p, C.c_void_p]),
     ("lsm_elastic_modes_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),

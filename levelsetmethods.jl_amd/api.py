@@ -3388,6 +3388,179 @@ def homogenize(phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress
         raise
 
 
+class ConductivityHomogenization:
+    """homogenize_conductivity's result and its operator, kept on the device.  The torus has m = n − 1 nodes (and
+    cells) per axis; there are N unit gradients e_0 … e_{N−1}.  `tensor` ((N, N) numpy, exactly symmetric), `iterations` and `relres`
+    (one entry per corrector), `levels`, `free_dofs`, `cells_shape`; corrector(k) → a ROCMeshField (image nodes n − 1 from node 0);
+    correctors() → host (N,) + m; sensitivity(W) → the ROCMeshField of the integrand of d(W:K^H)/dΩ, a normal speed (coeff.set_values
+    takes it device to device); cells(), apply(x), load(k), energy_cells(p, q) show the operator; solve(chi0=None, rtol, max_iters)
+    solves again (a warm start); solve_rhs(f, x0) runs the same PCG on a right-hand side of the caller's; with_correctors(chi) sets
+    the correctors without a solve; close() releases the device memory.  ϕ is read once, at construction: after ϕ has moved, build
+    a new object and pass the old correctors() as chi0."""
+
+    def __init__(self, phi_or_eq, *, a_in=1.0, a_out=1e-3, a=None, level=0.0, precond="mg"):
+        what = "homogenize_conductivity"
+        self._h = None
+        if precond not in _PRECONDS:
+            raise ValueError(f'{what}: precond must be "mg" or "jacobi", not {precond!r}')
+        a_host = None if a is None or hasattr(a, "is_cuda") else np.asarray(a, dtype=np.float64)
+        if a is None:
+            if not (_finite_positive(float(a_in)) and _finite_positive(float(a_out))):
+                raise ValueError(f"{what}: a_in and a_out must be finite and positive")
+            if not math.isfinite(float(level)):
+                raise ValueError(f"{what}: level must be finite")
+        elif a_host is not None and not _finite_positive(a_host):
+            raise ValueError(f"{what}: the cell coefficients `a` must be finite and positive")
+        phi = phi_or_eq.current_state() if isinstance(phi_or_eq, LevelSetEquation) else phi_or_eq
+        if not isinstance(phi, ROCMeshField):
+            raise TypeError(f"{what} takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
+        if isinstance(phi, ROCNarrowBandMeshField):
+            raise ValueError(f"{what} is not supported on NarrowBandMeshField: the cell problems are solved over the whole box. Use a full MeshField.")
+        if phi.mesh.ndim == 1:
+            raise ValueError(f"{what} of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+        if getattr(phi.backend, "slab", None) is not None:
+            raise ValueError(f"{what} of a slab-decomposed field (a field with a comm) is not supported")
+        n = tuple(int(m) for m in phi.mesh.n)
+        if any(m < 3 for m in n):
+            raise ValueError(f"{what} needs at least 2 cells (3 nodes) in every dimension")
+        self.cells_shape = cells = tuple(m - 1 for m in n)
+        if a_host is not None and a_host.ndim and a_host.shape != cells:
+            raise ValueError(f"{what}: `a` has shape {a_host.shape}, the grid has {cells} cells")
+        b = self.backend = phi.backend
+        self.mesh, self.bcs, self.precond, self.ndim = phi.mesh, phi.bcs, precond, len(n)
+        a_dev = None if a is None else b.node_array(a if a_host is None else a_host, "a", cells)
+        try:
+            self._h, stats = b.hcond_create(None if a is not None else phi.buf, level, a_in, a_out, a_dev, _PRECONDS[precond])
+        except L.LsmError as e:
+            why = {1: "phi must be finite", 2: "the cell coefficients must be finite and positive"}.get(getattr(e, "reason", 0))
+            if why is None:
+                raise
+            raise ValueError(f"{what}: {why} ({getattr(e, 'detail', 0)} entries are not)") from None
+        self.levels, self.free_dofs = stats[0], stats[1]
+        self.iterations, self.relres, self._tensor = [0] * self.ndim, [0.0] * self.ndim, None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the ConductivityHomogenization is closed")
+        return self._h
+
+    def _dev(self, v, lead, what):
+        """lead + m host values (or a device tensor of as many) as one flat float64 device array"""
+        b = self.backend
+        shape = tuple(lead) + self.cells_shape
+        if b.torch.is_tensor(v):
+            return b.node_array(v, what, shape)
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{what} has shape {a.shape}, expected {shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{what} must be finite")
+        flat = np.concatenate([r.reshape(-1, order="F") for r in a.reshape((-1,) + self.cells_shape)])
+        return b.torch.from_numpy(flat).to(b.device)
+
+    def _unflat(self, t, lead):
+        """a flat device tensor as a host array of shape lead + m"""
+        m = self.cells_shape
+        v = t.cpu().numpy().reshape((-1, int(np.prod(m))))
+        return np.stack([r.reshape(m, order="F") for r in v]).reshape(tuple(lead) + m)
+
+    def solve(self, chi0=None, rtol=1e-8, max_iters=500):
+        """all N correctors by PCG from chi0 ((N,) + m; zero without one).  A failure raises and leaves the stored correctors as they were."""
+        h = self._handle()
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("homogenize_conductivity: rtol must be positive and finite, max_iters at least 1")
+        guess = None if chi0 is None else self._dev(chi0, (self.ndim,), "homogenize_conductivity: chi0")
+        self.iterations, self.relres = self.backend.hcond_solve(h, guess, rtol, int(max_iters))
+        self._tensor = None
+        return self
+
+    def solve_rhs(self, f, x0=None, rtol=1e-8, max_iters=500):
+        """the same PCG for a right-hand side of the caller's, A x = f away from the pinned node 0: f and x0 host arrays of shape m.
+        Returns (x, iterations, relres); the correctors are not touched (for diagnostics and tests of the V-cycle)."""
+        fd = self._dev(f, (), "homogenize_conductivity: f")
+        xd = self._dev(np.zeros(self.cells_shape) if x0 is None else x0, (), "homogenize_conductivity: x0")
+        it, rel = self.backend.hcond_solve_rhs(self._handle(), fd, xd, float(rtol), int(max_iters))
+        return self._unflat(xd, ()), it, rel
+
+    def with_correctors(self, chi):
+        """take correctors from elsewhere ((N,) + m), without a solve"""
+        self.backend.hcond_set_correctors(self._handle(), self._dev(chi, (self.ndim,), "with_correctors: chi"))
+        self._tensor = None
+        return self
+
+    @property
+    def tensor(self):
+        if self._tensor is None:
+            self._tensor = self.backend.hcond_tensor(self._handle())
+        return self._tensor
+
+    def correctors(self):
+        return self._unflat(self.backend.hcond_correctors(self._handle()), (self.ndim,))
+
+    def _axis(self, k, what="the unit gradient"):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"homogenize_conductivity: {what} must be an integer, not {type(k).__name__}")
+        if not 0 <= int(k) < self.ndim:
+            raise ValueError(f"homogenize_conductivity: {what} {k} of {self.ndim}")
+        return int(k)
+
+    def corrector(self, k):
+        h = self._handle()
+        u = ROCMeshField(self.backend, self.mesh, self.bcs)
+        self.backend.hcond_corrector(h, self._axis(k), u.buf)
+        return u
+
+    def sensitivity(self, W):
+        W = np.asarray(W, dtype=np.float64)
+        N = self.ndim
+        if W.shape != (N, N) or not np.all(np.isfinite(W)) or not np.array_equal(W, W.T):
+            raise ValueError(f"homogenize_conductivity: W must be a finite symmetric {N}×{N} matrix")
+        g = ROCMeshField(self.backend, self.mesh, self.bcs)
+        self.backend.hcond_sensitivity(self._handle(), W, g.buf)
+        return g
+
+    def cells(self):
+        return self._unflat(self.backend.hcond_cells(self._handle()), ())
+
+    def apply(self, x):
+        """A x on all nodes, no pin: x a host array of shape m; returns one"""
+        return self._unflat(self.backend.hcond_apply(self._handle(), self._dev(x, (), "homogenize_conductivity: x")), ())
+
+    def load(self, k):
+        return self._unflat(self.backend.hcond_load(self._handle(), self._axis(k)), ())
+
+    def energy_cells(self, p, q):
+        return self._unflat(self.backend.hcond_energy_cells(self._handle(), self._axis(p), self._axis(q)), ())
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.hcond_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def homogenize_conductivity(phi_or_eq, *, a_in=1.0, a_out=1e-3, a=None, level=0.0, rtol=1e-8, max_iters=500, precond="mg", chi0=None):
+    """The effective conductivity tensor K^H of −∇·(a∇u) — thermal, electrical or diffusive — for the periodic material whose cell is the
+    box of ϕ's grid, on the device: elliptic_solve's edge discretisation and cell coefficients (a_out + (a_in −
+    a_out)·θ, or the cell array `a` of shape n − 1) with c = 0, on the torus of the grid's n − 1 cells per axis (node n − 1 is node 0; ϕ
+    needs no PeriodicBC, only its cells are read).  For each of the N unit gradients a periodic corrector χ^p (zero at node 0) is found
+    by conjugate gradients, from `chi0` ((N,) + (n − 1); zero without one) until ‖r‖₂ ≤ rtol·‖f^p‖₂, preconditioned by one wrapping
+    multigrid V-cycle (precond="mg") or the diagonal ("jacobi").  Returns a ConductivityHomogenization: `tensor`, `sensitivity(W)` and
+    the rest.  Raises ValueError / TypeError for what is refused (1-D, a band field, a slab, fewer than 2 cells in a dimension,
+    coefficients that are not finite and positive, non-finite data) and LsmNotConvergedError when max_iters does not suffice."""
+    hom = ConductivityHomogenization(phi_or_eq, a_in=a_in, a_out=a_out, a=a, level=level, precond=precond)
+    try:
+        return hom.solve(chi0=chi0, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        hom.close()
+        raise
+
+
 # ----------------------------------------------------------------------------- vibration modes (the eigenfrequency objective of a structural optimisation)
 
 def _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, from_phi):

@@ -641,6 +641,82 @@ class HipBackend:
     def homog_destroy(self, obj):
         self.lib.lsm_homog_destroy(obj)
 
+    # ---- conductivity homogenisation (lsm_hcond_*): vectors are flat float64 device tensors over the torus of n − 1 nodes per axis
+    def _hcond_sizes(self):
+        return self.ndim, int(np.prod([m - 1 for m in self.local_shape()]))
+
+    def hcond_create(self, phi, level, a_in, a_out, a_cells, precond):
+        """returns (object, (levels, free nodes, nodes of the torus, 0)); an LsmError raised for the data carries `reason` and `detail`"""
+        if self.slab is not None:
+            raise L.LsmError("hcond_create: this backend holds a slab of a decomposed grid; lsm_hcond_create works on the whole grid of one device")
+        out, stats = C.c_void_p(), (C.c_int64 * 4)()
+        code = self.lib.lsm_hcond_create(self.h, self.ptr(phi), float(level), float(a_in), float(a_out), self.ptr(a_cells), int(precond), C.byref(out), stats)
+        try:
+            L.check(self.h, code, "lsm_hcond_create")
+        except L.LsmError as e:
+            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0
+            e.detail = int(stats[1])
+            raise
+        return out, tuple(int(v) for v in stats)
+
+    def hcond_cells(self, obj):
+        out = self.torch.empty(self._hcond_sizes()[1], dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_hcond_cells(obj, self.ptr(out)), "lsm_hcond_cells")
+        return out
+
+    def hcond_apply(self, obj, x):
+        y = self.torch.empty_like(x)
+        L.check(self.h, self.lib.lsm_hcond_apply(obj, self.ptr(x), self.ptr(y)), "lsm_hcond_apply")
+        return y
+
+    def hcond_load(self, obj, k):
+        out = self.torch.empty(self._hcond_sizes()[1], dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_hcond_load(obj, int(k), self.ptr(out)), "lsm_hcond_load")
+        return out
+
+    def hcond_solve(self, obj, guess, rtol, max_iters):
+        """guess: a flat float64 device tensor of N·nn values or None; returns (iterations, relres), one entry per corrector"""
+        N = self.ndim
+        it, rel = (C.c_int * N)(), (C.c_double * N)()
+        L.check(self.h, self.lib.lsm_hcond_solve(obj, self.ptr(guess), float(rtol), int(max_iters), it, rel), "lsm_hcond_solve")
+        return [int(v) for v in it], [float(v) for v in rel]
+
+    def hcond_solve_rhs(self, obj, f, x, rtol, max_iters):
+        """x (in: the guess, out: the solution) and f are flat float64 device tensors of nn values; returns (iterations, relres)"""
+        it, rel = C.c_int(0), C.c_double(0.0)
+        L.check(self.h, self.lib.lsm_hcond_solve_rhs(obj, self.ptr(f), self.ptr(x), float(rtol), int(max_iters), C.byref(it), C.byref(rel)), "lsm_hcond_solve_rhs")
+        return it.value, rel.value
+
+    def hcond_set_correctors(self, obj, chi):
+        L.check(self.h, self.lib.lsm_hcond_set_correctors(obj, self.ptr(chi)), "lsm_hcond_set_correctors")
+
+    def hcond_correctors(self, obj):
+        N, nn = self._hcond_sizes()
+        out = self.torch.empty(N * nn, dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_hcond_correctors(obj, self.ptr(out)), "lsm_hcond_correctors")
+        return out
+
+    def hcond_energy_cells(self, obj, p, q):
+        out = self.torch.empty(self._hcond_sizes()[1], dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_hcond_energy_cells(obj, int(p), int(q), self.ptr(out)), "lsm_hcond_energy_cells")
+        return out
+
+    def hcond_tensor(self, obj):
+        N = self.ndim
+        out = np.zeros((N, N), dtype=np.float64)
+        L.check(self.h, self.lib.lsm_hcond_tensor(obj, out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_hcond_tensor")
+        return out
+
+    def hcond_corrector(self, obj, k, u):
+        L.check(self.h, self.lib.lsm_hcond_corrector(obj, int(k), self.ptr(u)), "lsm_hcond_corrector")
+
+    def hcond_sensitivity(self, obj, W, g):
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        L.check(self.h, self.lib.lsm_hcond_sensitivity(obj, W.ctypes.data_as(C.POINTER(C.c_double)), self.ptr(g)), "lsm_hcond_sensitivity")
+
+    def hcond_destroy(self, obj):
+        self.lib.lsm_hcond_destroy(obj)
+
     # ---- stress recovery (lsm_elastic_stress_*): `what` is L.STRESS_STRAIN, L.STRESS_STRESS or L.STRESS_VON_MISES
     def elastic_stress_cells(self, obj, u, what):
         """the component-major fp64 cell arrays as one flat device tensor"""

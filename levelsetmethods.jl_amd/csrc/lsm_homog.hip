@@ -9,9 +9,9 @@
 // zero on every level (fine node 2J = 0 is coarse node 0), which removes the translations; nothing else is fixed.  The correctors
 // are kept on the device, M vectors of N·nn doubles; a solve writes them only when all M have converged.
 //
-// What is mg_pcg.h's: the state, K2, the smoother, the coarsest kernel, the V-cycle's driver, the iteration loop, the report.  What
-// is this file's own: the wrapping apply (the Level), the wrapping gather and prolongation (mg_pcg.h calls them through the
-// Level), the load, and the cell kernels.
+// What is mg_pcg.h's: the state, K2, the smoother, the coarsest kernel, the wrapping gather and prolongation (launched through the
+// Level), the V-cycle's driver, the iteration loop, the report.  What is this file's own: the wrapping apply (the Level), the load,
+// and the cell kernels.
 #include <memory>
 
 #include "el_cell.h"
@@ -50,20 +50,6 @@ struct HgLevel {
     __device__ __forceinline__ void apply(int id, const int I[3], const double* x, int stride, double out[N]) const;
 };
 
-// c[d][o + 1] = ((I_d + o) mod n_d)·(the axis' stride), o ∈ {−1, 0, 1}: nodes and cells share it
-template <int N>
-__device__ __forceinline__ void hg_wrapped(const HgLevel& L, const int I[3], int c[3][3]) {
-    const int st[3] = {1, L.n[0], L.n[0] * L.n[1]};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        if (d < N) {
-            c[d][0] = (I[d] == 0 ? L.n[d] - 1 : I[d] - 1) * st[d];
-            c[d][1] = I[d] * st[d];
-            c[d][2] = (I[d] == L.n[d] - 1 ? 0 : I[d] + 1) * st[d];
-        } else c[d][0] = c[d][1] = c[d][2] = 0;
-    }
-}
-
 // (A x)_{I,·} in lsm_elastic.hip's order: the 2^N cells around I ascending (bit d of m set: cell I_d, clear: cell I_d − 1, wrapped);
 // per cell and row the columns from +0, corner b ascending, component j fastest; then the cell's modulus; the cell terms from +0.
 // xat(q, j): component j at node q.
@@ -71,7 +57,7 @@ template <int N, class X>
 __device__ __forceinline__ void hg_apply(const HgLevel& L, const int I[3], X xat, double out[N]) {
     constexpr int NC = 1 << N, NB = N == 2 ? 9 : 27, R = NC * N;
     int c[3][3];
-    hg_wrapped<N>(L, I, c);
+    mg_wrapped<N>(L.n, I, c);
     double v[NB][N];
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
@@ -107,17 +93,6 @@ __device__ __forceinline__ void hg_apply(const HgLevel& L, const int I[3], X xat
 template <int N, bool MASK>
 __device__ __forceinline__ void HgLevel::apply(int id, const int I[3], const double* x, int stride, double out[N]) const {
     hg_apply<N>(*this, I, [&](int q, int j) { return x[j * stride + q]; }, out);
-}
-
-// the 2^N corner nodes of cell C, wrapped
-template <int N>
-__device__ __forceinline__ void hg_corners(const HgLevel& L, const int C[3], int node[1 << N]) {
-    int up[3] = {0, 0, 0};
-#pragma unroll
-    for (int d = 0; d < N; ++d) up[d] = C[d] == L.n[d] - 1 ? 0 : C[d] + 1;
-#pragma unroll
-    for (int b = 0; b < (1 << N); ++b)
-        node[b] = ((b & 1) ? up[0] : C[0]) + L.n[0] * (((b >> 1) & 1 ? up[1] : C[1]) + (N > 2 ? L.n[1] * ((b >> 2) & 1 ? up[2] : C[2]) : 0));
 }
 
 // ---- setup of level 0: ϕ checked at every node of the dense grid; the cell moduli from ϕ (el_cell.h: lsm_elastic's array, the same
@@ -174,7 +149,7 @@ __global__ void __launch_bounds__(MG_THREADS) hg_diag_kernel(HgLevel L, double* 
     MG_LOOP(id, L.nn) {
         int I[3], c[3][3];
         mg_coords<N>(L.n, id, I);
-        hg_wrapped<N>(L, I, c);
+        mg_wrapped<N>(L.n, I, c);
         double acc[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) acc[i] = 0.0;
@@ -197,7 +172,7 @@ __global__ void __launch_bounds__(MG_THREADS) hg_load_kernel(HgLevel L, const do
     MG_LOOP(id, L.nn) {
         int I[3], c[3][3];
         mg_coords<N>(L.n, id, I);
-        hg_wrapped<N>(L, I, c);
+        mg_wrapped<N>(L.n, I, c);
         double acc[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) acc[i] = 0.0;
@@ -224,84 +199,6 @@ __global__ void __launch_bounds__(MG_THREADS) hg_apply_kernel(HgLevel L, const d
         hg_apply<N>(L, I, [&](int q, int j) { return x[j * nn + q]; }, out);
 #pragma unroll
         for (int i = 0; i < N; ++i) y[i * nn + id] = out[i];
-    }
-}
-
-// ---- the wrapping transfers, per component (blockIdx.y).  r_c[J] = 2^−k·Σ_o w_o·res[(2J + o) mod m], w = 1 at o = 0 and ½ at o = ±1
-// per coarsened axis (o0 fastest, from +0); zero at the pin
-template <int N>
-__global__ void __launch_bounds__(MG_THREADS) hg_gather_kernel(HgLevel Lf, HgLevel Lc, int co0, int co1, int co2, const double* __restrict__ res,
-                                                               double* __restrict__ rc, const MgState* st) {
-    if (st->status != MG_RUN) return;
-    const int co[3] = {co0, co1, co2};
-    const double scale = mg_coarsen_scale(co0 + co1 + co2);
-    const int comp = blockIdx.y;
-    res += (size_t)comp * Lf.nn;
-    rc += (size_t)comp * Lc.nn;
-    MG_LOOP(id, Lc.nn) {
-        double acc = 0.0;
-        if (id != 0) {
-            int J[3];
-            mg_coords<N>(Lc.n, id, J);
-            for (int m = 0; m < (N == 2 ? 9 : 27); ++m) {
-                const int o[3] = {m % 3 - 1, (m / 3) % 3 - 1, N > 2 ? m / 9 - 1 : 0};
-                int I[3] = {0, 0, 0};
-                double w = 1.0;
-                bool use = true;
-#pragma unroll
-                for (int d = 0; d < N; ++d) {
-                    if (!co[d]) {
-                        if (o[d] != 0) use = false;
-                        I[d] = J[d];
-                        continue;
-                    }
-                    I[d] = 2 * J[d] + o[d];
-                    if (I[d] < 0) I[d] += Lf.n[d];
-                    if (I[d] >= Lf.n[d]) I[d] -= Lf.n[d];
-                    if (o[d] != 0) w = w * 0.5;
-                }
-                if (use) acc += w * res[I[0] + Lf.n[0] * (I[1] + (N > 2 ? Lf.n[1] * I[2] : 0))];     // zero at the fine pin
-            }
-        }
-        rc[id] = acc * scale;
-    }
-}
-// x += P x_c away from the pin: the transpose of the gather without its 2^−k
-template <int N>
-__global__ void __launch_bounds__(MG_THREADS) hg_prolong_kernel(HgLevel Lf, HgLevel Lc, int co0, int co1, int co2, const double* __restrict__ xc,
-                                                                double* __restrict__ x, const MgState* st) {
-    if (st->status != MG_RUN) return;
-    const int co[3] = {co0, co1, co2};
-    const int comp = blockIdx.y;
-    xc += (size_t)comp * Lc.nn;
-    x += (size_t)comp * Lf.nn;
-    MG_LOOP(id, Lf.nn) {
-        if (id == 0) continue;
-        int I[3];
-        mg_coords<N>(Lf.n, id, I);
-        int J0[3] = {0, 0, 0}, J1[3] = {0, 0, 0}, two[3] = {0, 0, 0};
-#pragma unroll
-        for (int d = 0; d < N; ++d) {
-            J0[d] = co[d] ? I[d] >> 1 : I[d];
-            two[d] = co[d] && (I[d] & 1);
-            J1[d] = J0[d] + 1 == Lc.n[d] ? 0 : J0[d] + 1;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int m = 0; m < (1 << N); ++m) {
-            double w = 1.0;
-            bool use = true;
-            int J[3] = {0, 0, 0};
-#pragma unroll
-            for (int d = 0; d < N; ++d) {
-                const int b = (m >> d) & 1;
-                if (b && !two[d]) use = false;
-                if (two[d]) w = w * 0.5;
-                J[d] = b ? J1[d] : J0[d];
-            }
-            if (use) acc += w * xc[J[0] + Lc.n[0] * (J[1] + (N > 2 ? Lc.n[1] * J[2] : 0))];
-        }
-        x[id] = x[id] + acc;
     }
 }
 
@@ -389,7 +286,7 @@ __global__ void __launch_bounds__(MG_THREADS) hg_energy_kernel(HgLevel L, const 
     MG_LOOP(id, nn) {
         int C[3], node[NC];
         mg_coords<N>(L.n, id, C);
-        hg_corners<N>(L, C, node);
+        mg_wrapped_corners<N>(L.n, C, node);
         double wp[R], wq[R];
 #pragma unroll
         for (int b = 0; b < NC; ++b)
@@ -429,7 +326,7 @@ __global__ void __launch_bounds__(MG_THREADS) hg_tensor_kernel(HgLevel L, const 
     MG_LOOP(id, nn) {
         int C[3], node[NC];
         mg_coords<N>(L.n, id, C);
-        hg_corners<N>(L, C, node);
+        mg_wrapped_corners<N>(L.n, C, node);
         const double E = L.E[id];
         double w[M][R];
 #pragma unroll
@@ -475,7 +372,7 @@ __global__ void __launch_bounds__(MG_THREADS) hg_sens_gather_kernel(HgLevel L, H
         mg_coords<N>(G.n, id, I);
 #pragma unroll
         for (int d = 0; d < N; ++d) T[d] = I[d] == L.n[d] ? 0 : I[d];
-        hg_wrapped<N>(L, T, c);
+        mg_wrapped<N>(L.n, T, c);
         double acc = 0.0;
 #pragma unroll
         for (int m = 0; m < (1 << N); ++m) acc = acc + cell[c[0][m & 1] + c[1][(m >> 1) & 1] + (N > 2 ? c[2][(m >> 2) & 1] : 0)];
@@ -504,10 +401,10 @@ void HgLevel::launch_resid(int N, unsigned nb, hipStream_t s, const HgLevel& L, 
     MG_LAUNCH2(N, mg_resid_kernel, HgLevel, dim3(nb), dim3(MG_THREADS), s, L, r, x, res, st);
 }
 void HgLevel::launch_gather(int N, hipStream_t s, const HgLevel& Lf, const HgLevel& Lc, const int co[3], const double* res, double* rc, const MgState* st) {
-    MG_LAUNCH(N, hg_gather_kernel, dim3(mg_blocks(Lc.nn), N), MG_THREADS, s, Lf, Lc, co[0], co[1], co[2], res, rc, st);
+    MG_LAUNCH2(N, mg_wrap_gather_kernel, HgLevel, dim3(mg_blocks(Lc.nn), N), MG_THREADS, s, Lf, Lc, co[0], co[1], co[2], res, rc, st);
 }
 void HgLevel::launch_prolong(int N, hipStream_t s, const HgLevel& Lf, const HgLevel& Lc, const int co[3], const double* xc, double* x, const MgState* st) {
-    MG_LAUNCH(N, hg_prolong_kernel, dim3(mg_blocks(Lf.nn), N), MG_THREADS, s, Lf, Lc, co[0], co[1], co[2], xc, x, st);
+    MG_LAUNCH2(N, mg_wrap_prolong_kernel, HgLevel, dim3(mg_blocks(Lf.nn), N), MG_THREADS, s, Lf, Lc, co[0], co[1], co[2], xc, x, st);
 }
 
 struct HomogObject : MgSolver<HgLevel> {
