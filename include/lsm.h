@@ -641,7 +641,30 @@ void lsm_elliptic_destroy(LsmElliptic* s);
  *      q_C = sum_r u_r·(sum_s K0[r,s]·u_s), both sums from +0 ascending over the cell's 2^N·N corner values: the cell mean of
  *      E·C0 ε:ε, the integrand of the compliance shape derivative; into a dense field of the handle, rounded once.
  *      lsm_elastic_compliance: *out := prod h · sum b·u, reduced on the device in workgroup order.
- *      lsm_elastic_cells copies the level-0 cell moduli into a device buffer. */
+ *      lsm_elastic_cells copies the level-0 cell moduli into a device buffer.
+ *      lsm_elastic_solve_many: K load cases of the one operator (1 <= K <= LSM_ELASTIC_MAXCOLS) solved in the same launches.
+ *      Column k of the batch is lsm_elastic_solve of column k, bit for bit: the fields, the iteration count and the relative
+ *      residual (every column has the single solve's launch shape, arithmetic and order, and its own device state).  f is
+ *      K·N·nn fp64 on the device, column k at k·N·nn, component-major; u[k·N + i] is component i of column k, K·N distinct dense
+ *      fields of the handle holding the guess and the prescribed values.  iters, relres and status are host arrays of K,
+ *      filled for every column whatever the outcome; status: 1 converged, 2 out of iterations, −1 non-finite input, −2 breakdown
+ *      (p·Ap not positive), −3 breakdown (r·Mr not positive, or a non-finite residual).  A column that has ended is skipped by
+ *      its own workgroups while the others go on.  LSM_OK only when all columns converged, and only then are the free
+ *      components of all columns stored; otherwise no field of any column changes, the converged ones included, and the error
+ *      is LSM_ERR_INVALID if a column had non-finite input, else LSM_ERR_NOT_CONVERGED; the message names the lowest such column
+ *      with its iterations and residual.  LSM_ERR_INVALID without running anything: K out of range, a null or repeated field,
+ *      rtol not positive and finite, max_iters < 1.  The batch has a workspace of its own, allocated by the first call, kept on
+ *      the object and grown when a later call asks for more columns; when it cannot be allocated the HIP error is returned and
+ *      the object stays usable.  lsm_elastic_solve, the modes and the stress adjoint are unaffected by a batched call in
+ *      between.  Not to be called concurrently with another call on the object.
+ *      lsm_elastic_energy_many: e_I = sum_k w_k·e_{k,I}, k ascending from +0, e_{k,I} lsm_elastic_energy's value of column k in
+ *      fp64 before its rounding; rounded once to the storage type, ghosts untouched; one pass over the grid.  LSM_ERR_INVALID:
+ *      K out of range, a null or repeated field, an output that is an input, a weight that is not finite.
+ *      lsm_elastic_energy_mutual: m_I = (sum over the existing cells C around I, ascending, of E_C·q_C)/(their number),
+ *      q_C = sum_r u_r·(sum_s K0[r,s]·v_s), both sums from +0 in lsm_elastic_energy's order, rounded once: the integrand of the
+ *      shape derivative of l·u for the state K u = f and the adjoint K v = l.  With v = u it is lsm_elastic_energy bit for bit.
+ *      u and v may be the same fields; LSM_ERR_INVALID: a missing or repeated field within u or within v, an output that is an
+ *      input. */
 #define LSM_PLANE_STRESS 0
 #define LSM_PLANE_STRAIN 1
 typedef struct LsmElastic LsmElastic;
@@ -654,6 +677,12 @@ int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* 
 int lsm_elastic_energy(LsmElastic* s, const void* u0, const void* u1, const void* u2, void* e_out);
 int lsm_elastic_compliance(LsmElastic* s, const double* f, const void* u0, const void* u1, const void* u2, double* out);
 int lsm_elastic_cells(LsmElastic* s, double* e_out_cells);
+#define LSM_ELASTIC_MAXCOLS 8
+int lsm_elastic_solve_many(LsmElastic* s, int K, const double* f, void* const* u, double rtol, int max_iters, int* iters, double* relres,
+                           int* status, void* stream);
+int lsm_elastic_energy_many(LsmElastic* s, int K, void* const* u, const double* w, void* e_out);
+int lsm_elastic_energy_mutual(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* v0, const void* v1, const void* v2,
+                              void* e_out);
 void lsm_elastic_destroy(LsmElastic* s);
 
 /* ---- homogenize: the effective elasticity tensor C^H of the periodic material whose cell is the box of a dense 2-D or 3-D grid,

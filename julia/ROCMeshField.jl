@@ -667,6 +667,37 @@ end
 # the level-0 cell moduli into a ROCArray{Float64} of size n .- 1
 elasticity_cells!(a, K) = _check(K.h.ptr, ccall((:lsm_elastic_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), K.op, pointer(a)), "lsm_elastic_cells")
 
+# the field pointers of K columns of N fields each, column by column (include/lsm.h: u[k·N + i])
+_ucols(us) = Ptr{Cvoid}[pointer(c.buf) for u in us for c in u]
+
+# elasticity_solve_many!: K ≤ 8 load cases of one operator in one batched solve.  us: K tuples of N fields (guess and prescribed values in,
+# solutions out); f: a ROCArray{Float64} of K·N·nn values, column k at (k-1)·N·nn.  Column k is elasticity_solve! of column k bit for bit.
+# Returns the K iteration counts, residuals and statuses; unless every column converges it throws and leaves every field untouched.
+function elasticity_solve_many!(us, K, f; rtol = 1e-8, max_iters = 500)
+    nk = length(us)
+    iters, relres, status = zeros(Cint, nk), zeros(Float64, nk), zeros(Cint, nk)
+    p = _ucols(us)
+    _check(K.h.ptr, ccall((:lsm_elastic_solve_many, libhiplsm), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Ptr{Cvoid}}, Float64, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint}, Ptr{Cvoid}),
+        K.op, nk, pointer(f), p, rtol, max_iters, iters, relres, status, C_NULL), "lsm_elastic_solve_many")
+    return (; iterations = iters, relres = relres, status = status)
+end
+
+# Σ_k w_k·(the energy density of column k) into the field e, in one pass: the normal speed of a weighted multi-load compliance descent
+function elasticity_energy_many!(e::ROCMeshField, K, us, w)
+    p, wv = _ucols(us), collect(Float64, w)
+    _check(K.h.ptr, ccall((:lsm_elastic_energy_many, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Cvoid}),
+        K.op, length(us), p, wv, pointer(e.buf)), "lsm_elastic_energy_many")
+end
+
+# the mutual energy density E·C₀ε(u):ε(v) at the nodes into the field e: the shape-derivative integrand of l·u for the adjoint K v = l
+function elasticity_energy_mutual!(e::ROCMeshField, K, u, v)
+    p, q = _u3(u), _u3(v)
+    _check(K.h.ptr, ccall((:lsm_elastic_energy_mutual, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        K.op, p[1], p[2], p[3], q[1], q[2], q[3], pointer(e.buf)), "lsm_elastic_energy_mutual")
+end
+
 destroy_elasticity(K) = ccall((:lsm_elastic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), K.op)
 
 # homogenize: the effective elasticity tensor of the periodic material whose cell is the box of ϕ (include/lsm.h, lsm_homog_*).  The torus

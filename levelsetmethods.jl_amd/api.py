@@ -2888,6 +2888,17 @@ class ElasticitySolution:
         op.backend.elastic_energy(op._handle(), [c.buf for c in self.u], e.buf)
         return e
 
+    def mutual_energy_density(self, other):
+        """the ROCMeshField of m_I = the mean over the cells around I of E_C·(C₀ε(u):ε(v) averaged over the cell), v = other.u: the
+        integrand of the shape derivative of l·u for this state and the adjoint `other` (K v = l) of the same operator (DESIGN.md
+        §7.25).  With other = self it is energy_density() bit for bit."""
+        op = self.operator
+        if not isinstance(other, ElasticitySolution) or other.operator is not op:
+            raise ValueError("mutual_energy_density: the other solution belongs to another operator")
+        e = ROCMeshField(op.backend, self.u[0].mesh, self.u[0].bcs)
+        op.backend.elastic_energy_mutual(op._handle(), [c.buf for c in self.u], [c.buf for c in other.u], e.buf)
+        return e
+
     def compliance(self):
         op = self.operator
         if self._f is None:
@@ -2975,6 +2986,62 @@ class ElasticitySolution:
         adjoint = ElasticitySolution(op, lam, load, it, rel)
         b.elastic_stress_sensitivity(h, ubufs, [c.buf for c in lam], p, sref_used, value / (p * J), field.buf)
         return StressSensitivity(value, field, adjoint, it, p, sref_used)
+
+
+class ElasticityMultiSolution:
+    """solve_many's result: a sequence of K ElasticitySolutions of one operator (len, indexing, iteration), each with its own u,
+    iterations, relres and load, so that compliance(), the stress recovery, topological_derivative() and stress_sensitivity() work on
+    a column.  `iterations` and `relres` are tuples, `operator` and `levels` as on a single solution.  compliances() → the K values;
+    compliance(weights=None) = Σ w_k·c_k (weights default to 1); cross_compliance(i, j) = ∏h·Σ (m·f_i)·u_j; energy_density(weights=None)
+    → the ROCMeshField of Σ_k w_k·e_k in one pass over the grid; mutual_energy_density(i, j) → that of columns i and j."""
+
+    def __init__(self, op, columns):
+        self.operator, self._columns, self.levels = op, tuple(columns), op.levels
+        self.iterations = tuple(c.iterations for c in self._columns)
+        self.relres = tuple(c.relres for c in self._columns)
+
+    def __len__(self):
+        return len(self._columns)
+
+    def __getitem__(self, k):
+        return self._columns[k]
+
+    def __iter__(self):
+        return iter(self._columns)
+
+    def _weights(self, weights, what):
+        K = len(self._columns)
+        w = [1.0] * K if weights is None else [float(v) for v in weights]
+        if len(w) != K:
+            raise ValueError(f"{what}: {len(w)} weights for {K} columns")
+        if not all(math.isfinite(v) for v in w):
+            raise ValueError(f"{what}: the weights must be finite")
+        return w
+
+    def compliances(self):
+        return tuple(c.compliance() for c in self._columns)
+
+    def compliance(self, weights=None):
+        w = self._weights(weights, "compliance")
+        total = 0.0
+        for wk, ck in zip(w, self.compliances()):
+            total = total + wk * ck
+        return total
+
+    def cross_compliance(self, i, j):
+        op = self.operator
+        return op.backend.elastic_compliance(op._handle(), self._columns[i]._f, [c.buf for c in self._columns[j].u])
+
+    def energy_density(self, weights=None):
+        op = self.operator
+        w = self._weights(weights, "energy_density")
+        u0 = self._columns[0].u[0]
+        e = ROCMeshField(op.backend, u0.mesh, u0.bcs)
+        op.backend.elastic_energy_many(op._handle(), [[c.buf for c in col.u] for col in self._columns], w, e.buf)
+        return e
+
+    def mutual_energy_density(self, i, j):
+        return self._columns[i].mutual_energy_density(self._columns[j])
 
 
 def _stress_args(p, sref):
@@ -3139,6 +3206,41 @@ class ElasticityOperator:
             raise
         return ElasticitySolution(self, u, fd, it, rel)
 
+    def solve_many(self, fs, u0=None, homogeneous=None, rtol=1e-8, max_iters=500):
+        """K = len(fs) ≤ 8 load cases of this operator in one batched solve → ElasticityMultiSolution.  Column k is solve(fs[k], u0[k]) bit
+        for bit: u, iterations and relres.  `fs`: a sequence of loads, each in any form solve takes; `u0`: None or a
+        sequence of guesses (an entry may be None); `homogeneous`: a sequence of booleans — a true column takes zero on the fixed
+        components instead of the prescribed values (an adjoint column).  Unless every column converges nothing is kept:
+        LsmNotConvergedError carries .iterations, .relres and .status (1 converged, 2 out of iterations, −2 / −3 breakdown) tuples;
+        ValueError for what is refused and for non-finite data, naming the column."""
+        b = self.backend
+        h = self._handle()
+        what = "elasticity_solve_many"
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError(f"{what}: rtol must be positive and finite, max_iters at least 1")
+        if not isinstance(fs, (tuple, list)):
+            raise TypeError(f"{what}: fs must be a sequence of loads")
+        K = len(fs)
+        if not 1 <= K <= b.ELASTIC_MAXCOLS:
+            raise ValueError(f"{what}: {K} load cases (1 to {b.ELASTIC_MAXCOLS} are solved together)")
+        u0 = [None] * K if u0 is None else list(u0)
+        homogeneous = [False] * K if homogeneous is None else [bool(v) for v in homogeneous]
+        if len(u0) != K or len(homogeneous) != K:
+            raise ValueError(f"{what}: u0 and homogeneous must have one entry per load case ({K})")
+        fds = [self._load(f) for f in fs]
+        us = [self._fields(u0[k], fixed="zero" if homogeneous[k] else "prescribed", what=f"{what}: u0[{k}]") for k in range(K)]
+        try:
+            its, rels, _ = b.elastic_solve_many(h, b.torch.cat(fds), [[c.buf for c in u] for u in us], rtol, int(max_iters))
+        except L.LsmNotConvergedError:
+            raise
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                col = [k for k, v in enumerate(getattr(e, "status", ())) if v == -1]
+                raise ValueError(f"{what}: f, u0 and the Dirichlet values must be finite (column {col[0] if col else '?'})") from None
+            raise
+        return ElasticityMultiSolution(self, [ElasticitySolution(self, us[k], fds[k], its[k], rels[k]) for k in range(K)])
+
     def apply(self, x):
         """A x on all components, no elimination: x a host array of shape (N,)+n; returns one (for tests and diagnostics)"""
         b, N = self.backend, self.ndim
@@ -3185,6 +3287,19 @@ def elasticity_solve(phi_or_eq, f, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plan
     op = ElasticityOperator(phi_or_eq, E_in=E_in, E_out=E_out, E=E, nu=nu, plane=plane, dirichlet=dirichlet, level=level, precond=precond)
     try:
         return op.solve(f, u0=u0, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        op.close()
+        raise
+
+
+def elasticity_solve_many(phi_or_eq, fs, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", dirichlet=None, u0=None, homogeneous=None, level=0.0,
+                          rtol=1e-8, max_iters=500, precond="mg"):
+    """elasticity_solve for K ≤ 8 load cases `fs` of the one structure, solved together on the device (ElasticityOperator.solve_many):
+    several load cases of a compliance design, or a state and its adjoint (homogeneous=(False, True)) whose mutual_energy_density is
+    the speed of a displacement objective.  Returns an ElasticityMultiSolution; the other arguments are elasticity_solve's."""
+    op = ElasticityOperator(phi_or_eq, E_in=E_in, E_out=E_out, E=E, nu=nu, plane=plane, dirichlet=dirichlet, level=level, precond=precond)
+    try:
+        return op.solve_many(fs, u0=u0, homogeneous=homogeneous, rtol=rtol, max_iters=max_iters)
     except BaseException:
         op.close()
         raise

@@ -547,6 +547,35 @@ class HipBackend:
         L.check(self.h, self.lib.lsm_elastic_compliance(obj, self.ptr(f), *self._u3(u), C.byref(out)), "lsm_elastic_compliance")
         return out.value
 
+    ELASTIC_MAXCOLS = 8
+
+    def _ucols(self, us):
+        """the K·N field pointers of K columns of N fields as a C array"""
+        ptrs = [int(c.data_ptr()) for u in us for c in u]
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def elastic_solve_many(self, obj, f, us, rtol, max_iters):
+        """K columns in one batched solve: f the K·N·nn loads, us K lists of N fields.  Returns (iterations, relres, status) tuples; raises
+        after setting .iterations, .relres, .status on the error when the library filled them"""
+        K = len(us)
+        it, rel, stat = (C.c_int * K)(), (C.c_double * K)(), (C.c_int * K)()
+        code = self.lib.lsm_elastic_solve_many(obj, K, self.ptr(f), self._ucols(us), float(rtol), int(max_iters), it, rel, stat, None)
+        out = tuple(int(v) for v in it), tuple(float(v) for v in rel), tuple(int(v) for v in stat)
+        if code != L.OK:
+            try:
+                L.check(self.h, code, "lsm_elastic_solve_many")
+            except L.LsmError as e:
+                e.iterations, e.relres, e.status = out
+                raise
+        return out
+
+    def elastic_energy_many(self, obj, us, w, e):
+        K = len(us)
+        L.check(self.h, self.lib.lsm_elastic_energy_many(obj, K, self._ucols(us), (C.c_double * K)(*[float(v) for v in w]), self.ptr(e)), "lsm_elastic_energy_many")
+
+    def elastic_energy_mutual(self, obj, u, v, e):
+        L.check(self.h, self.lib.lsm_elastic_energy_mutual(obj, *self._u3(u), *self._u3(v), self.ptr(e)), "lsm_elastic_energy_mutual")
+
     def elastic_cells(self, obj):
         n = self.local_shape()
         out = self.torch.empty(int(np.prod([m - 1 for m in n])), dtype=self.torch.float64, device=self.device)

@@ -48,12 +48,22 @@ struct EsLevel {
     __device__ __forceinline__ bool fixed(int id, int i) const { return (mask[id] >> i) & 1; }
     __device__ __forceinline__ double omega() const { return om; }
     static void launch_resid(int N, unsigned nb, hipStream_t s, const EsLevel& L, const double* r, const double* x, double* res, const MgState* st);
+    static void launch_resid_many(int N, unsigned nb, unsigned cols, hipStream_t s, const EsLevel& L, const double* r, const double* x, double* res,
+                                  const MgState* st);
     // the eliminated operator's N rows at a node; x holds zero on the fixed components, so there is nothing to mask
     template <int N, bool MASK>
     __device__ __forceinline__ void apply(int id, const int I[3], const double* x, int stride, double out[N]) const;
 };
 
 struct EsU { void* p[3]; };
+// the fields of the columns of a batched solve (mg_pcg.h: the column is blockIdx.z) and their weights
+struct EsUMany { void* p[MG_MAXCOLS][3]; };
+struct EsW { double w[MG_MAXCOLS]; };
+static_assert(MG_MAXCOLS == LSM_ELASTIC_MAXCOLS, "the batch of mg_pcg.h carries the columns that include/lsm.h promises");
+template <class UT>
+constexpr bool es_many = std::is_same<UT, EsUMany>::value;
+__device__ __forceinline__ void* es_u(const EsU& U, int i) { return U.p[i]; }
+__device__ __forceinline__ void* es_u(const EsUMany& U, int i) { return U.p[blockIdx.z][i]; }
 
 // cell m of the 2^N around node I (bit d of m set: cell index I_d along d, clear: I_d − 1): its modulus, or zero where there is none
 template <int N>
@@ -253,6 +263,97 @@ __global__ void __launch_bounds__(MG_THREADS) es_energy_kernel(EsLevel L, MgFiel
     }
 }
 
+// ---- the weighted energy density of K columns in one pass: e_I = Σ_k w_k·e_{k,I} (k ascending, from +0), e_{k,I} es_energy_kernel's value of
+// column k in fp64.  A node loops over its cells and, inside, over the columns: the cell's modulus is read once for all of them.  The K
+// accumulators of a lane live in LDS (a column each, indexed by the loop's k): as a register array they would be indexed dynamically
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) es_energy_many_kernel(EsLevel L, MgField F, EsUMany U, int ncol, EsW W, void* __restrict__ e_out) {
+    constexpr int NC = 1 << N, R = NC * N;
+    __shared__ double accs[MG_MAXCOLS][MG_THREADS];
+    const double* __restrict__ K = L.K;
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
+#pragma unroll 1
+        for (int k = 0; k < ncol; ++k) accs[k][threadIdx.x] = 0.0;
+        double cnt = 0.0;
+#pragma unroll 1
+        for (int m = 0; m < NC; ++m) {
+            bool in;
+            const double E = es_cell<N>(L, I, m, in);
+            if (!in) continue;
+            const long long c0 = at + ((m & 1) - 1) + (((m >> 1) & 1) - 1) * F.s1 + (N > 2 ? (((m >> 2) & 1) - 1) * F.s2 : 0);     // the cell's lowest corner
+#pragma unroll 1
+            for (int k = 0; k < ncol; ++k) {
+                double uc[R];
+#pragma unroll
+                for (int b = 0; b < NC; ++b) {
+                    const long long o = (b & 1) + ((b >> 1) & 1) * F.s1 + (N > 2 ? ((b >> 2) & 1) * F.s2 : 0);
+#pragma unroll
+                    for (int j = 0; j < N; ++j) uc[b * N + j] = ld_val(U.p[k][j], c0 + o, F.f32);
+                }
+                double q = 0.0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int s = 0; s < R; ++s) t = t + K[r * R + s] * uc[s];
+                    q = q + uc[r] * t;
+                }
+                accs[k][threadIdx.x] = accs[k][threadIdx.x] + E * q;
+            }
+            cnt = cnt + 1.0;
+        }
+        double e = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < ncol; ++k) e = e + W.w[k] * (accs[k][threadIdx.x] / cnt);
+        st_val(e_out, at, F.f32, e);
+    }
+}
+
+// ---- the mutual energy density m_I = (Σ_C E_C·q_C)/(existing cells around I), q_C = Σ_r u_r·(Σ_s K0[r,s]·v_s): es_energy_kernel's sums with v
+// in the inner one, so that v = u gives its bits
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) es_energy_mutual_kernel(EsLevel L, MgField F, EsU U, EsU V, void* __restrict__ e_out) {
+    constexpr int NC = 1 << N, R = NC * N;
+    const double* __restrict__ K = L.K;
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
+        double acc = 0.0, cnt = 0.0;
+#pragma unroll 1
+        for (int m = 0; m < NC; ++m) {
+            bool in;
+            const double E = es_cell<N>(L, I, m, in);
+            if (!in) continue;
+            const long long c0 = at + ((m & 1) - 1) + (((m >> 1) & 1) - 1) * F.s1 + (N > 2 ? (((m >> 2) & 1) - 1) * F.s2 : 0);     // the cell's lowest corner
+            double uc[R], vc[R];
+#pragma unroll
+            for (int b = 0; b < NC; ++b) {
+                const long long o = (b & 1) + ((b >> 1) & 1) * F.s1 + (N > 2 ? ((b >> 2) & 1) * F.s2 : 0);
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    uc[b * N + j] = ld_val(U.p[j], c0 + o, F.f32);
+                    vc[b * N + j] = ld_val(V.p[j], c0 + o, F.f32);
+                }
+            }
+            double q = 0.0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int s = 0; s < R; ++s) t = t + K[r * R + s] * vc[s];
+                q = q + uc[r] * t;
+            }
+            acc = acc + E * q;
+            cnt = cnt + 1.0;
+        }
+        st_val(e_out, at, F.f32, acc / cnt);
+    }
+}
+
 // ---- Πh·Σ b·u is finished on the host: this reduces Σ (m·f)·u over the components
 template <int N>
 __global__ void __launch_bounds__(MG_THREADS) es_compliance_kernel(EsLevel L, MgField F, const double* __restrict__ f, EsU U, double* partial, MgState* st) {
@@ -271,26 +372,36 @@ __global__ void __launch_bounds__(MG_THREADS) es_compliance_kernel(EsLevel L, Mg
 
 // ---- PCG
 // x₀ = u (the guess and the prescribed values) as fp64, p = 0
-template <int N>
-__global__ void __launch_bounds__(MG_THREADS) es_load_kernel(EsLevel L, MgField F, EsVec V, EsU U) {
+template <int N, class UT = EsU>
+__global__ void __launch_bounds__(MG_THREADS) es_load_kernel(EsLevel L, MgField F, EsVec V, UT U) {
     const int nn = L.nn;
+    if constexpr (es_many<UT>) {
+        const size_t at = (size_t)blockIdx.z * N * nn;
+        V.x += at; V.p += at;
+    }
     MG_LOOP(id, nn) {
         int I[3];
         mg_coords<N>(L.n, id, I);
         const long long at = mg_padded(F, I);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            V.x[i * nn + id] = ld_val(U.p[i], at, F.f32);
+            V.x[i * nn + id] = ld_val(es_u(U, i), at, F.f32);
             V.p[i * nn + id] = 0.0;
         }
     }
 }
 // b = m·f, r₀ = b − A x₀ on the free components, 0 on the fixed ones; ‖b_free‖², ‖r₀‖²; jac: z = r/D and ρ = r·z as well
-template <int N>
+template <int N, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) es_init_kernel(EsLevel L, EsVec V, const double* __restrict__ x, const double* __restrict__ f,
                                                              double* __restrict__ rv, double* __restrict__ zv, int jac) {
     double red[4] = {0.0, 0.0, 0.0, 0.0};     // ‖b_free‖², ‖r₀‖², r·z, non-finite entries (a count below 2^53: exact)
     const int nn = L.nn;
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z, at = c * N * nn;
+        x += at; f += at; rv += at; zv += at;
+        V.partial += c * (4 * MG_MAXB);
+        V.st += c;
+    }
     MG_LOOP(id, nn) {
         int I[3];
         mg_coords<N>(L.n, id, I);
@@ -321,7 +432,13 @@ __global__ void __launch_bounds__(MG_THREADS) es_init_kernel(EsLevel L, EsVec V,
 }
 
 // the search direction over the nt = N·nn unknowns, in place: p = z + β p (z and p are zero on the fixed components, so p stays zero there)
+template <int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) es_dir_kernel(int nt, EsVec V) {
+    if constexpr (MANY) {
+        const size_t at = (size_t)blockIdx.z * nt;
+        V.z += at; V.p += at;
+        V.st += blockIdx.z;
+    }
     if (V.st->status != MG_RUN) return;
     const double beta = V.st->beta;
     const double* __restrict__ z = V.z;
@@ -331,8 +448,14 @@ __global__ void __launch_bounds__(MG_THREADS) es_dir_kernel(int nt, EsVec V) {
 // K1: q = A p, σ = p·q, α = ρ/σ.  The direction has a pass of its own, in place: one vector less than lsm_elliptic.hip's double-buffered
 // p, and the apply loads 3^N·N values, not twice as many.  The vectors are __restrict__ parameters, not fields of V: read through
 // the struct, this kernel and es_init_kernel compiled to 3.2 KB of scratch per lane in 3-D.
-template <int N>
+template <int N, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) es_k1_kernel(EsLevel L, const double* __restrict__ p, double* __restrict__ qv, double* partial, MgState* st) {
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z, at = c * N * L.nn;
+        p += at; qv += at;
+        partial += c * (4 * MG_MAXB);
+        st += c;
+    }
     if (st->status != MG_RUN) return;
     const int nn = L.nn;
     double red[1] = {0.0};
@@ -356,22 +479,29 @@ __global__ void __launch_bounds__(MG_THREADS) es_k1_kernel(EsLevel L, const doub
 }
 
 // ---- x → u on the free components (rounded to the storage type); the fixed components and the ghosts are left as they are
-template <int N>
-__global__ void __launch_bounds__(MG_THREADS) es_store_kernel(EsLevel L, MgField F, const double* __restrict__ x, EsU U) {
+template <int N, class UT = EsU>
+__global__ void __launch_bounds__(MG_THREADS) es_store_kernel(EsLevel L, MgField F, const double* __restrict__ x, UT U) {
+    if constexpr (es_many<UT>) x += (size_t)blockIdx.z * N * L.nn;
     MG_LOOP(id, L.nn) {
         int I[3];
         mg_coords<N>(L.n, id, I);
         const long long at = mg_padded(F, I);
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            if (!L.fixed(id, i)) st_val(U.p[i], at, F.f32, x[i * L.nn + id]);
+            if (!L.fixed(id, i)) st_val(es_u(U, i), at, F.f32, x[i * L.nn + id]);
     }
 }
 
 // the V-cycle's fine residual in 2-D, zero on the fixed components.  mg_resid_kernel<2, EsLevel> is the same loop with the operator
 // called through EsLevel::apply, and compiled to 106 SGPRs where this form takes 98: one wave per SIMD less.
+template <int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) es_resid2_kernel(EsLevel L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ res,
                                                                const MgState* st) {
+    if constexpr (MANY) {
+        const size_t at = (size_t)blockIdx.z * 2 * L.nn;
+        r += at; x += at; res += at;
+        st += blockIdx.z;
+    }
     if (st->status != MG_RUN) return;
     const int nn = L.nn;
     MG_LOOP(id, nn) {
@@ -386,13 +516,21 @@ __global__ void __launch_bounds__(MG_THREADS) es_resid2_kernel(EsLevel L, const 
 
 // ---- host side
 void EsLevel::launch_resid(int N, unsigned nb, hipStream_t s, const EsLevel& L, const double* r, const double* x, double* res, const MgState* st) {
-    if (N == 2) hipLaunchKernelGGL(es_resid2_kernel, dim3(nb), dim3(MG_THREADS), 0, s, L, r, x, res, st);
+    if (N == 2) hipLaunchKernelGGL(es_resid2_kernel<>, dim3(nb), dim3(MG_THREADS), 0, s, L, r, x, res, st);
     else hipLaunchKernelGGL((mg_resid_kernel<3, EsLevel>), dim3(nb), dim3(MG_THREADS), 0, s, L, r, x, res, st);
+}
+void EsLevel::launch_resid_many(int N, unsigned nb, unsigned cols, hipStream_t s, const EsLevel& L, const double* r, const double* x, double* res,
+                                const MgState* st) {
+    if (N == 2) hipLaunchKernelGGL(es_resid2_kernel<1>, dim3(nb, 1, cols), dim3(MG_THREADS), 0, s, L, r, x, res, st);
+    else hipLaunchKernelGGL((mg_resid_kernel<3, EsLevel, 1>), dim3(nb, 1, cols), dim3(MG_THREADS), 0, s, L, r, x, res, st);
 }
 struct ElasticObject : MgSolver<EsLevel> {
     std::vector<std::vector<double>> k0; // the levels' K0 as computed (what the device holds)
     double lam = 0.0, mu = 0.0;          // the material at E = 1 (plane-dependent), for the stress recovery
     int plane = 0;
+    // the batched solve's workspace: the vectors, states and partials of `cols` columns, with the levels (the operator's data) shared.
+    // Made by the first lsm_elastic_solve_many, grown when a later one asks for more columns; the single solve's workspace is not touched
+    std::unique_ptr<MgSolver<EsLevel>> many;
 };
 
 // the unit element matrix of a box cell with sides h, scaled by 1/∏h (include/lsm.h states the formula): a product over the axes
@@ -670,7 +808,7 @@ int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* 
     LSM_HIP(h, hipGetLastError());
     const int r1 = mg_iterate(h, o, max_iters, st, [&](int) {
         if (!jac) mg_vcycle(o, o.V.r, st);
-        hipLaunchKernelGGL(es_dir_kernel, dim3(nbt), dim3(MG_THREADS), 0, st, nt, o.V);
+        hipLaunchKernelGGL(es_dir_kernel<>, dim3(nbt), dim3(MG_THREADS), 0, st, nt, o.V);
         MG_LAUNCH(N, es_k1_kernel, dim3(nb), MG_THREADS, st, L, (const double*)o.V.p, o.V.q, o.partial.p, o.st.p);
         if (jac) hipLaunchKernelGGL(mg_k2_kernel<1>, dim3(nbt), dim3(MG_THREADS), 0, st, L.D, nt, (MgVec)o.V, (const double*)o.V.p);
         else hipLaunchKernelGGL(mg_k2_kernel<0>, dim3(nbt), dim3(MG_THREADS), 0, st, L.D, nt, (MgVec)o.V, (const double*)o.V.p);
@@ -681,6 +819,139 @@ int lsm_elastic_solve(LsmElastic* s, const double* f, void* u0, void* u1, void* 
     MG_LAUNCH(N, es_store_kernel, dim3(nb), MG_THREADS, st, L, o.F, (const double*)o.V.x, U);
     LSM_HIP(h, hipGetLastError());
     LSM_HIP(h, hipStreamSynchronize(st));
+    return LSM_OK;
+}
+
+// the batch workspace for K columns.  A larger one is built beside the old and takes its place only when every allocation succeeded
+static int es_many_reserve(LsmHandle* h, ElasticObject& o, int K) {
+    if (o.many && o.many->cols >= K) return LSM_OK;
+    std::unique_ptr<MgSolver<EsLevel>> w(new MgSolver<EsLevel>());
+    MgSolver<EsLevel>& M = *w;
+    const int N = o.N, nl = (int)o.lev.size();
+    M.N = N; M.precond = o.precond; M.cols = K; M.F = o.F;
+    M.lev = o.lev;
+    memcpy(M.co, o.co, sizeof(M.co));
+    size_t nd = 0;
+    for (int l = 0; l < nl; ++l) nd += (size_t)K * (size_t)N * (size_t)o.lev[l].nn * (size_t)(l ? 3 : 6);
+    LSM_HIP(h, M.buf.alloc(nd * sizeof(double)));
+    LSM_HIP(h, M.partial.alloc((size_t)K * 4 * MG_MAXB * sizeof(double)));
+    LSM_HIP(h, M.st.alloc(K * sizeof(MgState)));
+    LSM_HIP(h, M.h_st.alloc(K * sizeof(MgState)));
+    M.rhs.assign(nl, nullptr); M.xa.assign(nl, nullptr); M.xb.assign(nl, nullptr);
+    double* b = M.buf;
+    for (int l = 0; l < nl; ++l) {
+        const size_t m = (size_t)K * (size_t)N * (size_t)o.lev[l].nn;
+        M.xa[l] = b; b += m;
+        M.xb[l] = b; b += m;
+        if (l) { M.rhs[l] = b; b += m; }
+        else {
+            M.V.x = b; b += m; M.V.r = b; b += m; M.V.q = b; b += m; M.V.p = b; b += m;
+        }
+    }
+    M.V.z = o.precond == LSM_PRECOND_JACOBI ? M.xa[0] : M.xb[0];
+    M.V.partial = M.partial;
+    M.V.st = M.st;
+    o.many = std::move(w);
+    return LSM_OK;
+}
+
+// the K·N fields of a batched call: all given, no two the same
+static bool es_fields_many(int N, int K, void* const* u, EsUMany& U) {
+    memset(&U, 0, sizeof(U));
+    if (!u) return false;
+    for (int a = 0; a < K * N; ++a) {
+        if (!u[a]) return false;
+        for (int b = 0; b < a; ++b)
+            if (u[b] == u[a]) return false;
+        U.p[a / N][a % N] = u[a];
+    }
+    return true;
+}
+
+int lsm_elastic_solve_many(LsmElastic* s, int K, const double* f, void* const* u, double rtol, int max_iters, int* iters, double* relres, int* status,
+                           void* stream) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    ElasticObject& o = *s->o;
+    EsUMany U;
+    if (K < 1 || K > LSM_ELASTIC_MAXCOLS) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_solve_many: K must be 1 ... LSM_ELASTIC_MAXCOLS (8)");
+    if (!f || !iters || !relres || !status || !es_fields_many(o.N, K, u, U))
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_solve_many: f, the K·N distinct fields of u and the three result arrays must be given");
+    if (!(rtol > 0) || !std::isfinite(rtol) || max_iters < 1)
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_solve_many: rtol must be positive and max_iters at least 1");
+    const int N = o.N;
+    const EsLevel& L = o.lev[0];
+    const int jac = o.precond == LSM_PRECOND_JACOBI;
+    (void)hipSetDevice(h->device);
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int ra = es_many_reserve(h, o, K);
+    if (ra != LSM_OK) return ra;
+    MgSolver<EsLevel>& M = *o.many;
+    const int r0 = mg_reset(h, M, rtol, max_iters, st, K);
+    if (r0 != LSM_OK) return r0;
+    const unsigned nb = mg_blocks(L.nn), nbt = mg_blocks((long long)N * L.nn), nz = (unsigned)K;
+    const int nt = N * L.nn;
+    MG_LAUNCH2(N, es_load_kernel, EsUMany, dim3(nb, 1, nz), MG_THREADS, st, L, o.F, M.V, U);
+    MG_LAUNCH2(N, es_init_kernel, 1, dim3(nb, 1, nz), MG_THREADS, st, L, M.V, (const double*)M.V.x, f, M.V.r, M.V.z, jac);
+    LSM_HIP(h, hipGetLastError());
+    const int r1 = mg_iterate(h, M, max_iters, st, [&](int) {
+        if (!jac) mg_vcycle<1>(M, M.V.r, st, K);
+        hipLaunchKernelGGL(es_dir_kernel<1>, dim3(nbt, 1, nz), dim3(MG_THREADS), 0, st, nt, M.V);
+        MG_LAUNCH2(N, es_k1_kernel, 1, dim3(nb, 1, nz), MG_THREADS, st, L, (const double*)M.V.p, M.V.q, M.partial.p, M.st.p);
+        if (jac) hipLaunchKernelGGL((mg_k2_kernel<1, 1>), dim3(nbt, 1, nz), dim3(MG_THREADS), 0, st, L.D, nt, (MgVec)M.V, (const double*)M.V.p);
+        else hipLaunchKernelGGL((mg_k2_kernel<0, 1>), dim3(nbt, 1, nz), dim3(MG_THREADS), 0, st, L.D, nt, (MgVec)M.V, (const double*)M.V.p);
+    }, K);
+    if (r1 != LSM_OK) return r1;
+    // every column's outcome; the error is that of the lowest column with non-finite input, else of the lowest that did not converge
+    int bad = -1, bad_input = -1;
+    for (int k = 0; k < K; ++k) {
+        const MgState& S = M.h_st.p[k];
+        iters[k] = S.iters;
+        relres[k] = mg_relres(S);
+        status[k] = S.status == MG_RUN ? (int)MG_MAXITER : S.status;
+        if (S.status == MG_BREAK_INPUT && bad_input < 0) bad_input = k;
+        if (S.status != MG_CONVERGED && bad < 0) bad = k;
+    }
+    if (bad >= 0) return mg_report(h, M, "lsm_elastic_solve_many", rtol, nullptr, nullptr, bad_input >= 0 ? bad_input : bad);
+    M.last_iters = 0;
+    for (int k = 0; k < K; ++k) M.last_iters = std::max(M.last_iters, iters[k]);
+    MG_LAUNCH2(N, es_store_kernel, EsUMany, dim3(nb, 1, nz), MG_THREADS, st, L, o.F, (const double*)M.V.x, U);
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipStreamSynchronize(st));
+    return LSM_OK;
+}
+
+int lsm_elastic_energy_many(LsmElastic* s, int K, void* const* u, const double* w, void* e_out) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    EsUMany U;
+    EsW W;
+    memset(&W, 0, sizeof(W));
+    if (K < 1 || K > LSM_ELASTIC_MAXCOLS) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_energy_many: K must be 1 ... LSM_ELASTIC_MAXCOLS (8)");
+    if (!w || !e_out || !es_fields_many(s->o->N, K, u, U))
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_energy_many: the K·N distinct fields of u, w and e_out must be given");
+    for (int a = 0; a < K * s->o->N; ++a)
+        if (u[a] == e_out) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_energy_many: e_out must not be one of the inputs");
+    for (int k = 0; k < K; ++k) {
+        if (!std::isfinite(w[k])) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elastic_energy_many: the weights must be finite");
+        W.w[k] = w[k];
+    }
+    const EsLevel& L = s->o->lev[0];
+    MG_LAUNCH(s->o->N, es_energy_many_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, h->stream, L, s->o->F, U, K, W, e_out);
+    LSM_HIP(h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_energy_mutual(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* v0, const void* v1, const void* v2, void* e_out) {
+    if (!s) return LSM_ERR_INVALID;
+    EsU U, V;
+    if (!es_fields(s->o->N, u0, u1, u2, U) || !es_fields(s->o->N, v0, v1, v2, V) || !e_out)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_energy_mutual: the components of u, those of v and e_out must be given, distinct within u and within v");
+    for (int i = 0; i < s->o->N; ++i)
+        if (e_out == U.p[i] || e_out == V.p[i]) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_energy_mutual: e_out must not be one of the inputs");
+    const EsLevel& L = s->o->lev[0];
+    MG_LAUNCH(s->o->N, es_energy_mutual_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, s->o->F, U, V, e_out);
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 

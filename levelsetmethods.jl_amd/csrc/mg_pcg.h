@@ -9,6 +9,11 @@
 //   [z = M r, ρ' = r·z, β = ρ'/ρ]   the V-cycle, whose last sweep carries the dot product — or, for M = D⁻¹, part of K2
 //   K1  p' = z + β p,  q = A p',  σ = p'·q   → α = ρ/σ   (the operator's own kernels: how p is updated differs)
 //   K2  x += α p',  r −= α q,  r·r → converged?  (Jacobi: z = r/D, ρ' = r·z as well)
+// A batched solve (MANY = 1 on the kernels, mg_vcycle<1>) runs K ≤ MG_MAXCOLS right-hand sides of one operator in the same launches: the
+// column is blockIdx.z.  Every vector of a level is the single solve's layout repeated at the column stride comps·nn, every column has
+// its own MgState (tickets included) and its own 4·MG_MAXB partials, and the launch shape in x is the single solve's, so a column runs
+// the single solve's arithmetic in its order: the same bits.  A column that has left MG_RUN is skipped by its own workgroups.  With
+// MANY = 0 the kernels are the single solve's, token for token.
 // Reductions by wave.h's block_reduce_ordered: one partial per workgroup, the last workgroup to draw a ticket sums them in
 // workgroup order and updates the scalars; every kernel returns at once when the device status is set, the host enqueues
 // iterations in chunks and reads the status once per chunk.
@@ -46,6 +51,7 @@ namespace lsm {
 static const int MG_THREADS = 256;
 static const int MG_MAXB = 2048;
 static const int MG_NCOARSE = 16;
+static const int MG_MAXCOLS = 8;      // the columns of a batched solve (MANY, below)
 enum { MG_RUN = 0, MG_CONVERGED = 1, MG_MAXITER = 2, MG_BREAK_INPUT = -1, MG_BREAK_SIGMA = -2, MG_BREAK_RHO = -3 };
 
 struct MgState {
@@ -132,8 +138,14 @@ __device__ __forceinline__ void mg_rho_update(MgState& S, double rz) {
 }
 
 // K2 over the nt unknowns: x += α p, r −= α q, r·r → converged?; JAC: z = r/D, ρ' = r·z, β = ρ'/ρ
-template <int JAC>
+template <int JAC, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) mg_k2_kernel(const double* __restrict__ D, int nt, MgVec V, const double* __restrict__ p) {
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z, at = c * (size_t)nt;
+        V.x += at; V.r += at; V.q += at; V.z += at; p += at;
+        V.partial += c * (4 * MG_MAXB);
+        V.st += c;
+    }
     if (V.st->status != MG_RUN) return;
     const double alpha = V.st->alpha;
     double red[2] = {0.0, 0.0};
@@ -178,8 +190,13 @@ __device__ __forceinline__ double mg_coarsen_scale(int k) { return k == 1 ? 0.5 
 
 // ---- the V-cycle's kernels (any level)
 // first sweep from zero: x = ω r/D (NC: the components per node)
-template <int NC, class Level>
+template <int NC, class Level, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) mg_smooth0_kernel(Level L, const double* __restrict__ r, double* __restrict__ x, const MgState* st) {
+    if constexpr (MANY) {
+        const size_t at = (size_t)blockIdx.z * NC * L.nn;
+        r += at; x += at;
+        st += blockIdx.z;
+    }
     if (st->status != MG_RUN) return;
     const int nn = L.nn;
     MG_LOOP(id, nn) {
@@ -189,9 +206,15 @@ __global__ void __launch_bounds__(MG_THREADS) mg_smooth0_kernel(Level L, const d
 }
 // xn = x + ω (r − A x)/D; DOT (the cycle's last sweep on level 0): r·xn and the scalars.  (Here and below: a node whose only
 // component is fixed needs no row.)
-template <int N, int DOT, class Level>
+template <int N, int DOT, class Level, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) mg_smooth_kernel(Level L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ xn,
                                                                double* partial, MgState* st) {
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z, at = c * Level::comps(N) * L.nn;
+        r += at; x += at; xn += at;
+        partial += c * (4 * MG_MAXB);
+        st += c;
+    }
     if (st->status != MG_RUN) return;
     constexpr int NC = Level::comps(N);
     const int nn = L.nn;
@@ -225,9 +248,14 @@ __global__ void __launch_bounds__(MG_THREADS) mg_smooth_kernel(Level L, const do
     }
 }
 // the fine residual, zero on the fixed components, written once (into the level's free smoother buffer), then gathered
-template <int N, class Level>
+template <int N, class Level, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) mg_resid_kernel(Level L, const double* __restrict__ r, const double* __restrict__ x, double* __restrict__ res,
                                                               const MgState* st) {
+    if constexpr (MANY) {
+        const size_t at = (size_t)blockIdx.z * Level::comps(N) * L.nn;
+        r += at; x += at; res += at;
+        st += blockIdx.z;
+    }
     if (st->status != MG_RUN) return;
     constexpr int NC = Level::comps(N);
     const int nn = L.nn;
@@ -246,9 +274,15 @@ __global__ void __launch_bounds__(MG_THREADS) mg_resid_kernel(Level L, const dou
     }
 }
 // r_c = Pᵀ res / 2^k per component (blockIdx.y): a coarse node gathers from the fine nodes 2J + o, o ∈ {−1, 0, 1} per coarsened axis
-template <int N, class Level>
+template <int N, class Level, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) mg_gather_kernel(Level Lf, Level Lc, int co0, int co1, int co2, const double* __restrict__ res,
                                                                double* __restrict__ rc, const MgState* st) {
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z;
+        res += c * Level::comps(N) * Lf.nn;
+        rc += c * Level::comps(N) * Lc.nn;
+        st += c;
+    }
     if (st->status != MG_RUN) return;
     const int co[3] = {co0, co1, co2};
     const double scale = mg_coarsen_scale(co0 + co1 + co2);
@@ -283,9 +317,15 @@ __global__ void __launch_bounds__(MG_THREADS) mg_gather_kernel(Level Lf, Level L
     }
 }
 // x += P x_c on the free fine components, per component (blockIdx.y)
-template <int N, class Level>
+template <int N, class Level, int MANY = 0>
 __global__ void __launch_bounds__(MG_THREADS) mg_prolong_kernel(Level Lf, Level Lc, int co0, int co1, int co2, const double* __restrict__ xc,
                                                                 double* __restrict__ x, const MgState* st) {
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z;
+        xc += c * Level::comps(N) * Lc.nn;
+        x += c * Level::comps(N) * Lf.nn;
+        st += c;
+    }
     if (st->status != MG_RUN) return;
     const int co[3] = {co0, co1, co2};
     const int comp = blockIdx.y;
@@ -423,11 +463,16 @@ __global__ void __launch_bounds__(MG_THREADS) mg_wrap_prolong_kernel(Level Lf, L
     }
 }
 // the coarsest level (≤ 128 nodes): MG_NCOARSE sweeps from zero in one workgroup, x in LDS (component stride 128), double-buffered
-template <int N, int DOT, class Level>
+template <int N, int DOT, class Level, int MANY = 0>
 __global__ void __launch_bounds__(128) mg_coarsest_kernel(Level L, const double* __restrict__ r, double* __restrict__ x, MgState* st) {
     constexpr int NC = Level::comps(N);
     __shared__ double xs[2][NC * 128];
     __shared__ double red[2];
+    if constexpr (MANY) {      // one workgroup per column
+        const size_t at = (size_t)blockIdx.z * NC * L.nn;
+        r += at; x += at;
+        st += blockIdx.z;
+    }
     if (st->status != MG_RUN) return;
     const int id = threadIdx.x, nn = L.nn;
     const bool node = id < nn;
@@ -483,10 +528,12 @@ static unsigned mg_blocks(long long n) { return (unsigned)std::min<long long>((n
 #define MG_LAUNCH(N, kernel, ...) MG_LAUNCH_AS(N, kernel<2>, kernel<3>, __VA_ARGS__)
 #define MG_LAUNCH2(N, kernel, A, ...) MG_LAUNCH_AS(N, (kernel<2, A>), (kernel<3, A>), __VA_ARGS__)
 #define MG_LAUNCH3(N, kernel, A, B, ...) MG_LAUNCH_AS(N, (kernel<2, A, B>), (kernel<3, A, B>), __VA_ARGS__)
+#define MG_LAUNCH4(N, kernel, A, B, C, ...) MG_LAUNCH_AS(N, (kernel<2, A, B, C>), (kernel<3, A, B, C>), __VA_ARGS__)
 
 template <class Level>
 struct MgSolver {
     int N = 0, precond = 0, last_iters = 0;
+    int cols = 1;                        // the columns that the vectors, the states and the partials are allocated for (a batch workspace: > 1 possible)
     int co[32][3];                       // co[l]: the axes that coarsen from level l to l+1
     std::vector<Level> lev;
     std::vector<double*> rhs, xa, xb;    // per level ≥ 1: right-hand side and the two smoother buffers; level 0: xa, xb only
@@ -569,22 +616,26 @@ struct mg_wraps : std::false_type {};
 template <class Level>
 struct mg_wraps<Level, std::void_t<decltype(Level::wraps)>> : std::true_type {};
 
-// z = M r0 for M = one V-cycle, into xb[0]; the last kernel leaves ρ and β
-template <class Level>
-static void mg_vcycle(MgSolver<Level>& o, const double* r0, hipStream_t s) {
+// z = M r0 for M = one V-cycle, into xb[0]; the last kernel leaves ρ and β.  MANY: the same for the first `cols` columns of a batch
+// workspace (a Level that takes part has launch_resid_many); the launches are the single cycle's with the columns as the grid's z
+template <int MANY = 0, class Level>
+static void mg_vcycle(MgSolver<Level>& o, const double* r0, hipStream_t s, int cols = 1) {
+    static_assert(!MANY || !mg_wraps<Level>::value, "the wrapping transfers have no column dimension");
     const int N = o.N, nl = (int)o.lev.size(), nc = Level::comps(N);
+    const unsigned nz = (unsigned)cols;
     MgState* st = o.st;
     for (int l = 0; l + 1 < nl; ++l) {
         const Level& L = o.lev[l];
         const double* r = l == 0 ? r0 : o.rhs[l];
         const unsigned nb = mg_blocks(L.nn);
-        MG_LAUNCH_AS(N, (mg_smooth0_kernel<Level::comps(2), Level>), (mg_smooth0_kernel<Level::comps(3), Level>), nb, MG_THREADS, s, L, r, o.xa[l],
+        MG_LAUNCH_AS(N, (mg_smooth0_kernel<Level::comps(2), Level, MANY>), (mg_smooth0_kernel<Level::comps(3), Level, MANY>), dim3(nb, 1, nz), MG_THREADS, s, L, r, o.xa[l],
                      (const MgState*)st);
-        MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
-        Level::launch_resid(N, nb, s, L, r, o.xb[l], o.xa[l], st);      // xa is free until the post-smoothing
+        MG_LAUNCH4(N, mg_smooth_kernel, 0, Level, MANY, dim3(nb, 1, nz), MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
+        if constexpr (MANY) Level::launch_resid_many(N, nb, nz, s, L, r, o.xb[l], o.xa[l], st);
+        else Level::launch_resid(N, nb, s, L, r, o.xb[l], o.xa[l], st);      // xa is free until the post-smoothing
         if constexpr (mg_wraps<Level>::value) Level::launch_gather(N, s, L, o.lev[l + 1], o.co[l], (const double*)o.xa[l], o.rhs[l + 1], (const MgState*)st);
         else
-            MG_LAUNCH2(N, mg_gather_kernel, Level, dim3(mg_blocks(o.lev[l + 1].nn), nc), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2],
+            MG_LAUNCH3(N, mg_gather_kernel, Level, MANY, dim3(mg_blocks(o.lev[l + 1].nn), nc, nz), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2],
                        (const double*)o.xa[l], o.rhs[l + 1], (const MgState*)st);
     }
     {
@@ -596,16 +647,16 @@ static void mg_vcycle(MgSolver<Level>& o, const double* r0, hipStream_t s) {
             // are created): the same MG_NCOARSE sweeps, the same arithmetic, as launches of the smoother; the last one lands in xb
             static_assert(MG_NCOARSE % 2 == 0, "the sweeps alternate xa, xb and end in xb");
             const unsigned nb = mg_blocks(L.nn);
-            MG_LAUNCH_AS(N, (mg_smooth0_kernel<Level::comps(2), Level>), (mg_smooth0_kernel<Level::comps(3), Level>), nb, MG_THREADS, s, L, r, o.xa[l],
+            MG_LAUNCH_AS(N, (mg_smooth0_kernel<Level::comps(2), Level, MANY>), (mg_smooth0_kernel<Level::comps(3), Level, MANY>), dim3(nb, 1, nz), MG_THREADS, s, L, r, o.xa[l],
                          (const MgState*)st);
             for (int k = 1; k < MG_NCOARSE; ++k) {
                 const double* from = (k & 1) ? o.xa[l] : o.xb[l];
                 double* to = (k & 1) ? o.xb[l] : o.xa[l];
-                if (l == 0 && k == MG_NCOARSE - 1) MG_LAUNCH3(N, mg_smooth_kernel, 1, Level, nb, MG_THREADS, s, L, r, from, to, o.partial.p, st);
-                else MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, from, to, o.partial.p, st);
+                if (l == 0 && k == MG_NCOARSE - 1) MG_LAUNCH4(N, mg_smooth_kernel, 1, Level, MANY, dim3(nb, 1, nz), MG_THREADS, s, L, r, from, to, o.partial.p, st);
+                else MG_LAUNCH4(N, mg_smooth_kernel, 0, Level, MANY, dim3(nb, 1, nz), MG_THREADS, s, L, r, from, to, o.partial.p, st);
             }
-        } else if (l == 0) MG_LAUNCH3(N, mg_coarsest_kernel, 1, Level, 1, 128, s, L, r, o.xb[l], st);
-        else MG_LAUNCH3(N, mg_coarsest_kernel, 0, Level, 1, 128, s, L, r, o.xb[l], st);
+        } else if (l == 0) MG_LAUNCH4(N, mg_coarsest_kernel, 1, Level, MANY, dim3(1, 1, nz), 128, s, L, r, o.xb[l], st);
+        else MG_LAUNCH4(N, mg_coarsest_kernel, 0, Level, MANY, dim3(1, 1, nz), 128, s, L, r, o.xb[l], st);
     }
     for (int l = nl - 2; l >= 0; --l) {
         const Level& L = o.lev[l];
@@ -613,53 +664,62 @@ static void mg_vcycle(MgSolver<Level>& o, const double* r0, hipStream_t s) {
         const unsigned nb = mg_blocks(L.nn);
         if constexpr (mg_wraps<Level>::value) Level::launch_prolong(N, s, L, o.lev[l + 1], o.co[l], (const double*)o.xb[l + 1], o.xb[l], (const MgState*)st);
         else
-            MG_LAUNCH2(N, mg_prolong_kernel, Level, dim3(nb, nc), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2], (const double*)o.xb[l + 1],
+            MG_LAUNCH3(N, mg_prolong_kernel, Level, MANY, dim3(nb, nc, nz), MG_THREADS, s, L, o.lev[l + 1], o.co[l][0], o.co[l][1], o.co[l][2], (const double*)o.xb[l + 1],
                        o.xb[l], (const MgState*)st);
-        MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], o.partial.p, st);
-        if (l == 0) MG_LAUNCH3(N, mg_smooth_kernel, 1, Level, nb, MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
-        else MG_LAUNCH3(N, mg_smooth_kernel, 0, Level, nb, MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
+        MG_LAUNCH4(N, mg_smooth_kernel, 0, Level, MANY, dim3(nb, 1, nz), MG_THREADS, s, L, r, (const double*)o.xb[l], o.xa[l], o.partial.p, st);
+        if (l == 0) MG_LAUNCH4(N, mg_smooth_kernel, 1, Level, MANY, dim3(nb, 1, nz), MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
+        else MG_LAUNCH4(N, mg_smooth_kernel, 0, Level, MANY, dim3(nb, 1, nz), MG_THREADS, s, L, r, (const double*)o.xa[l], o.xb[l], o.partial.p, st);
     }
 }
 
-// the device state of a new solve
+// the device state of a new solve (of its first `cols` columns)
 template <class Level>
-static int mg_reset(LsmHandle* h, MgSolver<Level>& o, double rtol, int max_iters, hipStream_t st) {
-    MgState s0;
-    memset(&s0, 0, sizeof(s0));
-    s0.rtol2 = rtol * rtol;
-    s0.max_iters = max_iters;
-    LSM_HIP(h, hipMemcpyAsync(o.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+static int mg_reset(LsmHandle* h, MgSolver<Level>& o, double rtol, int max_iters, hipStream_t st, int cols = 1) {
+    MgState s0[MG_MAXCOLS];
+    memset(s0, 0, sizeof(s0));
+    for (int c = 0; c < cols; ++c) {
+        s0[c].rtol2 = rtol * rtol;
+        s0[c].max_iters = max_iters;
+    }
+    LSM_HIP(h, hipMemcpyAsync(o.st, s0, cols * sizeof(MgState), hipMemcpyHostToDevice, st));
     return LSM_OK;
 }
 
 // iterations in chunks: the first as long as the last solve took, then doubling up to 64; one status read per chunk.
-// enqueue(k) enqueues iteration k; the state is left in o.h_st
+// enqueue(k) enqueues iteration k; the states of the `cols` columns are left in o.h_st, and the loop ends when none of them is running
 template <class Level, class Enqueue>
-static int mg_iterate(LsmHandle* h, MgSolver<Level>& o, int max_iters, hipStream_t st, Enqueue enqueue) {
+static int mg_iterate(LsmHandle* h, MgSolver<Level>& o, int max_iters, hipStream_t st, Enqueue enqueue, int cols = 1) {
     int enq = 0;
     int chunk = std::max(4, o.last_iters + 1);
     for (;;) {
         const int k = std::min(chunk, max_iters - enq);
         for (int it = 0; it < k; ++it, ++enq) enqueue(enq);
         LSM_HIP(h, hipGetLastError());
-        LSM_HIP(h, hipMemcpyAsync(o.h_st, o.st, sizeof(MgState), hipMemcpyDeviceToHost, st));
+        LSM_HIP(h, hipMemcpyAsync(o.h_st, o.st, cols * sizeof(MgState), hipMemcpyDeviceToHost, st));
         LSM_HIP(h, hipStreamSynchronize(st));
-        if (o.h_st.p->status != MG_RUN || enq >= max_iters) break;
+        bool running = false;
+        for (int c = 0; c < cols; ++c) running = running || o.h_st.p[c].status == MG_RUN;
+        if (!running || enq >= max_iters) break;
         chunk = std::min(2 * chunk, 64);
     }
     return LSM_OK;
 }
 
-// what the solve came to, from o.h_st: the iterations, the relative residual, and LSM_OK only when it converged (fn: the caller's name)
+static double mg_relres(const MgState& S) { return S.bb > 0 ? std::sqrt(S.rr / S.bb) : (S.rr == 0 ? 0.0 : std::sqrt(S.rr)); }
+
+// what the solve came to, from o.h_st: the iterations, the relative residual, and LSM_OK only when it converged (fn: the caller's name).
+// col ≥ 0: of that column of a batched solve, which the message then names
 template <class Level>
-static int mg_report(LsmHandle* h, MgSolver<Level>& o, const char* fn, double rtol, int* iters_out, double* relres_out) {
-    const MgState S = *o.h_st;
-    const double rel = S.bb > 0 ? std::sqrt(S.rr / S.bb) : (S.rr == 0 ? 0.0 : std::sqrt(S.rr));
+static int mg_report(LsmHandle* h, MgSolver<Level>& o, const char* fn, double rtol, int* iters_out, double* relres_out, int col = -1) {
+    const MgState S = o.h_st.p[col < 0 ? 0 : col];
+    const double rel = mg_relres(S);
+    char who[24] = "";
+    if (col >= 0) snprintf(who, sizeof(who), " column %d:", col);
     if (iters_out) *iters_out = S.iters;
     if (relres_out) *relres_out = rel;
     if (S.status == MG_BREAK_INPUT) {
         char msg[200];
-        snprintf(msg, sizeof(msg), "%s: f and u must be finite (%llu entries are not); u is unchanged", fn, S.nonfinite);
+        snprintf(msg, sizeof(msg), "%s:%s f and u must be finite (%llu entries are not); u is unchanged", fn, who, S.nonfinite);
         return lsm_fail(h, LSM_ERR_INVALID, msg);
     }
     if (S.status != MG_CONVERGED) {
@@ -667,10 +727,10 @@ static int mg_report(LsmHandle* h, MgSolver<Level>& o, const char* fn, double rt
         const char* why = S.status == MG_MAXITER || S.status == MG_RUN ? "no convergence within max_iters"
                           : S.status == MG_BREAK_SIGMA ? "PCG breakdown (p·Ap not positive)"
                                                        : "PCG breakdown (r·Mr not positive, or a non-finite residual)";
-        snprintf(msg, sizeof(msg), "%s: %s: %d iterations, relative residual %.3e (rtol %.3e); u is unchanged", fn, why, S.iters, rel, rtol);
+        snprintf(msg, sizeof(msg), "%s:%s %s: %d iterations, relative residual %.3e (rtol %.3e); u is unchanged", fn, who, why, S.iters, rel, rtol);
         return lsm_fail(h, LSM_ERR_NOT_CONVERGED, msg);
     }
-    o.last_iters = S.iters;
+    o.last_iters = col < 0 ? S.iters : std::max(o.last_iters, S.iters);
     return LSM_OK;
 }
 
