@@ -869,6 +869,46 @@ int lsm_elastic_modes_store(LsmModes* md, int k, void* u0, void* u1, void* u2);
 int lsm_elastic_modes_sensitivity(LsmModes* md, int k, void* g_out);
 void lsm_elastic_modes_destroy(LsmModes* md);
 
+/* ---- elliptic_modes: the m smallest eigenpairs of A x = lambda·M x for the scalar operator of an LsmElliptic — the resonances of a
+ *      cavity, the tones of a membrane, the principal eigenvalue of a diffusion problem — by the LOBPCG of "elasticity_modes" above
+ *      with one component per node: the same core (csrc/lobpcg.h), the same iteration, steps 1 … 5, the same Rayleigh–Ritz, stop test,
+ *      returns and stats (csrc/lsm_elliptic.hip; tests/_emodes_ref.py restates it).  What differs:
+ *      A is lsm_elliptic_apply's operator, its c term included, scaled by 1/prod h as it is, with the fixed nodes eliminated: they are
+ *      zero in every mode.  A must be positive definite; lsm_elliptic_create refuses "no fixed node and c = 0", so a cavity with natural
+ *      walls only needs c > 0.  With a constant c and rho == 1 the spectrum is that of c = 0 shifted by exactly c (M_I is then
+ *      the node mass m_I of "elliptic_solve", bit for bit); in general the pencil is (K + c·m, M).  An exact spectral shift is not
+ *      offered.
+ *      Mass: M_I = (sum of rho_C over the existing cells around I, ascending, from +0)·2^−N, rho_C as for elasticity_modes (the cell
+ *      formula with (rho_in, rho_out), or rho_cells).  rho_out/rho_in must stay far below a_out/a_in.
+ *      Vectors: a block has m columns of nn fp64, column-major; the object holds 6·m·nn doubles plus the node mass and the cell
+ *      densities.  Start: x0 (device, m·nn doubles), or NULL: entry t = k·nn + id takes the splitmix64 value of elasticity_modes.
+ *      The fixed nodes are set to zero either way.
+ *      The preconditioner is one V-cycle of the LsmElliptic per unconverged column, or 1/D for LSM_PRECOND_JACOBI.
+ *      lsm_elliptic_modes_apply: y_k = A x_k for ncols (1 … 8, else LSM_ERR_INVALID) columns of nn doubles on the device, x zero on
+ *      the fixed nodes: the rows of fixed nodes are zero, fixed neighbours count as zero, and every column has the bits of
+ *      lsm_elliptic_apply's arithmetic in its order.  It is the solve's block apply, exported so that tests can see it.
+ *      LSM_ERR_INVALID as for elasticity_modes with "free nodes" for "free components" (3·m above the free nodes).
+ *      lsm_elliptic_modes_store: mode k into one dense field: X_k·(prod h)^−1/2 rounded once to the storage type, so that
+ *      prod h·sum M·u² = 1; exact zeros on the fixed nodes; ghosts untouched.  The sign of a mode is not specified.
+ *      lsm_elliptic_modes_sensitivity: g_I = e_I − (lambda_k·rhobar_I)·(u_I·u_I) into a dense field, rounded once: u the stored mode
+ *      (rounded to the storage type), e_I lsm_elliptic_energy's value of u in fp64 before its rounding, rhobar_I = (sum of rho_C over
+ *      the existing cells around I, ascending from +0)/(their number).  c does not move with the shape and gives no term.  For a
+ *      membrane whose outside nodes are fixed the shape derivative is a boundary flux, not this integrand.
+ *      The modes object borrows the LsmElliptic, which must outlive it, and uses its scratch vectors and its state: a solve of either
+ *      must not run concurrently with the other, and lsm_elliptic_solve's results are bit-identical with or without a modes solve in
+ *      between. */
+typedef struct LsmEllipticModes LsmEllipticModes;
+int lsm_elliptic_modes_create(LsmElliptic* s, const void* phi, double level, double rho_in, double rho_out, const double* rho_cells, int m,
+                              LsmEllipticModes** out);
+int lsm_elliptic_modes_mass(LsmEllipticModes* md, double* node_mass);
+int lsm_elliptic_modes_apply(LsmEllipticModes* md, int ncols, const double* x, double* y);
+int lsm_elliptic_modes_solve(LsmEllipticModes* md, const double* x0, double rtol, int max_iters, double* lambda, double* relres, int* iters,
+                             int64_t stats[4]);
+int lsm_elliptic_modes_vectors(LsmEllipticModes* md, double* x_out);
+int lsm_elliptic_modes_store(LsmEllipticModes* md, int k, void* u);
+int lsm_elliptic_modes_sensitivity(LsmEllipticModes* md, int k, void* g_out);
+void lsm_elliptic_modes_destroy(LsmEllipticModes* md);
+
 /* ---- stress recovery: the cell-mean strain and stress of a displacement u on an LsmElastic, the von Mises field, the p-norm
  *      aggregate of the von Mises stress with its adjoint load and its sensitivity to the cell moduli — the stress objective of a
  *      structural shape optimisation (csrc/lsm_elastic.hip; tests/_stress_ref.py restates every operation).  u0,

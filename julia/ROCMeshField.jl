@@ -840,6 +840,41 @@ modes_sensitivity!(g::ROCMeshField, M, k) =
 
 destroy_modes(M) = ccall((:lsm_elastic_modes_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), M.md)
 
+# elliptic_modes: the m ≤ 8 lowest eigenmodes A u = λ M u of an elliptic_operator A, its c term included (include/lsm.h,
+# lsm_elliptic_modes_*): cavity resonances, membrane tones, the principal eigenvalue.  The density of a cell is
+# rho_out + (rho_in − rho_out)·θ(ϕ), or `rho` (a ROCArray{Float64} of size n .- 1, required when A was built from `a`).  The object
+# borrows A, which must outlive it; release it with destroy_elliptic_modes.
+function elliptic_modes(A, ϕ::ROCMeshField, m; level = 0.0, rho_in = 1.0, rho_out = 1e-6, rho = nothing)
+    out = Ref{Ptr{Cvoid}}()
+    _check(A.h.ptr, ccall((:lsm_elliptic_modes_create, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+        A.op, rho === nothing ? pointer(ϕ.buf) : C_NULL, level, rho_in, rho_out, rho === nothing ? C_NULL : pointer(rho), m, out), "lsm_elliptic_modes_create")
+    return (; md = out[], h = A.h, m = m)
+end
+
+# elliptic_modes_solve!: LOBPCG from x0 (a ROCArray{Float64} of m·nn values, or nothing: the fixed pseudo-random start) until every
+# mode's relative residual is below rtol.  Returns (eigenvalues, relres, iterations); LSM_ERR_NOT_CONVERGED throws, the last iterate stays.
+function elliptic_modes_solve!(M; x0 = nothing, rtol = 1e-6, max_iters = 300)
+    lam, rel, iters, stats = zeros(Float64, M.m), zeros(Float64, M.m), Ref{Cint}(0), zeros(Int64, 4)
+    _check(M.h.ptr, ccall((:lsm_elliptic_modes_solve, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64, Cint, Ptr{Float64}, Ptr{Float64}, Ref{Cint}, Ptr{Int64}),
+        M.md, x0 === nothing ? C_NULL : pointer(x0), rtol, max_iters, lam, rel, iters, stats), "lsm_elliptic_modes_solve")
+    return (; eigenvalues = lam, relres = rel, iterations = iters[])
+end
+
+# the node mass into a ROCArray{Float64} of the grid's size; X into one of m·nn values (the next design's x0); y = A x for ncols ≤ 8
+# columns of nn values, x zero on the fixed nodes (the solve's block apply)
+elliptic_modes_mass!(a, M) = _check(M.h.ptr, ccall((:lsm_elliptic_modes_mass, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.md, pointer(a)), "lsm_elliptic_modes_mass")
+elliptic_modes_vectors!(x, M) = _check(M.h.ptr, ccall((:lsm_elliptic_modes_vectors, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.md, pointer(x)), "lsm_elliptic_modes_vectors")
+elliptic_modes_apply!(y, M, x, ncols) =
+    _check(M.h.ptr, ccall((:lsm_elliptic_modes_apply, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}), M.md, ncols, pointer(x), pointer(y)), "lsm_elliptic_modes_apply")
+
+# mode k (0-based, as in C) into the field u, normalised to ∫ρu² = 1; its shape-derivative integrand into the field g
+elliptic_modes_store!(u::ROCMeshField, M, k) =
+    _check(M.h.ptr, ccall((:lsm_elliptic_modes_store, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), M.md, k, pointer(u.buf)), "lsm_elliptic_modes_store")
+elliptic_modes_sensitivity!(g::ROCMeshField, M, k) =
+    _check(M.h.ptr, ccall((:lsm_elliptic_modes_sensitivity, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), M.md, k, pointer(g.buf)), "lsm_elliptic_modes_sensitivity")
+
+destroy_elliptic_modes(M) = ccall((:lsm_elliptic_modes_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), M.md)
+
 # Stress recovery of a displacement u (N fields; any displacement, not only a solution) on an elasticity_operator K (include/lsm.h,
 # lsm_elastic_stress_*).  `what`: 0 the strain, 1 the stress (both N(N+1)/2 components in Voigt order: 2-D (00, 11, 01), 3-D (00, 11,
 # 22, 12, 02, 01)), 2 the von Mises stress (one component).

@@ -211,6 +211,15 @@ _SIGS = [
     ("lsm_elastic_modes_store", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_elastic_modes_sensitivity", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     ("lsm_elastic_modes_destroy", None, [C.c_void_p]),
+    ("lsm_elliptic_modes_create", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("lsm_elliptic_modes_mass", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_modes_apply", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_modes_solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int64)]),
+    ("lsm_elliptic_modes_vectors", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_modes_store", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_elliptic_modes_sensitivity", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("lsm_elliptic_modes_destroy", None, [C.c_void_p]),
     ("lsm_elastic_stress_cells", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     ("lsm_elastic_stress", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),

@@ -2727,6 +2727,7 @@ class EllipticOperator:
             raise ValueError(f"{what}: c has shape {c_host.shape}, the grid has {n} nodes")
         b = self.backend = phi.backend
         self.mesh, self.bcs, self.precond = phi.mesh, phi.bcs, precond
+        self._phi, self._level = (None if a is not None else phi), float(level)      # the density of modes() is read from the same ϕ
         t = b.torch
         a_dev = None if a is None else b.node_array(a if a_host is None else a_host, "a", cells)
         c_dev = None
@@ -2802,6 +2803,10 @@ class EllipticOperator:
         """the level-0 cell coefficients, a host array of shape n − 1"""
         n = tuple(int(m) - 1 for m in self.mesh.n)
         return self.backend.elliptic_cells(self._handle()).cpu().numpy().reshape(n, order="F")
+
+    def modes(self, m, *, rho_in=1.0, rho_out=1e-6, rho=None, x0=None, rtol=1e-6, max_iters=300):
+        """the m smallest eigenpairs of A u = λ M u for this operator (the fixed nodes zero): an EllipticModes.  See elliptic_modes."""
+        return EllipticModes(self, m, rho_in=rho_in, rho_out=rho_out, rho=rho, x0=x0, rtol=rtol, max_iters=max_iters)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -3678,9 +3683,9 @@ def homogenize_conductivity(phi_or_eq, *, a_in=1.0, a_out=1e-3, a=None, level=0.
 
 # ----------------------------------------------------------------------------- vibration modes (the eigenfrequency objective of a structural optimisation)
 
-def _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, from_phi):
-    """elasticity_modes' refusals that need neither a field nor a device; returns ρ as a host array, a device tensor or None"""
-    what = "elasticity_modes"
+def _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, from_phi, what="elasticity_modes", cells="cell moduli `E`"):
+    """the refusals of elasticity_modes (or of `what`) that need neither a field nor a device; returns ρ as a host array, a device tensor
+    or None"""
     if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
         raise TypeError(f"{what}: m must be an integer, not {type(m).__name__}")
     if not 1 <= int(m) <= 8:
@@ -3690,7 +3695,7 @@ def _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, from_phi):
         raise ValueError(f"{what}: rtol must be positive and finite, max_iters at least 1")
     if rho is None:
         if not from_phi:
-            raise ValueError(f"{what}: the operator was built from cell moduli `E`, not from ϕ: give the cell densities `rho`")
+            raise ValueError(f"{what}: the operator was built from {cells}, not from ϕ: give the cell densities `rho`")
         if not (_finite_positive(float(rho_in)) and _finite_positive(float(rho_out))):
             raise ValueError(f"{what}: rho_in and rho_out must be finite and positive")
         return None
@@ -3832,6 +3837,153 @@ def elasticity_modes(phi_or_eq, m, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plan
     which carries `eigenvalues`, `relres`, `iterations` and `modes`, when max_iters does not suffice."""
     rho = _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, E is None)
     op = ElasticityOperator(phi_or_eq, E_in=E_in, E_out=E_out, E=E, nu=nu, plane=plane, dirichlet=dirichlet, level=level, precond=precond)
+    try:
+        return op.modes(m, rho_in=rho_in, rho_out=rho_out, rho=rho, x0=x0, rtol=rtol, max_iters=max_iters)
+    except BaseException as e:
+        if not isinstance(e, L.LsmNotConvergedError):     # the partial results of a failed solve still need their operator
+            op.close()
+        raise
+
+
+# ----------------------------------------------------------------------------- scalar eigenmodes (cavities, membranes, the λ₁ objective)
+
+class EllipticModes:
+    """elliptic_modes' result: `eigenvalues` (λ_k, ascending), `frequencies` (√λ/2π), `iterations` (block iterations), `relres` (per
+    mode, the recursive ‖A x − λ M x‖₂/(λ‖M x‖₂)), `stats` (iterations, preconditioner applications, directions dropped, unconverged
+    columns), `operator`; mode(k) → one ROCMeshField normalised to ∫ρu² = 1, exact zeros on the fixed nodes, the sign unspecified;
+    sensitivity(k) → the ROCMeshField g = e − λ_k·ρ̄·u², e the energy density a|∇u|² of the mode: the integrand of dλ_k/dΩ that a
+    NormalMotionTerm takes as its speed (c does not move with the shape and gives no term; for a membrane whose outside nodes are
+    fixed the derivative is a boundary flux, not this field); vectors() → a host array (m,) + n, the next design's `x0`; mass() → the
+    lumped node mass, n-shaped; solve(x0=None, rtol=…, max_iters=…) runs again; close() releases the device memory.  The object
+    borrows its operator: after operator.close() every use is a ValueError."""
+
+    def __init__(self, op, m, *, rho_in=1.0, rho_out=1e-6, rho=None, x0=None, rtol=1e-6, max_iters=300):
+        self._h = None
+        rho = _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, getattr(op, "_phi", None) is not None, "elliptic_modes", "cell coefficients `a`")
+        self.operator, self.m = op, int(m)
+        b = self.backend = op.backend
+        n = tuple(int(k) for k in op.mesh.n)
+        if 3 * self.m > op.free_nodes:
+            raise ValueError(f"elliptic_modes: 3·m = {3 * self.m} exceeds the {op.free_nodes} free nodes")
+        cells = tuple(k - 1 for k in n)
+        if rho is not None and not hasattr(rho, "is_cuda") and rho.ndim and rho.shape != cells:
+            raise ValueError(f"elliptic_modes: `rho` has shape {rho.shape}, the grid has {cells} cells")
+        rho_dev = None if rho is None else b.node_array(rho, "rho", cells)
+        try:
+            self._h = b.emodes_create(op._handle(), None if rho is not None else op._phi.buf, op._level, rho_in, rho_out, rho_dev, self.m)
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                raise ValueError("elliptic_modes: " + str(e).split(": ", 2)[-1]) from None
+            raise
+        self.eigenvalues = self.relres = None
+        self.iterations = 0
+        self.solve(x0=x0, rtol=rtol, max_iters=max_iters)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the EllipticModes object is closed")
+        self.operator._handle()     # ValueError once the operator is closed: the modes object borrows it
+        return self._h
+
+    def solve(self, x0=None, rtol=1e-6, max_iters=300):
+        h = self._handle()
+        b, op, m = self.backend, self.operator, self.m
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("elliptic_modes: rtol must be positive and finite, max_iters at least 1")
+        n = tuple(int(k) for k in op.mesh.n)
+        xd = None
+        if x0 is not None:
+            if b.torch.is_tensor(x0):
+                xd = b.node_array(x0, "x0", (m,) + n)
+            else:
+                a = np.asarray(x0, dtype=np.float64)
+                if a.shape != (m,) + n:
+                    raise ValueError(f"elliptic_modes: x0 has shape {a.shape}, expected {(m,) + n}")
+                if not np.all(np.isfinite(a)):
+                    raise ValueError("elliptic_modes: x0 must be finite")
+                xd = b.torch.from_numpy(np.concatenate([a[k].reshape(-1, order="F") for k in range(m)])).to(b.device)
+        try:
+            code, lam, rel, it, stats = b.emodes_solve(h, m, xd, rtol, int(max_iters))
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                raise ValueError("elliptic_modes: x0 must be finite") from None
+            raise
+        self.eigenvalues, self.relres, self.iterations, self.stats = lam, rel, it, stats
+        if code != L.OK:
+            msg = b.lib.lsm_last_error(b.h)
+            err = L.LsmNotConvergedError(f"lsm_elliptic_modes_solve failed ({code}): {msg.decode() if msg else ''}")
+            err.eigenvalues, err.relres, err.iterations, err.modes = lam, rel, it, self
+            raise err
+        return self
+
+    @property
+    def frequencies(self):
+        return np.sqrt(self.eigenvalues) / (2.0 * math.pi)
+
+    def _k(self, k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"elliptic_modes: the mode index must be an integer, not {type(k).__name__}")
+        if not 0 <= int(k) < self.m:
+            raise ValueError(f"elliptic_modes: mode {k} of {self.m}")
+        return int(k)
+
+    def mode(self, k):
+        h, k, op = self._handle(), self._k(k), self.operator
+        u = ROCMeshField(self.backend, op.mesh, op.bcs)
+        self.backend.emodes_store(h, k, u.buf)
+        return u
+
+    def sensitivity(self, k):
+        h, k, op = self._handle(), self._k(k), self.operator
+        g = ROCMeshField(self.backend, op.mesh, op.bcs)
+        self.backend.emodes_sensitivity(h, k, g.buf)
+        return g
+
+    def vectors(self):
+        h, op, m = self._handle(), self.operator, self.m
+        n = tuple(int(k) for k in op.mesh.n)
+        nn = int(np.prod(n))
+        x = self.backend.emodes_vectors(h, m * nn).cpu().numpy()
+        return np.stack([x[k * nn:(k + 1) * nn].reshape(n, order="F") for k in range(m)])
+
+    def mass(self):
+        h = self._handle()
+        n = tuple(int(k) for k in self.operator.mesh.n)
+        return self.backend.emodes_mass(h).cpu().numpy().reshape(n, order="F")
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            try:
+                self.backend.emodes_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+
+def elliptic_modes(phi_or_eq, m, *, a_in=1.0, a_out=1e-3, a=None, c=0.0, dirichlet=None, level=0.0, precond="mg", rho_in=1.0, rho_out=1e-6, rho=None, x0=None,
+                   rtol=1e-6, max_iters=300):
+    """The m (1 … 8) lowest eigenmodes of −∇·(a∇u) + c·u = λ ρ u on the box of ϕ's grid: the smallest eigenpairs of A u = λ M u on the
+    device — the resonances of a cavity or the cut-off wavenumbers of a waveguide (natural walls, ersatz material in
+    the void), the tones of a membrane, the principal eigenvalue of a diffusion problem, the objective of a "maximise λ₁" shape
+    optimisation.  A is elliptic_solve's operator with its arguments (`a_in` … `precond`) and its c term; the nodes of `dirichlet` are
+    zero in every mode whatever values it prescribes.  A must be positive definite: a cavity with natural walls only needs c > 0.
+    With a constant c and ρ ≡ 1 the spectrum is that of c = 0 shifted by exactly c; in general the pencil is (K + c·m, M), and an exact
+    spectral shift is not offered.  M is a lumped mass: the density of a cell is rho_out + (rho_in − rho_out)·θ with the coefficient's
+    fill fraction θ, or `rho` (a scalar or an array of shape n − 1), which is required when `a` gave the coefficients.  Keep
+    rho_out/rho_in far below a_out/a_in (the defaults: 1e-6 against 1e-3): with equal densities the ersatz material is as heavy as
+    the domain and a thousand times softer, and the lowest "modes" are spurious ones that live in the void (a clamped two-hole plate
+    on 33×33: a first "mode" of 0.26 in the holes, against 2.09 with rho_out = 1e-6).  A membrane of shape {ϕ < 0} fixes the
+    nodes outside: dirichlet=(ϕ.values() >= 0, 0.0).  A locally optimal block preconditioned CG (LOBPCG) from `x0` (a host array
+    (m,) + n, such as the last design's vectors(); a fixed pseudo-random start without one) until ‖A x − λ M x‖₂ ≤ rtol·λ·‖M x‖₂ for
+    every mode.  Returns an EllipticModes, whose `operator` the caller closes.  Raises ValueError / TypeError for what is refused
+    (elliptic_solve's refusals, m outside 1 … 8, 3·m above the free nodes, densities not finite and positive, `a` without `rho`, a
+    non-finite x0) and LsmNotConvergedError, which carries `eigenvalues`, `relres`, `iterations` and `modes`, when max_iters does
+    not suffice."""
+    rho = _modes_args(m, rho_in, rho_out, rho, rtol, max_iters, a is None, "elliptic_modes", "cell coefficients `a`")
+    op = EllipticOperator(phi_or_eq, a_in=a_in, a_out=a_out, a=a, c=c, dirichlet=dirichlet, level=level, precond=precond)
     try:
         return op.modes(m, rho_in=rho_in, rho_out=rho_out, rho=rho, x0=x0, rtol=rtol, max_iters=max_iters)
     except BaseException as e:

@@ -818,6 +818,46 @@ class HipBackend:
     def modes_destroy(self, md):
         self.lib.lsm_elastic_modes_destroy(md)
 
+    # ---- scalar eigenmodes (lsm_elliptic_modes_*): the modes object borrows the elliptic object
+    def emodes_create(self, obj, phi, level, rho_in, rho_out, rho_cells, m):
+        out = C.c_void_p()
+        L.check(self.h, self.lib.lsm_elliptic_modes_create(obj, self.ptr(phi), float(level), float(rho_in), float(rho_out), self.ptr(rho_cells), int(m),
+                                                           C.byref(out)), "lsm_elliptic_modes_create")
+        return out
+
+    def emodes_mass(self, md):
+        out = self.torch.empty(int(np.prod(self.local_shape())), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elliptic_modes_mass(md, self.ptr(out)), "lsm_elliptic_modes_mass")
+        return out
+
+    def emodes_apply(self, md, ncols, x):
+        """the block apply: x holds ncols columns of nn float64 values, zero on the fixed nodes; returns A x, the fixed rows zero"""
+        y = self.torch.empty_like(x)
+        L.check(self.h, self.lib.lsm_elliptic_modes_apply(md, int(ncols), self.ptr(x), self.ptr(y)), "lsm_elliptic_modes_apply")
+        return y
+
+    def emodes_solve(self, md, m, x0, rtol, max_iters):
+        """returns (status, λ, relres, iterations, stats); status is OK or ERR_NOT_CONVERGED (whose message lsm_last_error keeps), anything else raises"""
+        lam, rel, it, stats = (C.c_double * m)(), (C.c_double * m)(), C.c_int(0), (C.c_int64 * 4)()
+        code = self.lib.lsm_elliptic_modes_solve(md, self.ptr(x0), float(rtol), int(max_iters), lam, rel, C.byref(it), stats)
+        if code != L.ERR_NOT_CONVERGED:
+            L.check(self.h, code, "lsm_elliptic_modes_solve")
+        return code, np.array(lam[:]), np.array(rel[:]), it.value, tuple(int(v) for v in stats)
+
+    def emodes_vectors(self, md, count):
+        out = self.torch.empty(int(count), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elliptic_modes_vectors(md, self.ptr(out)), "lsm_elliptic_modes_vectors")
+        return out
+
+    def emodes_store(self, md, k, u):
+        L.check(self.h, self.lib.lsm_elliptic_modes_store(md, int(k), self.ptr(u)), "lsm_elliptic_modes_store")
+
+    def emodes_sensitivity(self, md, k, g):
+        L.check(self.h, self.lib.lsm_elliptic_modes_sensitivity(md, int(k), self.ptr(g)), "lsm_elliptic_modes_sensitivity")
+
+    def emodes_destroy(self, md):
+        self.lib.lsm_elliptic_modes_destroy(md)
+
     # ---- pictures (lsm_render_*)
     def render_create(self, phi, mask, level):
         """the renderer of a field: builds the brick table; borrows phi and mask"""

@@ -13,6 +13,7 @@
 //   K1  p' = z + β p fused into the apply (p double-buffered: neighbours read the old one),  q = A p',  σ = p'·q   → α = ρ/σ
 //   a NULL mask (no fixed node) costs no read; a neighbour's mask byte is read instead of its value where it is fixed.
 #include "el_cell.h"
+#include "lobpcg.h"
 #include "mg_pcg.h"
 
 namespace lsm {
@@ -496,4 +497,209 @@ void lsm_elliptic_destroy(LsmElliptic* s) {
     if (!s) return;
     delete s->o;
     delete s;
+}
+
+// ======================================================================================================================================
+// elliptic_modes: the m ≤ 8 smallest eigenpairs of A x = λ M x on the free nodes — A the operator above with its c term, the fixed nodes
+// eliminated, M the lumped mass of an ersatz density — by lobpcg.h's LOBPCG, preconditioned by mg_vcycle (or 1/D).  include/lsm.h
+// ("elliptic_modes") is the normative text, tests/_emodes_ref.py restates it, DESIGN.md §7.26 has the compiler's report.
+//
+// The iteration, its block passes and the workspace are lobpcg.h's with one component per node.  This file's own: the block apply, which
+// loads a node's 2^N cells and forms its 2N edge coefficients once for all columns (in the scalar operator they are most of an apply's
+// work), the stored mode and the sensitivity.  Nothing above this line changes: the modes object borrows the LsmElliptic's hierarchy, its
+// xa / xb scratch, its MgState and its diagonal, and lsm_elliptic_solve resets the state it reads.
+namespace lsm {
+
+// ---- y_k = A x_k for ncols columns of nn doubles, the rows of fixed nodes zero, fixed neighbours read as zero.  A thread owns a node:
+// the cells, the edge coefficients, c·m and the neighbours' mask bytes once, then per column el_apply's arithmetic in its order
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) elm_apply_kernel(ElLevel L, int ncols, const double* __restrict__ x, double* __restrict__ y) {
+    const int cs[3] = {1, L.n[0], L.n[0] * L.n[1]};
+    const double half = N == 2 ? 0.5 : 0.25;
+    const size_t nn = (size_t)L.nn;
+    MG_LOOP(id, L.nn) {
+        if (L.fixed(id, 0)) {
+            for (int k = 0; k < ncols; ++k) y[k * nn + id] = 0.0;
+            continue;
+        }
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        double v[1 << N];
+        el_cells_around<N>(L, I, v);
+        double w[2 * N];
+        int q[2 * N];
+        bool edge[2 * N], rd[2 * N];      // the edge exists; its far node is free (its value is read)
+#pragma unroll
+        for (int d = 0; d < N; ++d)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int e = 2 * d + s;
+                edge[e] = s ? I[d] < L.n[d] - 1 : I[d] > 0;
+                q[e] = edge[e] ? (s ? id + cs[d] : id - cs[d]) : id;
+                rd[e] = edge[e] && !L.fixed(q[e], 0);
+                w[e] = (el_edge_sum<N>(v, d, s) * half) * L.ih2[d];
+            }
+        const double cm = el_cm<N>(L, id, I);
+        for (int k = 0; k < ncols; ++k) {
+            const double* __restrict__ xk = x + k * nn;
+            const double xi = xk[id];
+            double acc = 0.0;
+#pragma unroll
+            for (int e = 0; e < 2 * N; ++e) {
+                const double xn = rd[e] ? xk[q[e]] : 0.0;
+                if (edge[e]) acc = acc + w[e] * (xi - xn);
+            }
+            y[k * nn + id] = acc + cm * xi;
+        }
+    }
+}
+
+// ---- mode k into a field: x·scale rounded once to the storage type, exact zeros on the fixed nodes; the ghosts stay
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) elm_store_kernel(ElLevel L, MgField F, const double* __restrict__ x, double scale, void* __restrict__ u) {
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        st_val(u, mg_padded(F, I), F.f32, L.fixed(id, 0) ? 0.0 : x[id] * scale);
+    }
+}
+
+// ---- g_I = e_I − (λ·ρ̄_I)·(u_I·u_I), u = the stored mode (x·scale rounded to the storage type).  e_I is el_energy_kernel's, the same
+// operations in the same order on values read from x instead of a field; ρ̄_I = (Σ ρ_C over the existing cells, ascending from +0)/cells.
+// c does not move with the shape: it gives no term
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) elm_sens_kernel(ElLevel L, MgField F, const double* __restrict__ x, double scale, double lam,
+                                                              const double* __restrict__ rho, void* __restrict__ g_out) {
+    const int cs[3] = {1, L.n[0], L.n[0] * L.n[1]};
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        double v[1 << N];
+        el_cells_around<N>(L, I, v);
+        const double ui = em_round(x[id] * scale, F.f32);
+        double e = 0.0;
+#pragma unroll
+        for (int d = 0; d < N; ++d) {
+            double ncell = 1.0;
+#pragma unroll
+            for (int o = 0; o < N; ++o)
+                if (o != d && I[o] > 0 && I[o] < L.n[o] - 1) ncell = ncell * 2.0;
+            double s = 0.0, cnt = 0.0;
+            if (I[d] > 0) {
+                const double g = (em_round(x[id - cs[d]] * scale, F.f32) - ui) / L.h[d];
+                s = s + (el_edge_sum<N>(v, d, 0) / ncell) * (g * g);
+                cnt = cnt + 1.0;
+            }
+            if (I[d] < L.n[d] - 1) {
+                const double g = (em_round(x[id + cs[d]] * scale, F.f32) - ui) / L.h[d];
+                s = s + (el_edge_sum<N>(v, d, 1) / ncell) * (g * g);
+                cnt = cnt + 1.0;
+            }
+            e = e + s / cnt;
+        }
+        double rs = 0.0, nc = 0.0;
+#pragma unroll
+        for (int m = 0; m < (1 << N); ++m) {
+            bool in;
+            const double r = em_cell(L, rho, I, m, N, in);
+            if (in) {
+                rs = rs + r;
+                nc = nc + 1.0;
+            }
+        }
+        st_val(g_out, mg_padded(F, I), F.f32, e - (lam * (rs / nc)) * (ui * ui));
+    }
+}
+
+}  // namespace lsm
+
+struct LsmEllipticModes { LsmElliptic* e; ModesObject* o; };
+
+int lsm_elliptic_modes_create(LsmElliptic* s, const void* phi, double level, double rho_in, double rho_out, const double* rho_cells, int m, LsmEllipticModes** out) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    EllipticObject& eo = *s->o;
+    if (!out) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_create: null argument");
+    if (!phi && !rho_cells) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_create: give phi or the cell densities");
+    if (m < 1 || m > EM_MAXM) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_create: m must be between 1 and 8");
+    if (3LL * m > eo.nfree) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_create: 3·m exceeds the number of free nodes");
+    if (!rho_cells && (!(rho_in > 0) || !std::isfinite(rho_in) || !(rho_out > 0) || !std::isfinite(rho_out)))
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_create: rho_in and rho_out must be finite and positive");
+    if (!rho_cells && !std::isfinite(level)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_create: level must be finite");
+    (void)hipSetDevice(h->device);
+    std::unique_ptr<ModesObject> guard(new ModesObject());
+    const int r = em_create(h, eo, *guard, "lsm_elliptic_modes_create", phi, level, rho_in, rho_out, rho_cells, m);
+    if (r != LSM_OK) return r;
+    *out = new LsmEllipticModes{s, guard.release()};
+    return LSM_OK;
+}
+
+int lsm_elliptic_modes_mass(LsmEllipticModes* md, double* node_mass) {
+    if (!md) return LSM_ERR_INVALID;
+    LsmHandle* h = md->e->h;
+    if (!node_mass) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_mass: null argument");
+    LSM_HIP(h, hipMemcpyAsync(node_mass, md->o->Mn, (size_t)md->e->o->lev[0].nn * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return LSM_OK;
+}
+
+static void elm_apply(const EllipticObject& eo, int ncols, const double* x, double* y, hipStream_t st) {
+    const ElLevel& L = eo.lev[0];
+    MG_LAUNCH(eo.N, elm_apply_kernel, mg_blocks(L.nn), MG_THREADS, st, L, ncols, x, y);
+}
+
+int lsm_elliptic_modes_apply(LsmEllipticModes* md, int ncols, const double* x, double* y) {
+    if (!md) return LSM_ERR_INVALID;
+    LsmHandle* h = md->e->h;
+    if (!x || !y || x == y) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_apply: x and y must be two arrays");
+    if (ncols < 1 || ncols > EM_MAXM) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_apply: ncols must be between 1 and 8");
+    elm_apply(*md->e->o, ncols, x, y, h->stream);
+    LSM_HIP(h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elliptic_modes_solve(LsmEllipticModes* md, const double* x0, double rtol, int max_iters, double* lambda, double* relres, int* iters, int64_t stats[4]) {
+    if (!md) return LSM_ERR_INVALID;
+    EllipticObject& eo = *md->e->o;
+    return em_solve(md->e->h, eo, *md->o, "lsm_elliptic_modes_solve", [&](int na, const double* x, double* y, hipStream_t st) { elm_apply(eo, na, x, y, st); }, x0, rtol,
+                    max_iters, lambda, relres, iters, stats);
+}
+
+int lsm_elliptic_modes_vectors(LsmEllipticModes* md, double* x_out) {
+    if (!md) return LSM_ERR_INVALID;
+    LsmHandle* h = md->e->h;
+    if (!x_out || !md->o->solved) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_vectors: null argument, or no solve has run");
+    LSM_HIP(h, hipMemcpyAsync(x_out, md->o->B.base, (size_t)md->o->m * (size_t)md->o->nt * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return LSM_OK;
+}
+
+int lsm_elliptic_modes_store(LsmEllipticModes* md, int k, void* u) {
+    if (!md) return LSM_ERR_INVALID;
+    LsmHandle* h = md->e->h;
+    EllipticObject& eo = *md->e->o;
+    ModesObject& o = *md->o;
+    if (!o.solved || k < 0 || k >= o.m) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_store: no such mode, or no solve has run");
+    if (!u) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_store: null field");
+    const ElLevel& L = eo.lev[0];
+    MG_LAUNCH(eo.N, elm_store_kernel, mg_blocks(L.nn), MG_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), u);
+    LSM_HIP(h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elliptic_modes_sensitivity(LsmEllipticModes* md, int k, void* g_out) {
+    if (!md) return LSM_ERR_INVALID;
+    LsmHandle* h = md->e->h;
+    EllipticObject& eo = *md->e->o;
+    ModesObject& o = *md->o;
+    if (!o.solved || k < 0 || k >= o.m || !g_out) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_modes_sensitivity: no such mode, no solve has run, or a null field");
+    const ElLevel& L = eo.lev[0];
+    MG_LAUNCH(eo.N, elm_sens_kernel, mg_blocks(L.nn), MG_THREADS, h->stream, L, eo.F, (const double*)(o.B.base + (size_t)k * o.nt), em_scale(L, eo.N), o.lam[k],
+              (const double*)o.rho, g_out);
+    LSM_HIP(h, hipGetLastError());
+    return LSM_OK;
+}
+
+void lsm_elliptic_modes_destroy(LsmEllipticModes* md) {
+    if (!md) return;
+    delete md->o;
+    delete md;
 }
