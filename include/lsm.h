@@ -573,7 +573,30 @@ int lsm_nucleate_punch(LsmHandle* h, void* phi, const void* centres, int64_t cou
  *      / (number of existing edges along d at I), d ascending, into a dense field of the handle (rounded once).
  *      lsm_elliptic_compliance: *out := prod h · sum_I (m_I·f_I)·u_I, reduced on the device.
  *      lsm_elliptic_cells copies the level-0 cell array into a device buffer.  All but solve run on the handle's stream;
- *      solve, compliance and create are synchronous. */
+ *      solve, compliance and create are synchronous.
+ *      lsm_elliptic_solve_many: K sources of the one operator (1 <= K <= LSM_ELLIPTIC_MAXCOLS) solved in the same launches.
+ *      Column k of the batch is lsm_elliptic_solve of column k, bit for bit: the field, the iteration count and the relative
+ *      residual (every column has the single solve's launch shape, arithmetic and order, and its own device state).  f is
+ *      K·nn fp64 on the device, column k at k·nn; u[k] is the field of column k, K distinct dense fields of the handle holding
+ *      the guess and the Dirichlet values.  iters, relres and status are host arrays of K, filled for every column whatever
+ *      the outcome; status: 1 converged, 2 out of iterations, −1 non-finite input, −2 breakdown (p·Ap not positive), −3
+ *      breakdown (r·Mr not positive, or a non-finite residual).  A column that has ended is skipped by its own workgroups while
+ *      the others go on.  LSM_OK only when all columns converged, and only then are the free nodes of all columns stored;
+ *      otherwise no field of any column changes, the converged ones included, and the error is LSM_ERR_INVALID if a column had
+ *      non-finite input, else LSM_ERR_NOT_CONVERGED; the message names the lowest such column with its iterations and residual.
+ *      LSM_ERR_INVALID without running anything: K out of range, a null or repeated field, rtol not positive and finite,
+ *      max_iters < 1.  The batch has a workspace of its own (7 doubles per node and column on level 0, 3 on the others),
+ *      allocated by the first call, kept on the object and grown when a later call asks for more columns; when it cannot be
+ *      allocated the HIP error is returned and the object stays usable.  lsm_elliptic_solve and the modes of the object are
+ *      unaffected by a batched call in between.  Not to be called concurrently with another call on the object.
+ *      lsm_elliptic_energy_many: e_I = sum_k w_k·e_{k,I}, k ascending from +0, e_{k,I} lsm_elliptic_energy's value of column k
+ *      in fp64 before its rounding; rounded once to the storage type, ghosts untouched; one pass over the grid.
+ *      LSM_ERR_INVALID: K out of range, a null or repeated field, an output that is an input, a weight that is not finite.
+ *      lsm_elliptic_energy_mutual: m_I = lsm_elliptic_energy's sums with g·g replaced by g_u·g_v, g_u = (u_J − u_I)/h_d and g_v the
+ *      same for v, in the same order, rounded once: the integrand of the shape derivative of l·u for the state A u = f and
+ *      the adjoint A v = l.  With v = u it is lsm_elliptic_energy bit for bit; m(u, v) and m(v, u) are the same bits.  Like
+ *      lsm_elliptic_energy it is the a∇u·∇v part only: the c·u·v term is not in it.  u and v may be the same field;
+ *      LSM_ERR_INVALID: a null field, an output that is an input. */
 #define LSM_PRECOND_MG 0
 #define LSM_PRECOND_JACOBI 1
 typedef struct LsmElliptic LsmElliptic;
@@ -584,6 +607,11 @@ int lsm_elliptic_solve(LsmElliptic* s, const double* f, void* u, double rtol, in
 int lsm_elliptic_energy(LsmElliptic* s, const void* u, void* e_out);
 int lsm_elliptic_compliance(LsmElliptic* s, const double* f, const void* u, double* out);
 int lsm_elliptic_cells(LsmElliptic* s, double* a_out_cells);
+#define LSM_ELLIPTIC_MAXCOLS 8
+int lsm_elliptic_solve_many(LsmElliptic* s, int K, const double* f, void* const* u, double rtol, int max_iters, int* iters, double* relres,
+                            int* status, void* stream);
+int lsm_elliptic_energy_many(LsmElliptic* s, int K, void* const* u, const double* w, void* e_out);
+int lsm_elliptic_energy_mutual(LsmElliptic* s, const void* u, const void* v, void* e_out);
 void lsm_elliptic_destroy(LsmElliptic* s);
 
 /* ---- elasticity_solve: −∇·σ(u) = f on the box of a dense 2-D or 3-D grid, σ = E(x)·C0(ν):ε(u), the state equation of a

@@ -611,6 +611,31 @@ end
 # the level-0 cell coefficients into a ROCArray{Float64} of size n .- 1
 elliptic_cells!(a, E) = _check(E.h.ptr, ccall((:lsm_elliptic_cells, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Float64}), E.op, pointer(a)), "lsm_elliptic_cells")
 
+# elliptic_solve_many!: K ≤ 8 sources of one operator in one batched solve.  us: K fields (guess and Dirichlet values in, solutions out);
+# f: a ROCArray{Float64} of K·nn values, column k at (k-1)·nn.  Column k is elliptic_solve! of column k bit for bit.  Returns the K
+# iteration counts, residuals and statuses; unless every column converges it throws and leaves every field untouched.
+function elliptic_solve_many!(us, E, f; rtol = 1e-8, max_iters = 500)
+    nk = length(us)
+    iters, relres, status = zeros(Cint, nk), zeros(Float64, nk), zeros(Cint, nk)
+    p = Ptr{Cvoid}[pointer(u.buf) for u in us]
+    _check(E.h.ptr, ccall((:lsm_elliptic_solve_many, libhiplsm), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Ptr{Cvoid}}, Float64, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint}, Ptr{Cvoid}),
+        E.op, nk, pointer(f), p, rtol, max_iters, iters, relres, status, C_NULL), "lsm_elliptic_solve_many")
+    return (; iterations = iters, relres = relres, status = status)
+end
+
+# Σ_k w_k·(the energy density of column k) into the field e, in one pass: the normal speed of a weighted multi-source compliance descent
+function elliptic_energy_many!(e::ROCMeshField, E, us, w)
+    p, wv = Ptr{Cvoid}[pointer(u.buf) for u in us], collect(Float64, w)
+    _check(E.h.ptr, ccall((:lsm_elliptic_energy_many, libhiplsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Float64}, Ptr{Cvoid}),
+        E.op, length(us), p, wv, pointer(e.buf)), "lsm_elliptic_energy_many")
+end
+
+# the mutual energy density a∇u·∇v at the nodes into the field e (without the c·u·v term): the shape-derivative integrand of l·u for the adjoint A v = l
+elliptic_energy_mutual!(e::ROCMeshField, E, u::ROCMeshField, v::ROCMeshField) =
+    _check(E.h.ptr, ccall((:lsm_elliptic_energy_mutual, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        E.op, pointer(u.buf), pointer(v.buf), pointer(e.buf)), "lsm_elliptic_energy_mutual")
+
 destroy_elliptic(E) = ccall((:lsm_elliptic_destroy, libhiplsm), Cvoid, (Ptr{Cvoid},), E.op)
 
 # elasticity_operator: the discrete Q1 operator of −∇·σ(u), σ = E(x)·C₀(ν):ε(u), on ϕ's grid with its multigrid hierarchy

@@ -18,7 +18,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
                   components, remove_components_, prune_, Components, nucleate_, find_nucleation_sites, Nucleation,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
-                  elasticity_solve, elasticity_solve_many, ElasticityOperator, ElasticitySolution, ElasticityMultiSolution, elasticity_modes, ElasticityModes, elliptic_modes, EllipticModes,
+                  elliptic_solve_many, EllipticMultiSolution, elasticity_solve, elasticity_solve_many, ElasticityOperator, ElasticitySolution, ElasticityMultiSolution, elasticity_modes, ElasticityModes, elliptic_modes, EllipticModes,
                   StressSensitivity,
                   homogenize, Homogenization, homogenize_conductivity, ConductivityHomogenization)
 
@@ -35,6 +35,6 @@ __all__ = [
     "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
     "components", "remove_components_", "prune_", "Components", "nucleate_", "find_nucleation_sites", "Nucleation",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
-    "elasticity_solve", "elasticity_solve_many", "ElasticityOperator", "ElasticitySolution", "ElasticityMultiSolution", "elasticity_modes", "ElasticityModes", "elliptic_modes", "EllipticModes", "StressSensitivity",
+    "elliptic_solve_many", "EllipticMultiSolution", "elasticity_solve", "elasticity_solve_many", "ElasticityOperator", "ElasticitySolution", "ElasticityMultiSolution", "elasticity_modes", "ElasticityModes", "elliptic_modes", "EllipticModes", "StressSensitivity",
     "homogenize", "Homogenization", "homogenize_conductivity", "ConductivityHomogenization",
 ]

@@ -160,6 +160,10 @@ _SIGS = [
     ("lsm_elliptic_energy", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_elliptic_compliance", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("lsm_elliptic_cells", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("lsm_elliptic_solve_many", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_int), C.c_void_p]),
+    ("lsm_elliptic_energy_many", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.c_void_p]),
+    ("lsm_elliptic_energy_mutual", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_elliptic_destroy", None, [C.c_void_p]),
     ("lsm_elastic_create", C.c_int, [_H, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int,
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),

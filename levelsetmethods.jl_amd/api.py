@@ -2674,9 +2674,75 @@ class EllipticSolution:
         op.backend.elliptic_energy(op._handle(), self.u.buf, e.buf)
         return e
 
+    def mutual_energy_density(self, other):
+        """the ROCMeshField of m_I = energy_density()'s sums with g·g replaced by g_u·g_v, v = other.u: a∇u·∇v at the nodes, the integrand
+        of the shape derivative of l·u for this state and the adjoint `other` (A v = l) of the same operator.  The c·u·v
+        term is not in it.  With other = self it is energy_density() bit for bit, and it is symmetric bit for bit."""
+        op = self.operator
+        if not isinstance(other, EllipticSolution) or other.operator is not op:
+            raise ValueError("mutual_energy_density: the other solution belongs to another operator")
+        e = ROCMeshField(op.backend, self.u.mesh, self.u.bcs)
+        op.backend.elliptic_energy_mutual(op._handle(), self.u.buf, other.u.buf, e.buf)
+        return e
+
     def compliance(self):
         op = self.operator
         return op.backend.elliptic_compliance(op._handle(), self._f, self.u.buf)
+
+
+class EllipticMultiSolution:
+    """solve_many's result: a sequence of K EllipticSolutions of one operator (len, indexing, iteration), each with its own u, iterations,
+    relres and source.  `iterations` and `relres` are tuples, `operator` and `levels` as on a single solution.  compliances() → the K
+    values; compliance(weights=None) = Σ w_k·c_k (weights default to 1); cross_compliance(i, j) = ∏h·Σ (m·f_i)·u_j; energy_density(weights=None)
+    → the ROCMeshField of Σ_k w_k·e_k in one pass over the grid; mutual_energy_density(i, j) → that of columns i and j."""
+
+    def __init__(self, op, columns):
+        self.operator, self._columns, self.levels = op, tuple(columns), op.levels
+        self.iterations = tuple(c.iterations for c in self._columns)
+        self.relres = tuple(c.relres for c in self._columns)
+
+    def __len__(self):
+        return len(self._columns)
+
+    def __getitem__(self, k):
+        return self._columns[k]
+
+    def __iter__(self):
+        return iter(self._columns)
+
+    def _weights(self, weights, what):
+        K = len(self._columns)
+        w = [1.0] * K if weights is None else [float(v) for v in weights]
+        if len(w) != K:
+            raise ValueError(f"{what}: {len(w)} weights for {K} columns")
+        if not all(math.isfinite(v) for v in w):
+            raise ValueError(f"{what}: the weights must be finite")
+        return w
+
+    def compliances(self):
+        return tuple(c.compliance() for c in self._columns)
+
+    def compliance(self, weights=None):
+        w = self._weights(weights, "compliance")
+        total = 0.0
+        for wk, ck in zip(w, self.compliances()):
+            total = total + wk * ck
+        return total
+
+    def cross_compliance(self, i, j):
+        op = self.operator
+        return op.backend.elliptic_compliance(op._handle(), self._columns[i]._f, self._columns[j].u.buf)
+
+    def energy_density(self, weights=None):
+        op = self.operator
+        w = self._weights(weights, "energy_density")
+        u0 = self._columns[0].u
+        e = ROCMeshField(op.backend, u0.mesh, u0.bcs)
+        op.backend.elliptic_energy_many(op._handle(), [c.u.buf for c in self._columns], w, e.buf)
+        return e
+
+    def mutual_energy_density(self, i, j):
+        return self._columns[i].mutual_energy_density(self._columns[j])
 
 
 class EllipticOperator:
@@ -2755,8 +2821,9 @@ class EllipticOperator:
             raise ValueError("the EllipticOperator is closed")
         return self._h
 
-    def _field(self, u0):
-        """a new field holding the guess (zero without one) and the Dirichlet values"""
+    def _field(self, u0, homogeneous=False):
+        """a new field holding the guess (zero without one) and, on the Dirichlet nodes, their values — or zero (homogeneous: an adjoint
+        column)"""
         b = self.backend
         u = ROCMeshField(b, self.mesh, self.bcs)
         if isinstance(u0, ROCMeshField):
@@ -2768,8 +2835,15 @@ class EllipticOperator:
             u.copy_(np.broadcast_to(v, tuple(int(m) for m in self.mesh.n)))
         if self._mask is not None:
             iv = b.interior(u.buf)
-            iv.copy_(b.torch.where(self._mask, self._values.to(iv.dtype), iv))
+            iv.copy_(b.torch.where(self._mask, b.torch.zeros_like(iv) if homogeneous else self._values.to(iv.dtype), iv))
         return u
+
+    def _source(self, f):
+        """f as one flat float64 device array"""
+        b = self.backend
+        if isinstance(f, ROCMeshField):
+            return b.interior(f.buf).to(b.torch.float64).contiguous().reshape(-1)
+        return b.node_array(f if b.torch.is_tensor(f) else _host_values(f), "f")       # a flat float64 device tensor is taken as it is
 
     def solve(self, f, u0=None, rtol=1e-8, max_iters=500):
         b = self.backend
@@ -2777,10 +2851,7 @@ class EllipticOperator:
         rtol = float(rtol)
         if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
             raise ValueError("elliptic_solve: rtol must be positive and finite, max_iters at least 1")
-        if isinstance(f, ROCMeshField):
-            fd = b.interior(f.buf).to(b.torch.float64).contiguous().reshape(-1)
-        else:
-            fd = b.node_array(f if b.torch.is_tensor(f) else _host_values(f), "f")       # a flat float64 device tensor is taken as it is
+        fd = self._source(f)
         u = self._field(u0)
         try:
             it, rel = b.elliptic_solve(h, fd, u.buf, rtol, int(max_iters))
@@ -2791,6 +2862,45 @@ class EllipticOperator:
                 raise ValueError("elliptic_solve: f, u0 and the Dirichlet values must be finite") from None
             raise
         return EllipticSolution(self, u, fd, it, rel)
+
+    def solve_many(self, fs, u0=None, homogeneous=None, rtol=1e-8, max_iters=500):
+        """K = len(fs) ≤ 8 sources of this operator in one batched solve → EllipticMultiSolution.  Column k is solve(fs[k], u0[k]) bit for
+        bit: u, iterations and relres.  `fs`: a sequence of sources, each in any form solve takes; `u0`: None or a
+        sequence of guesses (an entry may be None); `homogeneous`: a sequence of booleans — a true column takes zero on the Dirichlet
+        nodes instead of their values (an adjoint column).  Unless every column converges nothing is kept: LsmNotConvergedError carries
+        .iterations, .relres and .status (1 converged, 2 out of iterations, −2 / −3 breakdown) tuples; ValueError for what is refused
+        and for non-finite data, naming the column."""
+        what = "elliptic_solve_many"
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError(f"{what}: rtol must be positive and finite, max_iters at least 1")
+        if not isinstance(fs, (tuple, list)):
+            raise TypeError(f"{what}: fs must be a sequence of sources")
+        b = self.backend
+        K = len(fs)
+        if not 1 <= K <= b.ELLIPTIC_MAXCOLS:
+            raise ValueError(f"{what}: {K} sources (1 to {b.ELLIPTIC_MAXCOLS} are solved together)")
+        if u0 is not None and not isinstance(u0, (tuple, list)):
+            raise TypeError(f"{what}: u0 must be None or a sequence of guesses, one per source")
+        if homogeneous is not None and not isinstance(homogeneous, (tuple, list)):
+            raise TypeError(f"{what}: homogeneous must be None or a sequence of booleans, one per source")
+        u0 = [None] * K if u0 is None else list(u0)
+        homogeneous = [False] * K if homogeneous is None else [bool(v) for v in homogeneous]
+        if len(u0) != K or len(homogeneous) != K:
+            raise ValueError(f"{what}: u0 and homogeneous must have one entry per source ({K})")
+        h = self._handle()
+        fds = [self._source(f) for f in fs]
+        us = [self._field(u0[k], homogeneous[k]) for k in range(K)]
+        try:
+            its, rels, _ = b.elliptic_solve_many(h, b.torch.cat(fds), [u.buf for u in us], rtol, int(max_iters))
+        except L.LsmNotConvergedError:
+            raise
+        except L.LsmError as e:
+            if "must be finite" in str(e):
+                col = [k for k, v in enumerate(getattr(e, "status", ())) if v == -1]
+                raise ValueError(f"{what}: f, u0 and the Dirichlet values must be finite (column {col[0] if col else '?'})") from None
+            raise
+        return EllipticMultiSolution(self, [EllipticSolution(self, us[k], fds[k], its[k], rels[k]) for k in range(K)])
 
     def apply(self, x):
         """A x on all nodes, no elimination: x a host array of the grid's shape; returns one (for tests and diagnostics)"""
@@ -2835,6 +2945,20 @@ def elliptic_solve(phi_or_eq, f, *, a_in=1.0, a_out=1e-3, a=None, c=0.0, dirichl
     op = EllipticOperator(phi_or_eq, a_in=a_in, a_out=a_out, a=a, c=c, dirichlet=dirichlet, level=level, precond=precond)
     try:
         return op.solve(f, u0=u0, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        op.close()
+        raise
+
+
+def elliptic_solve_many(phi_or_eq, fs, *, a_in=1.0, a_out=1e-3, a=None, c=0.0, dirichlet=None, u0=None, homogeneous=None, level=0.0, rtol=1e-8, max_iters=500,
+                        precond="mg"):
+    """elliptic_solve for K ≤ 8 sources `fs` of the one structure, solved together on the device (EllipticOperator.solve_many): several
+    load cases of a thermal compliance design, or a state and its adjoint (homogeneous=(False, True)) whose mutual_energy_density is the
+    speed of an objective l·u — a sensor temperature, a mean over a region.  Returns an EllipticMultiSolution; the other arguments are
+    elliptic_solve's."""
+    op = EllipticOperator(phi_or_eq, a_in=a_in, a_out=a_out, a=a, c=c, dirichlet=dirichlet, level=level, precond=precond)
+    try:
+        return op.solve_many(fs, u0=u0, homogeneous=homogeneous, rtol=rtol, max_iters=max_iters)
     except BaseException:
         op.close()
         raise

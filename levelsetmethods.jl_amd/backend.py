@@ -499,6 +499,36 @@ class HipBackend:
         L.check(self.h, self.lib.lsm_elliptic_cells(obj, self.ptr(out)), "lsm_elliptic_cells")
         return out
 
+    ELLIPTIC_MAXCOLS = 8
+
+    def _fields_array(self, us):
+        """the field pointers of K columns as a C array"""
+        ptrs = [int(u.data_ptr()) for u in us]
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def elliptic_solve_many(self, obj, f, us, rtol, max_iters):
+        """K columns in one batched solve: f the K·nn sources, us the K fields.  Returns (iterations, relres, status) tuples; raises after
+        setting .iterations, .relres, .status on the error when the library filled them"""
+        K = len(us)
+        it, rel, stat = (C.c_int * K)(), (C.c_double * K)(), (C.c_int * K)()
+        code = self.lib.lsm_elliptic_solve_many(obj, K, self.ptr(f), self._fields_array(us), float(rtol), int(max_iters), it, rel, stat, None)
+        out = tuple(int(v) for v in it), tuple(float(v) for v in rel), tuple(int(v) for v in stat)
+        if code != L.OK:
+            try:
+                L.check(self.h, code, "lsm_elliptic_solve_many")
+            except L.LsmError as e:
+                e.iterations, e.relres, e.status = out
+                raise
+        return out
+
+    def elliptic_energy_many(self, obj, us, w, e):
+        K = len(us)
+        L.check(self.h, self.lib.lsm_elliptic_energy_many(obj, K, self._fields_array(us), (C.c_double * K)(*[float(v) for v in w]), self.ptr(e)),
+                "lsm_elliptic_energy_many")
+
+    def elliptic_energy_mutual(self, obj, u, v, e):
+        L.check(self.h, self.lib.lsm_elliptic_energy_mutual(obj, self.ptr(u), self.ptr(v), self.ptr(e)), "lsm_elliptic_energy_mutual")
+
     def elliptic_destroy(self, obj):
         self.lib.lsm_elliptic_destroy(obj)
 

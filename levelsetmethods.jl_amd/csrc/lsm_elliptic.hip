@@ -12,6 +12,9 @@
 // The PCG iteration and the V-cycle are mg_pcg.h's, with one component per node and ω = 0.8.  What is this file's own:
 //   K1  p' = z + β p fused into the apply (p double-buffered: neighbours read the old one),  q = A p',  σ = p'·q   → α = ρ/σ
 //   a NULL mask (no fixed node) costs no read; a neighbour's mask byte is read instead of its value where it is fixed.
+// The batched solve (lsm_elliptic_solve_many) is mg_pcg.h's batched V-cycle and K2 with this file's init (a MANY switch)
+// and store: the column is blockIdx.z, its vectors lie at the column stride nn, its fields come as K pointers in a kernel argument.  Its
+// K1 (el_k1_many_kernel) keeps the columns in one workgroup instead: a thread owns a node for all columns and forms its coefficients once.
 #include "el_cell.h"
 #include "lobpcg.h"
 #include "mg_pcg.h"
@@ -22,6 +25,8 @@ static const double EL_OMEGA = 0.8;
 enum { EL_BAD_PHI = 0, EL_BAD_A = 1, EL_BAD_C = 2, EL_NFIXED = 3, EL_CPOS = 4, EL_NSTAT = 8 };
 
 struct ElVec : MgVec { double* p[2]; };     // p double-buffered: K1 writes the one, its neighbours read the other
+struct ElUMany { void* p[MG_MAXCOLS]; };    // the fields of the columns of a batched call
+struct ElW { double w[MG_MAXCOLS]; };       // their weights
 
 struct ElLevel {
     int n[3];
@@ -38,6 +43,8 @@ struct ElLevel {
     __device__ __forceinline__ bool fixed(int id, int) const { return mask && mask[id]; }
     __device__ __forceinline__ static double omega() { return EL_OMEGA; }
     static void launch_resid(int N, unsigned nb, hipStream_t s, const ElLevel& L, const double* r, const double* x, double* res, const MgState* st);
+    static void launch_resid_many(int N, unsigned nb, unsigned cols, hipStream_t s, const ElLevel& L, const double* r, const double* x, double* res,
+                                  const MgState* st);
     // the eliminated operator at a free node: with MASK fixed neighbours count as zero unread, without it x holds zero there
     template <int N, bool MASK>
     __device__ __forceinline__ void apply(int id, const int I[3], const double* x, int stride, double out[1]) const;
@@ -226,9 +233,17 @@ __global__ void __launch_bounds__(MG_THREADS) el_compliance_kernel(ElLevel L, Mg
 
 // ---- PCG
 // x₀ = u (the guess and the Dirichlet values), b = m·f, r₀ = b − A x₀ on the free nodes, 0 on the fixed ones; ‖b_free‖², ‖r₀‖²;
-// jac: z = r/D and ρ = r·z as well
-template <int N>
-__global__ void __launch_bounds__(MG_THREADS) el_init_kernel(ElLevel L, MgField F, ElVec V, const double* __restrict__ f, const void* __restrict__ u, int jac) {
+// jac: z = r/D and ρ = r·z as well.  MANY: column blockIdx.z of a batch; its field is um.p[blockIdx.z] (um: one ElUMany; u is not read)
+template <int N, int MANY = 0, class... UM>
+__global__ void __launch_bounds__(MG_THREADS) el_init_kernel(ElLevel L, MgField F, ElVec V, const double* __restrict__ f, const void* __restrict__ u, int jac,
+                                                             UM... um) {
+    if constexpr (MANY) {
+        const size_t c = blockIdx.z, at = c * (size_t)L.nn;
+        V.x += at; V.r += at; V.z += at; V.p[0] += at; f += at;
+        V.partial += c * (4 * MG_MAXB);
+        V.st += c;
+        u = (um.p[c], ...);
+    }
     double red[4] = {0.0, 0.0, 0.0, 0.0};     // ‖b_free‖², ‖r₀‖², r·z, non-finite entries (a count below 2^53: exact)
     MG_LOOP(id, L.nn) {
         int I[3];
@@ -288,6 +303,87 @@ __global__ void __launch_bounds__(MG_THREADS) el_k1_kernel(ElLevel L, ElVec V, i
     mg_k1_tail(*V.st, red[0]);
 }
 
+// K1 of a batch of NCOL columns (vectors at the column stride nn, states and partials per column, as mg_pcg.h lays a batch out).  The
+// columns are not on blockIdx.z here: a thread owns a node for all of them — the cells, the edge coefficients, c·m and the neighbours'
+// mask bytes once, as elm_apply_kernel forms them (in the scalar operator they are most of an apply), then per running column
+// el_k1_kernel's arithmetic in its order; a column that has left MG_RUN is skipped.  The launch shape and the grid-stride assignment of
+// nodes to threads are el_k1_kernel's, and p'·q is reduced per column into that column's own partials and ticket: the same partials in
+// the same order, hence the single solve's bits.  NCOL is a compile-time count, so that red[] stays in registers; the z-column form of
+// this kernel (a MANY switch on el_k1_kernel) was built, measured slower and removed
+template <int N, int NCOL>
+__global__ void __launch_bounds__(MG_THREADS) el_k1_many_kernel(ElLevel L, ElVec V, int par) {
+    bool run[NCOL], any = false;
+    double beta[NCOL], red[NCOL];
+#pragma unroll
+    for (int k = 0; k < NCOL; ++k) {
+        run[k] = V.st[k].status == MG_RUN;
+        beta[k] = V.st[k].beta;
+        red[k] = 0.0;
+        any = any || run[k];
+    }
+    if (!any) return;
+    const double* __restrict__ z = V.z;
+    const double* __restrict__ po = V.p[par];
+    double* __restrict__ pn = V.p[par ^ 1];
+    double* __restrict__ qv = V.q;
+    const int cs[3] = {1, L.n[0], L.n[0] * L.n[1]};
+    const double half = N == 2 ? 0.5 : 0.25;
+    const size_t nn = (size_t)L.nn;
+    MG_LOOP(id, L.nn) {
+        if (L.fixed(id, 0)) {
+#pragma unroll
+            for (int k = 0; k < NCOL; ++k)
+                if (run[k]) {
+                    pn[k * nn + id] = 0.0;
+                    qv[k * nn + id] = 0.0;
+                }
+            continue;
+        }
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        double v[1 << N];
+        el_cells_around<N>(L, I, v);
+        double w[2 * N];
+        int q[2 * N];
+        bool edge[2 * N], rd[2 * N];      // the edge exists; its far node is free (its value is read)
+#pragma unroll
+        for (int d = 0; d < N; ++d)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int e = 2 * d + s;
+                edge[e] = s ? I[d] < L.n[d] - 1 : I[d] > 0;
+                q[e] = edge[e] ? (s ? id + cs[d] : id - cs[d]) : id;
+                rd[e] = edge[e] && !L.fixed(q[e], 0);
+                w[e] = (el_edge_sum<N>(v, d, s) * half) * L.ih2[d];
+            }
+        const double cm = el_cm<N>(L, id, I);
+#pragma unroll
+        for (int k = 0; k < NCOL; ++k) {
+            if (!run[k]) continue;
+            const double* __restrict__ zk = z + k * nn;
+            const double* __restrict__ pk = po + k * nn;
+            const double pp = zk[id] + beta[k] * pk[id];
+            double acc = 0.0;
+#pragma unroll
+            for (int e = 0; e < 2 * N; ++e) {
+                const double xn = rd[e] ? zk[q[e]] + beta[k] * pk[q[e]] : 0.0;
+                if (edge[e]) acc = acc + w[e] * (pp - xn);
+            }
+            const double qq = acc + cm * pp;
+            red[k] += pp * qq;
+            pn[k * nn + id] = pp;
+            qv[k * nn + id] = qq;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NCOL; ++k) {
+        if (!run[k]) continue;      // uniform over the grid
+        double r1[1] = {red[k]};
+        if (block_reduce_ordered<1, MG_THREADS>(r1, V.partial + (size_t)k * (4 * MG_MAXB), &V.st[k].ticket[1]) && threadIdx.x == 0) mg_k1_tail(V.st[k], r1[0]);
+        __syncthreads();      // the reduction's LDS is reused by the next column
+    }
+}
+
 // ---- x → u on the free nodes (rounded to the storage type); the fixed nodes and the ghosts are left as they are
 template <int N>
 __global__ void __launch_bounds__(MG_THREADS) el_store_kernel(ElLevel L, MgField F, const double* __restrict__ x, void* __restrict__ u) {
@@ -299,11 +395,114 @@ __global__ void __launch_bounds__(MG_THREADS) el_store_kernel(ElLevel L, MgField
     }
 }
 
+// the same for the columns of a batch: column blockIdx.z of x into its field
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) el_store_many_kernel(ElLevel L, MgField F, const double* __restrict__ x, ElUMany U) {
+    x += (size_t)blockIdx.z * L.nn;
+    void* __restrict__ u = U.p[blockIdx.z];
+    MG_LOOP(id, L.nn) {
+        if (L.fixed(id, 0)) continue;
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        st_val(u, mg_padded(F, I), F.f32, x[id]);
+    }
+}
+
+// ---- the fields of a batch
+// what el_energy_kernel forms at a node before it reads u: per edge k̄ = S/(cells of the edge) and whether the edge exists
+template <int N>
+struct ElEdges {
+    double kb[2 * N];
+    bool on[2 * N];
+    long long off[2 * N];
+};
+template <int N>
+__device__ __forceinline__ void el_edges(const ElLevel& L, const MgField& F, const int I[3], ElEdges<N>& E) {
+    double v[1 << N];
+    el_cells_around<N>(L, I, v);
+    const long long fs[3] = {1, F.s1, F.s2};
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        double ncell = 1.0;
+#pragma unroll
+        for (int o = 0; o < N; ++o)
+            if (o != d && I[o] > 0 && I[o] < L.n[o] - 1) ncell = ncell * 2.0;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            E.on[2 * d + s] = s ? I[d] < L.n[d] - 1 : I[d] > 0;
+            E.kb[2 * d + s] = el_edge_sum<N>(v, d, s) / ncell;
+            E.off[2 * d + s] = s ? fs[d] : -fs[d];
+        }
+    }
+}
+// el_energy_kernel's sums at a node with g·g replaced by g_u·g_v (v = u: its bits)
+template <int N>
+__device__ __forceinline__ double el_energy_at(const ElLevel& L, const MgField& F, const ElEdges<N>& E, long long at, const void* __restrict__ u,
+                                               const void* __restrict__ v) {
+    const double ui = ld_val(u, at, F.f32), vi = ld_val(v, at, F.f32);
+    double e = 0.0;
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        double s = 0.0, cnt = 0.0;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const int k = 2 * d + side;
+            if (E.on[k]) {
+                const double gu = (ld_val(u, at + E.off[k], F.f32) - ui) / L.h[d];
+                const double gv = (ld_val(v, at + E.off[k], F.f32) - vi) / L.h[d];
+                s = s + E.kb[k] * (gu * gv);
+                cnt = cnt + 1.0;
+            }
+        }
+        e = e + s / cnt;
+    }
+    return e;
+}
+// ---- the mutual energy density m_I(u, v): the a∇u·∇v part only (the c·u·v term is not in it, as it is not in el_energy_kernel)
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) el_energy_mutual_kernel(ElLevel L, MgField F, const void* __restrict__ u, const void* __restrict__ v,
+                                                                      void* __restrict__ e_out) {
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        ElEdges<N> E;
+        el_edges<N>(L, F, I, E);
+        const long long at = mg_padded(F, I);
+        st_val(e_out, at, F.f32, el_energy_at<N>(L, F, E, at, u, v));
+    }
+}
+// ---- the weighted energy density of ncol columns in one pass: e_I = Σ_k w_k·e_{k,I}, k ascending from +0, e_{k,I} el_energy_kernel's
+// value of column k in fp64.  The edge coefficients and the counts of a node once; inside, the columns, each e_k finished before
+// w_k·e_k is added (no accumulator per column: nothing is indexed by k but the kernel arguments)
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) el_energy_many_kernel(ElLevel L, MgField F, ElUMany U, int ncol, ElW W, void* __restrict__ e_out) {
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        ElEdges<N> E;
+        el_edges<N>(L, F, I, E);
+        const long long at = mg_padded(F, I);
+        double e = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < ncol; ++k) e = e + W.w[k] * el_energy_at<N>(L, F, E, at, U.p[k], U.p[k]);
+        st_val(e_out, at, F.f32, e);
+    }
+}
+
 // ---- host side
 void ElLevel::launch_resid(int N, unsigned nb, hipStream_t s, const ElLevel& L, const double* r, const double* x, double* res, const MgState* st) {
     MG_LAUNCH2(N, mg_resid_kernel, ElLevel, nb, MG_THREADS, s, L, r, x, res, st);
 }
-using EllipticObject = MgSolver<ElLevel>;
+void ElLevel::launch_resid_many(int N, unsigned nb, unsigned cols, hipStream_t s, const ElLevel& L, const double* r, const double* x, double* res,
+                                const MgState* st) {
+    MG_LAUNCH3(N, mg_resid_kernel, ElLevel, 1, dim3(nb, 1, cols), MG_THREADS, s, L, r, x, res, st);
+}
+struct EllipticObject : MgSolver<ElLevel> {
+    // the batched solve's workspace: the vectors, states and partials of `cols` columns, with the levels (cells, D, c, masks) shared.
+    // Made by the first lsm_elliptic_solve_many, grown when a later one asks for more columns; the single solve's workspace, which
+    // the modes borrow, is not touched
+    std::unique_ptr<MgSolver<ElLevel>> many;
+};
 
 }  // namespace lsm
 
@@ -490,6 +689,145 @@ int lsm_elliptic_solve(LsmElliptic* s, const double* f, void* u, double rtol, in
     MG_LAUNCH(N, el_store_kernel, nb, MG_THREADS, st, L, o.F, (const double*)o.V.x, u);
     LSM_HIP(h, hipGetLastError());
     LSM_HIP(h, hipStreamSynchronize(st));
+    return LSM_OK;
+}
+
+// the batch workspace for K columns.  A larger one is built beside the old and takes its place only when every allocation succeeded
+static int el_many_reserve(LsmHandle* h, EllipticObject& o, int K) {
+    if (o.many && o.many->cols >= K) return LSM_OK;
+    std::unique_ptr<MgSolver<ElLevel>> w(new MgSolver<ElLevel>());
+    MgSolver<ElLevel>& M = *w;
+    const int nl = (int)o.lev.size();
+    M.N = o.N; M.precond = o.precond; M.cols = K; M.F = o.F;
+    M.lev = o.lev;
+    memcpy(M.co, o.co, sizeof(M.co));
+    // per level xa, xb, [rhs]; level 0: x r q p0 p1 as well
+    size_t nd = 0;
+    for (int l = 0; l < nl; ++l) nd += (size_t)K * (size_t)o.lev[l].nn * (size_t)(l ? 3 : 7);
+    LSM_HIP(h, M.buf.alloc(nd * sizeof(double)));
+    LSM_HIP(h, M.partial.alloc((size_t)K * 4 * MG_MAXB * sizeof(double)));
+    LSM_HIP(h, M.st.alloc(K * sizeof(MgState)));
+    LSM_HIP(h, M.h_st.alloc(K * sizeof(MgState)));
+    M.rhs.assign(nl, nullptr); M.xa.assign(nl, nullptr); M.xb.assign(nl, nullptr);
+    double* b = M.buf;
+    for (int l = 0; l < nl; ++l) {
+        const size_t m = (size_t)K * (size_t)o.lev[l].nn;
+        M.xa[l] = b; b += m;
+        M.xb[l] = b; b += m;
+        if (l) { M.rhs[l] = b; b += m; }
+        else {
+            M.V.x = b; b += m; M.V.r = b; b += m; M.V.q = b; b += m; M.V.p[0] = b; b += m; M.V.p[1] = b; b += m;
+        }
+    }
+    M.V.z = o.precond == LSM_PRECOND_JACOBI ? M.xa[0] : M.xb[0];
+    M.V.partial = M.partial;
+    M.V.st = M.st;
+    o.many = std::move(w);
+    return LSM_OK;
+}
+
+// K1 of a batch: el_k1_many_kernel for the handle's N and the K columns of the call (a compile-time count)
+template <int N>
+static void el_k1_many_launch(int K, unsigned nb, hipStream_t st, const ElLevel& L, const ElVec& V, int par) {
+    switch (K) {
+#define EL_K1_MANY_CASE(C) case C: hipLaunchKernelGGL((el_k1_many_kernel<N, C>), dim3(nb), dim3(MG_THREADS), 0, st, L, V, par); break;
+        EL_K1_MANY_CASE(1) EL_K1_MANY_CASE(2) EL_K1_MANY_CASE(3) EL_K1_MANY_CASE(4) EL_K1_MANY_CASE(5) EL_K1_MANY_CASE(6) EL_K1_MANY_CASE(7) EL_K1_MANY_CASE(8)
+#undef EL_K1_MANY_CASE
+    }
+}
+static_assert(MG_MAXCOLS == 8 && LSM_ELLIPTIC_MAXCOLS == MG_MAXCOLS, "el_k1_many_launch has a case per column count");
+
+// the K fields of a batched call: all given, no two the same
+static bool el_fields_many(int K, void* const* u, ElUMany& U) {
+    memset(&U, 0, sizeof(U));
+    if (!u) return false;
+    for (int a = 0; a < K; ++a) {
+        if (!u[a]) return false;
+        for (int b = 0; b < a; ++b)
+            if (u[b] == u[a]) return false;
+        U.p[a] = u[a];
+    }
+    return true;
+}
+
+int lsm_elliptic_solve_many(LsmElliptic* s, int K, const double* f, void* const* u, double rtol, int max_iters, int* iters, double* relres, int* status,
+                            void* stream) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    EllipticObject& o = *s->o;
+    ElUMany U;
+    if (K < 1 || K > LSM_ELLIPTIC_MAXCOLS) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_solve_many: K must be 1 ... LSM_ELLIPTIC_MAXCOLS (8)");
+    if (!f || !iters || !relres || !status || !el_fields_many(K, u, U))
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_solve_many: f, the K distinct fields of u and the three result arrays must be given");
+    if (!(rtol > 0) || !std::isfinite(rtol) || max_iters < 1)
+        return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_solve_many: rtol must be positive and max_iters at least 1");
+    const int N = o.N;
+    const ElLevel& L = o.lev[0];
+    const int jac = o.precond == LSM_PRECOND_JACOBI;
+    (void)hipSetDevice(h->device);
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int ra = el_many_reserve(h, o, K);
+    if (ra != LSM_OK) return ra;
+    MgSolver<ElLevel>& M = *o.many;
+    const int r0 = mg_reset(h, M, rtol, max_iters, st, K);
+    if (r0 != LSM_OK) return r0;
+    const unsigned nb = mg_blocks(L.nn), nz = (unsigned)K;
+    MG_LAUNCH3(N, el_init_kernel, 1, ElUMany, dim3(nb, 1, nz), MG_THREADS, st, L, o.F, M.V, f, (const void*)nullptr, jac, U);
+    LSM_HIP(h, hipGetLastError());
+    const int r1 = mg_iterate(h, M, max_iters, st, [&](int enq) {
+        const int par = enq & 1;
+        if (!jac) mg_vcycle<1>(M, M.V.r, st, K);
+        if (N == 2) el_k1_many_launch<2>(K, nb, st, L, M.V, par);
+        else el_k1_many_launch<3>(K, nb, st, L, M.V, par);
+        if (jac) hipLaunchKernelGGL((mg_k2_kernel<1, 1>), dim3(nb, 1, nz), dim3(MG_THREADS), 0, st, L.D, L.nn, (MgVec)M.V, (const double*)M.V.p[par ^ 1]);
+        else hipLaunchKernelGGL((mg_k2_kernel<0, 1>), dim3(nb, 1, nz), dim3(MG_THREADS), 0, st, L.D, L.nn, (MgVec)M.V, (const double*)M.V.p[par ^ 1]);
+    }, K);
+    if (r1 != LSM_OK) return r1;
+    // every column's outcome; the error is that of the lowest column with non-finite input, else of the lowest that did not converge
+    int bad = -1, bad_input = -1;
+    for (int k = 0; k < K; ++k) {
+        const MgState& S = M.h_st.p[k];
+        iters[k] = S.iters;
+        relres[k] = mg_relres(S);
+        status[k] = S.status == MG_RUN ? (int)MG_MAXITER : S.status;
+        if (S.status == MG_BREAK_INPUT && bad_input < 0) bad_input = k;
+        if (S.status != MG_CONVERGED && bad < 0) bad = k;
+    }
+    if (bad >= 0) return mg_report(h, M, "lsm_elliptic_solve_many", rtol, nullptr, nullptr, bad_input >= 0 ? bad_input : bad);
+    M.last_iters = 0;
+    for (int k = 0; k < K; ++k) M.last_iters = std::max(M.last_iters, iters[k]);
+    MG_LAUNCH(N, el_store_many_kernel, dim3(nb, 1, nz), MG_THREADS, st, L, o.F, (const double*)M.V.x, U);
+    LSM_HIP(h, hipGetLastError());
+    LSM_HIP(h, hipStreamSynchronize(st));
+    return LSM_OK;
+}
+
+int lsm_elliptic_energy_many(LsmElliptic* s, int K, void* const* u, const double* w, void* e_out) {
+    if (!s) return LSM_ERR_INVALID;
+    LsmHandle* h = s->h;
+    ElUMany U;
+    ElW W;
+    memset(&W, 0, sizeof(W));
+    if (K < 1 || K > LSM_ELLIPTIC_MAXCOLS) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_energy_many: K must be 1 ... LSM_ELLIPTIC_MAXCOLS (8)");
+    if (!w || !e_out || !el_fields_many(K, u, U)) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_energy_many: the K distinct fields of u, w and e_out must be given");
+    for (int k = 0; k < K; ++k) {
+        if (u[k] == e_out) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_energy_many: e_out must not be one of the inputs");
+        if (!std::isfinite(w[k])) return lsm_fail(h, LSM_ERR_INVALID, "lsm_elliptic_energy_many: the weights must be finite");
+        W.w[k] = w[k];
+    }
+    const ElLevel& L = s->o->lev[0];
+    MG_LAUNCH(s->o->N, el_energy_many_kernel, mg_blocks(L.nn), MG_THREADS, h->stream, L, s->o->F, U, K, W, e_out);
+    LSM_HIP(h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elliptic_energy_mutual(LsmElliptic* s, const void* u, const void* v, void* e_out) {
+    if (!s) return LSM_ERR_INVALID;
+    if (!u || !v || !e_out) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elliptic_energy_mutual: u, v and e_out must be given");
+    if (e_out == u || e_out == v) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elliptic_energy_mutual: e_out must not be one of the inputs");
+    const ElLevel& L = s->o->lev[0];
+    MG_LAUNCH(s->o->N, el_energy_mutual_kernel, mg_blocks(L.nn), MG_THREADS, s->h->stream, L, s->o->F, u, v, e_out);
+    LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
 
