@@ -462,6 +462,56 @@ int lsm_mesh_distance(LsmHandle* h, int64_t nverts, const void* vertices, int64_
 int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, double cutoff, int64_t max_iters, int64_t stats[4],
                 void* stream);
 
+/* ---- extend_from_interface_(F, phi): K <= 8 fields carried off a frozen set along the characteristics of |phi|,
+ *      grad F · grad |phi| = 0, first-order upwind, each value computed exactly once on lsm_eikonal's tile lists
+ *      (csrc/lsm_eikonal.hip; tests/_extend_ref.py restates every operation).  This comment is the rule.
+ *      phi: a dense field of the handle, read only (interior only).  F[0..nfields): fields of the handle in phi's padded layout
+ *      and storage type (device pointers; the array F itself is on the host), updated in place over the interior, the ghosts
+ *      left as they are.  Neighbours off the grid do not exist, whatever the boundary condition.  The key of node I is
+ *      g_I = |phi_I|, except under LSM_EXTEND_INSIDE, g_I = phi_I, and LSM_EXTEND_OUTSIDE, g_I = -phi_I: the same at the free
+ *      nodes, but with every frozen node below every free one (with |phi| a free node next to the interface whose frozen
+ *      neighbour sits deeper than it sits itself would have nobody to take a value from); w_d = 1/(h_d·h_d).
+ *      The frozen set.  LSM_EXTEND_RULE: lsm_eikonal's seeding set — I is crossing-adjacent when phi_I != 0 and an axis
+ *      neighbour J that exists has (phi_J > 0) != (phi_I > 0) or phi_J = 0; width = 0: the crossing-adjacent nodes and the
+ *      nodes with phi_I = 0; width = w > 0: the crossing-adjacent nodes and every node with |phi_I| <= w.  LSM_EXTEND_MASK:
+ *      `frozen`, a device array of one byte per interior node, n-shaped, axis 0 fastest; non-zero: frozen.
+ *      LSM_EXTEND_INSIDE: phi_I <= 0.  LSM_EXTEND_OUTSIDE: phi_I >= 0.  `frozen` is read by LSM_EXTEND_MASK only.
+ *      The seeds.  LSM_EXTEND_NODES: a frozen node keeps its F.  LSM_EXTEND_INTERFACE (with LSM_EXTEND_RULE only): a
+ *      crossing-adjacent node I takes the value at its crossings, computed from the input fields: per axis d with a crossing,
+ *      among the crossing neighbours the J with the smaller sigma_d = h_d·theta, theta = |phi_I|/(|phi_I| + |phi_J|) (a tie:
+ *      the - side); Fc_d = F_I + theta·(F_J - F_I), u_d = 1/(sigma_d·sigma_d); F_I := (sum_d u_d·Fc_d)/(sum_d u_d), the axes
+ *      ascending, the sums started at 0, clamped to [min_d Fc_d, max_d Fc_d] (below).  Every other frozen node keeps its F.
+ *      A node that is not frozen and has |phi_I| >= cutoff (0 < cutoff <= +inf) takes `fill` (counted in stats[4]).
+ *      Every other node is free.  Per axis d, a_d is the smaller key of its two axis neighbours (one, at a face), J_d the
+ *      neighbour that holds it (a tie: the - side).  Axis d participates iff a_d < g_I, strictly; c_d = w_d·(g_I - a_d).
+ *      F_I = (sum_d c_d·F_Jd)/(sum_d c_d) over the participating axes, ascending, the sums started at 0, plain multiplies and
+ *      adds (no fused multiply-add); then the clamp: r = the quotient; if not r >= lo then r = lo; if not r <= hi then r = hi,
+ *      with lo and hi the smallest and the largest F_Jd of the participating axes.  The clamp changes the quotient by
+ *      rounding at most; with it every value lies within the minimum and the maximum of the seeds exactly and a constant comes
+ *      back as it is.  A free node with no participating axis is an orphan: it keeps its input value and behaves as a frozen
+ *      node in every respect (counted in stats[3]); orphans appear where phi is not distance-like and on ties of rounded
+ *      values; the plateau beyond lsm_eikonal's cutoff is filled, not orphaned, when the same cutoff is passed.  The
+ *      dependencies are acyclic by the strict inequality, so every free node is reached whatever phi holds, every value is
+ *      computed once from final values, and the result does not depend on the tile schedule: the same bits in every run.
+ *      Refused with LSM_ERR_INVALID after one pointwise kernel, before any field is written: a non-finite phi (reason 1), a
+ *      non-finite F_k at a frozen node or an orphan (2), no frozen node at all (3); stats := {-reason, offending nodes, 0, 0, 0}
+ *      then.  The input values at the other nodes are never read and may be NaN.
+ *      max_iters: the bound on the outer iterations (rebuilds of the tile list, each followed by one launch of the tile
+ *      kernel over the listed tiles and all fields); <= 0: 2·sum_d n_d.  LSM_ERR_NOT_CONVERGED: the list was not empty after
+ *      max_iters iterations, or — an internal error, the message says so — it emptied with values left uncomputed.
+ *      stats[5] (may be NULL) := {frozen nodes by the rule or the mask, outer iterations, tile visits, orphans, filled nodes}.
+ *      LSM_ERR_INVALID without running anything: a 1-D grid, a handle with a communicator or of a slab, a periodic dimension,
+ *      fewer than two nodes in a dimension, nfields outside 1…8, a null field, the same field twice, a field that is phi,
+ *      width < 0 or not finite, cutoff <= 0 or NaN, a non-finite fill, LSM_EXTEND_MASK without a mask, an unknown rule or
+ *      source, LSM_EXTEND_INTERFACE with another rule than LSM_EXTEND_RULE.  In every failure the fields are untouched: only
+ *      the final pass writes them.  All arithmetic is fp64; an f32 handle is read once and rounded once on store.  stream:
+ *      NULL = the handle's.  The scratch arrays are lsm_eikonal's and 8·nfields bytes per node; they belong to the handle and
+ *      only grow.  Synchronous. */
+enum { LSM_EXTEND_RULE = 0, LSM_EXTEND_MASK = 1, LSM_EXTEND_INSIDE = 2, LSM_EXTEND_OUTSIDE = 3 };
+enum { LSM_EXTEND_NODES = 0, LSM_EXTEND_INTERFACE = 1 };
+int lsm_extend(LsmHandle* h, const void* phi, void* const* F, int nfields, int frozen_rule, const unsigned char* frozen,
+               double width, int source, double cutoff, double fill, int64_t max_iters, int64_t stats[5], void* stream);
+
 /* ---- components(ϕ, level, side): the connected components of the set S = {ϕ < level} (side 0) or of its complement (side 1)
  *      on the dense grid, labelled on the device by block-based union–find (csrc/lsm_cc.hip, DESIGN.md §7.16;
  *      tests/_cc_ref.py restates the definition).  inside(I) := ϕ[I] < level, as lsm_iso_*: ϕ == level is outside.  Two nodes

@@ -542,6 +542,23 @@ function eikonal!(ϕ::ROCMeshField; speed = nothing, width = 0.0, cutoff = Inf, 
     return (; frozen = stats[1], iterations = stats[2], visits = stats[3], clamped = stats[4])
 end
 
+# extend_from_interface!: the fields Fs (one ROCMeshField or a vector of 1…8, on ϕ's handle) carried off a frozen set along the
+# characteristics of |ϕ| (include/lsm.h, lsm_extend), in place; ϕ is read only.  frozen = nothing: eikonal!'s seeding set for the
+# same width; :inside (ϕ <= 0), :outside (ϕ >= 0), or a ROCVector{UInt8} with one byte per interior node (non-zero: frozen).
+# source = :nodes or :interface (the values at the crossings; with frozen = nothing only).  Returns (frozen, iterations, visits,
+# orphans, filled).
+function extend_from_interface!(Fs, ϕ::ROCMeshField; width = 0.0, frozen = nothing, source = :nodes, cutoff = Inf, fill = 0.0, max_iters = 0)
+    fields = Fs isa ROCMeshField ? [Fs] : collect(Fs)
+    ptrs = Ptr{Cvoid}[pointer(F.buf) for F in fields]
+    rule = frozen === nothing ? 0 : frozen === :inside ? 2 : frozen === :outside ? 3 : 1
+    stats = zeros(Int64, 5)
+    _check(ϕ.h.ptr, ccall((:lsm_extend, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Cint, Cint, Ptr{UInt8}, Float64, Cint, Float64, Float64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+        ϕ.h.ptr, pointer(ϕ.buf), ptrs, length(fields), rule, rule == 1 ? pointer(frozen) : C_NULL, width, source === :interface ? 1 : 0, cutoff, fill,
+        max_iters, stats, C_NULL), "lsm_extend")
+    return (; frozen = stats[1], iterations = stats[2], visits = stats[3], orphans = stats[4], filled = stats[5])
+end
+
 # components: the connected components of {ϕ < level} (side = :inside) or of its complement (:outside) over the Kuhn edges
 # (include/lsm.h, lsm_cc_*), numbered by their smallest linear node index.  Returns the object `cc` (release it with
 # destroy_components; remove_components! needs it), count, labels (Int32, one per node, −1 off the set, on the device), nodes

@@ -15,7 +15,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   perimeter, volume, InterpolatedField, NewtonSDF, hausdorff_distance, SideField, curvature, curvature_field, gradient, gradient_field, normal, normal_field,
                   vortex_deformation, show, LocalGroup, nodeindices, cellindices, getnode, getcell, active_nodeindices, active_cellindices,
                   update_band_, quadrature, integrate, Quadrature, CellQuadratures, isosurface, export_surface_mesh, InterfaceMesh, Camera, Renderer, render, record_, Image,
-                  volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_,
+                  volume_mesh, export_volume_mesh, DomainMesh, mesh_distance, mesh_distance_, read_mesh, eikonal, eikonal_, extend_from_interface_,
                   components, remove_components_, prune_, Components, nucleate_, find_nucleation_sites, Nucleation,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
                   elliptic_solve_many, EllipticMultiSolution, elasticity_solve, elasticity_solve_many, ElasticityOperator, ElasticitySolution, ElasticityMultiSolution, elasticity_modes, ElasticityModes, elliptic_modes, EllipticModes,
@@ -32,7 +32,7 @@ __all__ = [
     "InterpolatedField", "NewtonSDF", "hausdorff_distance", "SideField", "curvature", "curvature_field", "gradient", "gradient_field", "normal", "normal_field", "show", "LocalGroup",
     "nodeindices", "cellindices", "getnode", "getcell", "active_nodeindices", "active_cellindices", "update_band_",
     "quadrature", "integrate", "Quadrature", "CellQuadratures", "isosurface", "export_surface_mesh", "InterfaceMesh", "Camera", "Renderer", "render", "record_", "Image",
-    "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_",
+    "volume_mesh", "export_volume_mesh", "DomainMesh", "mesh_distance", "mesh_distance_", "read_mesh", "eikonal", "eikonal_", "extend_from_interface_",
     "components", "remove_components_", "prune_", "Components", "nucleate_", "find_nucleation_sites", "Nucleation",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
     "elliptic_solve_many", "EllipticMultiSolution", "elasticity_solve", "elasticity_solve_many", "ElasticityOperator", "ElasticitySolution", "ElasticityMultiSolution", "elasticity_modes", "ElasticityModes", "elliptic_modes", "EllipticModes", "StressSensitivity",

@@ -149,6 +149,8 @@ _SIGS = [
     ("lsm_vol_destroy", None, [C.c_void_p]),
     ("lsm_mesh_distance", C.c_int, [_H, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     ("lsm_eikonal", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    ("lsm_extend", C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int64,
+                             C.POINTER(C.c_int64), C.c_void_p]),
     ("lsm_cc_create", C.c_int, [_H, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("lsm_cc_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_cc_flip", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),

@@ -2279,7 +2279,7 @@ def mesh_distance(mesh, grid, cutoff=None, dtype=None, mode="fast", device=0, fa
 
 # ----------------------------------------------------------------------------- far-field distance and travel times
 
-def eikonal_(phi, speed=None, width=None, cutoff=None, max_iters=None):
+def eikonal_(phi, speed=None, width=None, cutoff=None, max_iters=None, extend=None, extend_source="nodes"):
     """Overwrite a device field with sign(ϕ)·min(T, cutoff), T the first-order Godunov solution of |∇T| = 1/speed over the whole
     grid, solved on the device by the block-based fast iterative method.  speed=None: T is the distance to
     the interface {ϕ = 0} — a redistancing of the whole grid in O(nodes), first-order accurate; where the exact distance of a
@@ -2289,7 +2289,13 @@ def eikonal_(phi, speed=None, width=None, cutoff=None, max_iters=None):
     |ϕ| <= w keep |ϕ| (ϕ already holds distances or times there).  cutoff=None means +inf: nodes with T <= cutoff hold the
     values they hold without one, the others ±cutoff.  `max_iters` bounds the outer iterations (default 2·Σ n_d); exceeding it
     raises a RuntimeError (LsmNotConvergedError) with ϕ unchanged.  `phi`: a dense ROCMeshField or a LevelSetEquation (its current
-    state), changed in place.  Returns ϕ."""
+    state), changed in place.  `extend`: a field or a sequence of 1…8 fields that extend_from_interface_ carries along the new
+    distance right after the solve, with the same `width` and `cutoff`, fill=0.0 and source=`extend_source`: redistance and
+    extend in one call.  Returns ϕ."""
+    if extend is not None:
+        _extend_fields(extend, phi.current_state() if isinstance(phi, LevelSetEquation) else phi, "eikonal_")    # refused before ϕ changes
+        if extend_source not in ("nodes", "interface"):
+            raise ValueError(f"eikonal_: extend_source must be 'nodes' or 'interface', not {extend_source!r}")
     eq = phi if isinstance(phi, LevelSetEquation) else None
     if eq is not None:
         phi = eq.current_state()
@@ -2339,7 +2345,103 @@ def eikonal_(phi, speed=None, width=None, cutoff=None, max_iters=None):
             raise
         raise ValueError(f"eikonal_: {why}") from None
     phi.ghosts_dirty = True
+    if extend is not None:
+        extend_from_interface_(extend, phi, width=width, source=extend_source, cutoff=cutoff, fill=0.0, max_iters=max_iters)
     return phi
+
+
+# ----------------------------------------------------------------------------- extension velocities over the whole grid
+
+def _extend_fields(F, phi, who):
+    """the list of device fields F names, checked against ϕ: the refusals of extend_from_interface_ that need no data"""
+    fields = [F] if isinstance(F, (ROCMeshField, MeshField)) or not isinstance(F, (list, tuple)) else list(F)
+    if not isinstance(phi, ROCMeshField):
+        raise TypeError(f"{who} takes a device field (ROCMeshField) or a LevelSetEquation as phi, not {type(phi).__name__}")
+    for f in fields:
+        if not isinstance(f, ROCMeshField):
+            raise TypeError(f"{who} extends device fields (ROCMeshField), not {type(f).__name__}")
+    for f in fields + [phi]:
+        if isinstance(f, ROCNarrowBandMeshField):
+            raise ValueError(f"{who} is not supported on NarrowBandMeshField: the extension runs over the whole grid")
+    if not 1 <= len(fields) <= 8:
+        raise ValueError(f"{who}: 1 to 8 fields, not {len(fields)}")
+    for k, f in enumerate(fields):
+        if f is phi or f.buf is phi.buf:
+            raise ValueError(f"{who}: a field to extend is phi itself")
+        if any(f is o or f.buf is o.buf for o in fields[:k]):
+            raise ValueError(f"{who}: the same field twice")
+        if f.backend is not phi.backend:
+            raise ValueError(f"{who}: a field lives on another backend than phi (fields of one equation share one)")
+        if f.mesh is not phi.mesh and (tuple(f.mesh.n) != tuple(phi.mesh.n) or tuple(f.mesh.lc) != tuple(phi.mesh.lc) or tuple(f.mesh.hc) != tuple(phi.mesh.hc)):
+            raise ValueError(f"{who}: a field lives on another mesh than phi")
+    return fields
+
+
+def extend_from_interface_(F, phi, *, width=None, frozen=None, source="nodes", cutoff=None, fill=0.0, max_iters=None):
+    """Carry the values of F off the interface of ϕ over the whole grid, constant along the characteristics of |ϕ|
+    (∇F·∇|ϕ| = 0, first-order upwind), on the device in O(nodes): the extension velocity an optimisation loop
+    needs before every advection, where extend_along_normals_ moves the information about `cfl` of a cell per sweep.  ϕ should
+    be distance-like (eikonal_, reinitialize_); every node is reached whatever ϕ holds.  `F`: a ROCMeshField or a sequence of
+    1…8 of them on ϕ's backend, changed in place; `phi`: a dense ROCMeshField or a LevelSetEquation (its current state), read only.
+    The frozen nodes keep their F.  frozen=None: eikonal_'s seeding set for the same `width` — the nodes next to a sign change
+    and the zeros of ϕ, with width = w > 0 also every node with |ϕ| <= w; "inside": ϕ <= 0; "outside": ϕ >= 0; a boolean or
+    0–1 array of the grid's shape or a host MeshField on the same grid: where it is non-zero.  source="interface" (with
+    frozen=None): the nodes next to a sign change first take the value F has at their crossings, interpolated along the grid
+    lines.  Nodes that are not frozen and have |ϕ| >= cutoff take `fill`.  Every value lies within the range of the seeds; the
+    result is the same bits in every run.  `max_iters` bounds the outer iterations (default 2·Σ n_d); exceeding it raises a
+    RuntimeError (LsmNotConvergedError) with F unchanged.  Returns F."""
+    eq = phi if isinstance(phi, LevelSetEquation) else None
+    if eq is not None:
+        phi = eq.current_state()
+    fields = _extend_fields(F, phi, "extend_from_interface_")
+    N = phi.mesh.ndim
+    if N == 1:
+        raise ValueError("extend_from_interface_ of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
+    b = phi.backend
+    if getattr(b, "slab", None) is not None:
+        raise ValueError("extend_from_interface_ of a slab-decomposed field (a field with a comm) is not supported")
+    if phi.bcs is not None and any(bc.kind == L.BC_PERIODIC for pair in phi.bcs for bc in pair):
+        raise ValueError("extend_from_interface_ with a PeriodicBC dimension is not supported: the characteristics do not wrap around")
+    w = 0.0 if width is None else float(width)
+    if not (w > 0 and math.isfinite(w)) and width is not None:
+        raise ValueError("extend_from_interface_: width must be positive and finite (None: the crossing seed)")
+    c = float("inf") if cutoff is None else float(cutoff)
+    if not c > 0:
+        raise ValueError("extend_from_interface_: cutoff must be positive (None or inf: no cutoff)")
+    fill = float(fill)
+    if not math.isfinite(fill):
+        raise ValueError("extend_from_interface_: fill must be finite")
+    if source not in ("nodes", "interface"):
+        raise ValueError(f"extend_from_interface_: source must be 'nodes' or 'interface', not {source!r}")
+    if source == "interface" and frozen is not None:
+        raise ValueError("extend_from_interface_: source='interface' takes the values at the crossings of phi and goes with frozen=None only")
+    rule, mask = "rule", None
+    if isinstance(frozen, str):
+        if frozen not in ("inside", "outside"):
+            raise ValueError(f"extend_from_interface_: frozen must be None, 'inside', 'outside' or a mask, not {frozen!r}")
+        rule = frozen
+    elif frozen is not None:
+        if isinstance(frozen, MeshField):
+            if tuple(frozen.mesh.n) != tuple(phi.mesh.n):
+                raise ValueError("extend_from_interface_: the frozen mask is a MeshField on another grid")
+            frozen = frozen.vals
+        mask = np.asarray(frozen)
+        if mask.shape != tuple(phi.mesh.n):
+            raise ValueError(f"extend_from_interface_: the frozen mask has shape {mask.shape}, the grid has {tuple(phi.mesh.n)} nodes")
+        rule = "mask"
+    try:
+        b.extend([f.buf for f in fields], phi.buf, rule, mask, w, source, c, fill, 0 if max_iters is None else max(1, int(max_iters)))
+    except L.LsmNotConvergedError:
+        raise
+    except L.LsmError as e:
+        why = {1: "phi must be finite", 2: "every field must be finite at the frozen nodes",
+               3: "no node is frozen (phi has no interface, or the mask is empty)"}.get(getattr(e, "reason", 0))
+        if why is None:
+            raise
+        raise ValueError(f"extend_from_interface_: {why} ({getattr(e, 'offenders', 0)} nodes)") from None
+    for f in fields:
+        f.ghosts_dirty = True
+    return F
 
 
 def eikonal(phi, speed=None, width=None, cutoff=None, max_iters=None, mode="fast", device=0):

@@ -367,6 +367,41 @@ class HipBackend:
             raise
         return tuple(int(s) for s in stats)
 
+    # ---- extension off a frozen set along the characteristics of |ϕ| (lsm_extend)
+    EXTEND_RULES = {"rule": 0, "mask": 1, "inside": 2, "outside": 3}
+    EXTEND_SOURCES = {"nodes": 0, "interface": 1}
+
+    def extend(self, fields, phi, rule="rule", mask=None, width=0.0, source="nodes", cutoff=float("inf"), fill=0.0, max_iters=0):
+        """fields: 1…8 device buffers of this backend, updated in place; rule: "rule", "mask" (mask: n-shaped, non-zero = frozen,
+        host or device, axis 0 fastest), "inside" or "outside"; source: "nodes" or "interface"; width 0: the crossing seed.  Returns
+        (frozen nodes, outer iterations, tile visits, orphans, filled nodes).  An LsmError raised for the data carries `reason`:
+        1 a non-finite ϕ, 2 a non-finite field at a frozen node, 3 no frozen node."""
+        t = self.torch
+        if getattr(self, "slab", None) is not None:
+            raise L.LsmError("extend: this backend holds a slab of a decomposed grid; lsm_extend works on the whole grid of one device")
+        fields = list(fields)
+        m = None
+        if mask is not None:
+            if not t.is_tensor(mask):
+                mask = np.asarray(mask)
+                if mask.shape != self.local_shape():
+                    raise L.LsmError(f"extend: the mask has shape {mask.shape}, the grid {self.local_shape()}")
+                mask = np.ascontiguousarray((mask != 0).reshape(-1, order="F").astype(np.uint8))
+            m = t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
+            if m.numel() != int(np.prod(self.local_shape())):
+                raise L.LsmError(f"extend: the mask has {m.numel()} values, the grid {int(np.prod(self.local_shape()))} nodes")
+        ptrs = (C.c_void_p * max(1, len(fields)))(*[self.ptr(f) for f in fields])
+        stats = (C.c_int64 * 5)()
+        code = self.lib.lsm_extend(self.h, self.ptr(phi), ptrs, len(fields), self.EXTEND_RULES[rule], self.ptr(m) if m is not None else None,
+                                   float(width), self.EXTEND_SOURCES[source], float(cutoff), float(fill), int(max_iters), stats, None)
+        try:
+            L.check(self.h, code, "lsm_extend")
+        except L.LsmError as e:
+            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0     # include/lsm.h: what the data was refused for
+            e.offenders = int(stats[1]) if e.reason else 0
+            raise
+        return tuple(int(s) for s in stats)
+
     # ---- connected components (lsm_cc_*)
     def cc_create(self, phi, level, side):
         """returns (result handle, (K, nodes in the set, cross-tile edges, non-finite nodes)); side 0: {ϕ < level}, 1: the

@@ -1826,6 +1826,43 @@ int lsm_eikonal(LsmHandle* h, void* phi, const double* speed, double width, doub
     return module_rc(h, r, err, "lsm_eikonal");
 }
 
+// extend: K fields carried off a frozen set along the characteristics of |phi|, on eikonal's tile lists (lsm_eikonal.hip)
+int lsm_extend(LsmHandle* h, const void* phi, void* const* F, int nfields, int frozen_rule, const unsigned char* frozen, double width, int source,
+               double cutoff, double fill, int64_t max_iters, int64_t stats[5], void* stream) {
+    if (!h || !phi || !F) return h ? fail(h, LSM_ERR_INVALID, "lsm_extend: null argument") : LSM_ERR_INVALID;
+    const int N = h->grid.ndim;
+    if (N == 1) return fail(h, LSM_ERR_INVALID, "lsm_extend: a 1-dimensional grid is not supported (2-D and 3-D only)");
+    if (h->comm) return fail(h, LSM_ERR_INVALID, "lsm_extend: the handle has a communicator attached (single device only)");
+    LSM_TRY(check_single_device(h));
+    for (int d = 0; d < N; ++d) {
+        if (h->bc[d][0].kind == LSM_BC_PERIODIC || h->bc[d][1].kind == LSM_BC_PERIODIC)
+            return fail(h, LSM_ERR_INVALID, "lsm_extend: a periodic dimension is not supported (the characteristics do not wrap)");
+        if (h->nloc[d] < 2) return fail(h, LSM_ERR_INVALID, "lsm_extend: at least two nodes per dimension");
+    }
+    if (nfields < 1 || nfields > 8) return fail(h, LSM_ERR_INVALID, "lsm_extend: nfields must be 1 to 8");
+    for (int k = 0; k < nfields; ++k) {
+        if (!F[k]) return fail(h, LSM_ERR_INVALID, "lsm_extend: a null field");
+        if (F[k] == phi) return fail(h, LSM_ERR_INVALID, "lsm_extend: a field is phi itself");
+        for (int j = 0; j < k; ++j)
+            if (F[j] == F[k]) return fail(h, LSM_ERR_INVALID, "lsm_extend: the same field twice");
+    }
+    if (frozen_rule < LSM_EXTEND_RULE || frozen_rule > LSM_EXTEND_OUTSIDE) return fail(h, LSM_ERR_INVALID, "lsm_extend: unknown frozen_rule");
+    if (source != LSM_EXTEND_NODES && source != LSM_EXTEND_INTERFACE) return fail(h, LSM_ERR_INVALID, "lsm_extend: unknown source");
+    if (source == LSM_EXTEND_INTERFACE && frozen_rule != LSM_EXTEND_RULE)
+        return fail(h, LSM_ERR_INVALID, "lsm_extend: source INTERFACE goes with frozen_rule RULE only");
+    if (frozen_rule == LSM_EXTEND_MASK && !frozen) return fail(h, LSM_ERR_INVALID, "lsm_extend: frozen_rule MASK without a mask");
+    if (!(width >= 0) || std::isinf(width)) return fail(h, LSM_ERR_INVALID, "lsm_extend: width must be finite and not negative (0: the crossing seed)");
+    if (!(cutoff > 0)) return fail(h, LSM_ERR_INVALID, "lsm_extend: cutoff must be positive (+inf: no cutoff)");
+    if (!std::isfinite(fill)) return fail(h, LSM_ERR_INVALID, "lsm_extend: fill must be finite");
+    const char* err = nullptr;
+    long long c[5] = {0, 0, 0, 0, 0};
+    const int r = extend_run(N, h->nloc, h->lay.stride[1], h->lay.stride[2], h->lay.origin, h->h, phi, is_f32(h), F, nfields, frozen_rule, frozen, width,
+                             source, cutoff, fill, max_iters, stream ? (hipStream_t)stream : h->stream, c, &err, &h->eikonal_ws);
+    if (stats)
+        for (int i = 0; i < 5; ++i) stats[i] = c[i];
+    return module_rc(h, r, err, "lsm_extend");
+}
+
 // components: the connected pieces of {phi < level} (side 0) or of its complement (side 1) over the Kuhn edges (lsm_cc.hip)
 struct LsmCc { LsmHandle* h; CcObject* o; };
 int lsm_cc_create(LsmHandle* h, const void* phi, double level, int side, LsmCc** out, int64_t stats[4]) {

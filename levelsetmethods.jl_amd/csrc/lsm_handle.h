@@ -225,6 +225,9 @@ namespace lsm {   // lsm_eikonal.hip: |∇T| = 1/F over the whole grid by the bl
 int eikonal_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double h[3], void* phi, int f32, const double* speed,
                 double width, double cutoff, long long max_iters, hipStream_t stream, long long stats[4], const char** err, EikonalWorkspace** workspace);
 void eikonal_workspace_free(EikonalWorkspace* w);   // delete, where the type is complete
+int extend_run(int ndim, const int n[3], long long s1, long long s2, long long origin, const double h[3], const void* phi, int f32, void* const* F, int K,
+               int rule, const unsigned char* mask, double width, int source, double cutoff, double fill, long long max_iters, hipStream_t stream,
+               long long stats[5], const char** err, EikonalWorkspace** workspace);   // extend_from_interface_ on eikonal's tile lists
 }
 namespace lsm {   // lsm_cc.hip: connected components of {ϕ < level} or of its complement over the Kuhn edges, by block-based union–find
 struct CcObject;
