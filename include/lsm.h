@@ -1064,6 +1064,53 @@ int lsm_elastic_stress_sensitivity(LsmElastic* s, const void* u0, const void* u1
 int lsm_elastic_topo_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, double* out);
 int lsm_elastic_topo(LsmElastic* s, const void* u0, const void* u1, const void* u2, void* o0);
 
+/* ---- thermoelastic coupling: a temperature field T as a load on the structure of an LsmElastic, the stress with the thermal strain
+ *      taken off, the elastic adjoint carried back into the heat problem, and the sensitivity of l·u to the cell moduli with the
+ *      thermal load in it (csrc/lsm_elastic.hip; tests/_thermo_ref.py restates every operation).  The setting is the
+ *      stress recovery's: the corners b of a cell C, c_j, lambda, mu, E_C, and tr_C(v) = G_00 + G_11 (+ G_22), the cell-mean divergence
+ *      of a displacement v, formed exactly as there.  Everything is fp64 without contraction; every sum starts from +0 and runs in the
+ *      stated order; a float32 handle converts its fields to fp64 first and rounds an output field once.  T, u, v and minus are dense
+ *      fields of the handle.
+ *      beta = 3·lambda + 2·mu in 3-D and for LSM_PLANE_STRAIN, 2·lambda + 2·mu for LSM_PLANE_STRESS — 1/(1−2nu) and 1/(1−nu) —
+ *      computed once on the host.  ab_C = alpha_C·beta, alpha_C = alpha_cells[C] (n−1 per axis, axis 0 fastest, fp64 on the device)
+ *      or, with alpha_cells == NULL, the scalar alpha (which is not read otherwise).  theta_C = (sum_b T_b, b ascending)·2^−N − t_ref.
+ *      t_C = ab_C·theta_C, the unit thermal stress; g_C = E_C·t_C.
+ *      lsm_elastic_thermal_load: b_{I,i} = sum over the existing cells C around I, ascending m, of ±(c_i·g_C), + where I is on C's
+ *      upper side along i (bit i of m clear); f = b/m_I is written, N·nn fp64 on the device, component-major: the form
+ *      lsm_elastic_solve takes, as lsm_elastic_stress_load writes it.  It is the consistent Q1 load of the eigenstress
+ *      E·C0:(alpha·theta·I) with theta taken at the centroid, so that A u = b_m + b_th is the thermally loaded state; with uniform E,
+ *      alpha and theta the free expansion u_i = eps·x_i, eps = alpha·theta (3-D, plane stress) or (1+nu)·alpha·theta (plane strain),
+ *      satisfies A u = b_th on every node to rounding.
+ *      lsm_elastic_thermal_stress_cells, lsm_elastic_thermal_stress: lsm_elastic_stress_cells and lsm_elastic_stress with every normal
+ *      unit stress replaced by shat_ii − t_C; in 2-D the out-of-plane one is lambda·tr − t_C for LSM_PLANE_STRAIN and stays 0 for
+ *      LSM_PLANE_STRESS; the shears are unchanged; the von Mises value is the same formula on these values, so that it differs
+ *      from the isothermal one in plane stress only (elsewhere t_C cancels in the three differences, up to rounding).  what:
+ *      LSM_STRESS_STRESS or LSM_STRESS_VON_MISES; LSM_STRESS_STRAIN is refused: the total strain is lsm_elastic_stress's.  The node
+ *      fields follow the stress recovery's rule.
+ *      lsm_elastic_thermal_source: q_I = (sum over the existing cells around I, ascending, of E_C·(ab_C·tr_C(v)))/(their number),
+ *      nn fp64 on the device.  m_I·q_I = d(v·b_th)/dT_I: with the elastic adjoint v (A v = b_l, zero on the fixed components) it is the
+ *      source lsm_elliptic_solve takes for the heat adjoint w.
+ *      lsm_elastic_thermal_sensitivity: z_C = E_C·(t_C·tr_C(v) − q_C), q_C = sum_r u_r·(sum_s K0[r,s]·v_s) in
+ *      lsm_elastic_energy_mutual's order; d_I = (sum of z_C over the existing cells around I, ascending)/(their number) − minus_I, minus
+ *      a dense field converted to fp64, or NULL (nothing is subtracted), rounded once into the dense field g_out.  z_C is
+ *      E_C·dJ'/dE_C, exact for the discrete problem, for J' = sum b_l·u, the state A u = b_m + b_th(T) and the adjoint v, prescribed
+ *      non-zero displacements included.  With minus = lsm_elliptic_energy_mutual(T, w) of the heat state and its adjoint, d is the
+ *      integrand of the shape derivative of l·u in the library's convention, for the coupled problem in which one phi gives both the
+ *      conductivity and the modulus.  With alpha = 0 it is −lsm_elastic_energy_mutual bit for bit (for a finite T).
+ *      LSM_ERR_INVALID without running anything: a missing or repeated field (within u, within v; T one of u's or v's), an output that
+ *      is missing or one of the inputs, a non-finite t_ref, a non-finite scalar alpha where it is read, a `what` not listed above.  A
+ *      non-finite T, u, v or alpha cell propagates.  The calls use the object's scratch vectors as the stress recovery does (only
+ *      lsm_elastic_thermal_stress writes them): none must run concurrently with a solve of the object or of its modes, and the results
+ *      of a later solve are unaffected. */
+int lsm_elastic_thermal_load(LsmElastic* s, const void* T, double t_ref, double alpha, const double* alpha_cells, double* f_out);
+int lsm_elastic_thermal_stress_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* T, double t_ref, double alpha,
+                                     const double* alpha_cells, int what, double* out);
+int lsm_elastic_thermal_stress(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* T, double t_ref, double alpha,
+                               const double* alpha_cells, int what, void* o0, void* o1, void* o2, void* o3, void* o4, void* o5);
+int lsm_elastic_thermal_source(LsmElastic* s, const void* v0, const void* v1, const void* v2, double alpha, const double* alpha_cells, double* q_out);
+int lsm_elastic_thermal_sensitivity(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* v0, const void* v1, const void* v2,
+                                    const void* T, double t_ref, double alpha, const double* alpha_cells, const void* minus, void* g_out);
+
 /* ---- volume_mesh(ϕ, level): the interior {ϕ < level} as a body-fitted simplicial mesh — the splitting phase of
  *      mmg2d_O3 / mmg3d_O3 -ls that export_volume_mesh (ext/MMGVolumeExt.jl) runs over the Kuhn triangulation of the grid,
  *      without the remesher.  Every simplex of the Freudenthal subdivision (lsm_iso_*'s) that the level crosses is split at

@@ -979,6 +979,52 @@ function topological_derivative!(g::ROCMeshField, K, u)
     return g
 end
 
+# Thermoelastic coupling on an elasticity_operator K (include/lsm.h, lsm_elastic_thermal_*): T a temperature field, t_ref the stress-free
+# temperature, alpha the expansion coefficient — a number, or a ROCArray{Float64} of prod(n .- 1) cell values.
+_alpha(alpha::Real) = (Float64(alpha), Ptr{Float64}(C_NULL))
+_alpha(alpha) = (0.0, pointer(alpha))
+
+# the load of the eigenstress E·C₀:(α(T − t_ref)I) as elasticity_solve!'s f (a ROCArray{Float64} of N·nn values)
+function thermal_load!(f, K, T::ROCMeshField, t_ref, alpha)
+    a = _alpha(alpha)
+    _check(K.h.ptr, ccall((:lsm_elastic_thermal_load, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+        K.op, pointer(T.buf), t_ref, a[1], a[2], pointer(f)), "lsm_elastic_thermal_load")
+end
+
+# the stress recovery with the thermal strain taken off (`what`: LSM_STRESS_STRESS or LSM_STRESS_VON_MISES): the cell arrays, and the
+# node fields into the tuple `out`.  The von Mises stress differs from the isothermal one in plane stress only.
+function thermal_stress_cells!(a, K, u, T::ROCMeshField, t_ref, alpha, what)
+    p, al = _u3(u), _alpha(alpha)
+    _check(K.h.ptr, ccall((:lsm_elastic_thermal_stress_cells, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Cint, Ptr{Float64}),
+        K.op, p[1], p[2], p[3], pointer(T.buf), t_ref, al[1], al[2], what, pointer(a)), "lsm_elastic_thermal_stress_cells")
+end
+function thermal_stress_fields!(out, K, u, T::ROCMeshField, t_ref, alpha, what)
+    p, al = _u3(u), _alpha(alpha)
+    o = ntuple(k -> k <= length(out) ? pointer(out[k].buf) : C_NULL, 6)
+    _check(K.h.ptr, ccall((:lsm_elastic_thermal_stress, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        K.op, p[1], p[2], p[3], pointer(T.buf), t_ref, al[1], al[2], what, o[1], o[2], o[3], o[4], o[5], o[6]), "lsm_elastic_thermal_stress")
+end
+
+# the source of the heat adjoint from the elastic adjoint v (N fields), as elliptic_solve!'s f (a ROCArray{Float64} of nn values)
+function thermal_source!(q, K, v, alpha)
+    p, al = _u3(v), _alpha(alpha)
+    _check(K.h.ptr, ccall((:lsm_elastic_thermal_source, libhiplsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Float64}, Ptr{Float64}),
+        K.op, p[1], p[2], p[3], al[1], al[2], pointer(q)), "lsm_elastic_thermal_source")
+end
+
+# the sensitivity of l·u into the field g from the state u, the elastic adjoint v and T; `minus` (a field, or nothing) is subtracted:
+# the mutual energy density of the heat state and its adjoint when the temperature depends on the design
+function thermal_sensitivity!(g::ROCMeshField, K, u, v, T::ROCMeshField, t_ref, alpha; minus = nothing)
+    p, q, al = _u3(u), _u3(v), _alpha(alpha)
+    m = minus === nothing ? C_NULL : pointer(minus.buf)
+    _check(K.h.ptr, ccall((:lsm_elastic_thermal_sensitivity, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+        K.op, p[1], p[2], p[3], q[1], q[2], q[3], pointer(T.buf), t_ref, al[1], al[2], m, pointer(g.buf)), "lsm_elastic_thermal_sensitivity")
+    return g
+end
+
 # Nucleation (include/lsm.h, lsm_nucleate_*).  find_nucleation_sites: the nodes where t < threshold and ϕ ≤ level − clearance whose
 # (value, linear index) is the smallest among such nodes within ceil(spacing/h) nodes along every axis; returns the 0-based linear
 # indices (ascending, on the device) and t at them.  punch!: a ball of `radius` removed around each of the 0-based linear node

@@ -19,7 +19,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
                   components, remove_components_, prune_, Components, nucleate_, find_nucleation_sites, Nucleation,
                   elliptic_solve, regularize_, face_mask, EllipticOperator, EllipticSolution,
                   elliptic_solve_many, EllipticMultiSolution, elasticity_solve, elasticity_solve_many, ElasticityOperator, ElasticitySolution, ElasticityMultiSolution, elasticity_modes, ElasticityModes, elliptic_modes, EllipticModes,
-                  StressSensitivity,
+                  StressSensitivity, Thermoelastic, ThermoelasticSolution, ThermoelasticSensitivity, thermoelastic_solve,
                   homogenize, Homogenization, homogenize_conductivity, ConductivityHomogenization)
 
 __all__ = [
@@ -36,5 +36,6 @@ __all__ = [
     "components", "remove_components_", "prune_", "Components", "nucleate_", "find_nucleation_sites", "Nucleation",
     "elliptic_solve", "regularize_", "face_mask", "EllipticOperator", "EllipticSolution",
     "elliptic_solve_many", "EllipticMultiSolution", "elasticity_solve", "elasticity_solve_many", "ElasticityOperator", "ElasticitySolution", "ElasticityMultiSolution", "elasticity_modes", "ElasticityModes", "elliptic_modes", "EllipticModes", "StressSensitivity",
+    "Thermoelastic", "ThermoelasticSolution", "ThermoelasticSensitivity", "thermoelastic_solve",
     "homogenize", "Homogenization", "homogenize_conductivity", "ConductivityHomogenization",
 ]

@@ -235,6 +235,14 @@ _SIGS = [
                                                  C.c_double, C.c_void_p]),
     ("lsm_elastic_topo_cells", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_elastic_topo", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_thermal_load", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_thermal_stress_cells", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int,
+                                                   C.c_void_p]),
+    ("lsm_elastic_thermal_stress", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_thermal_source", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    ("lsm_elastic_thermal_sensitivity", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                  C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("lsm_nucleate_create", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_int64)]),
     ("lsm_nucleate_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

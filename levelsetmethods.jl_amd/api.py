@@ -3536,6 +3536,157 @@ def elasticity_solve_many(phi_or_eq, fs, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3
         raise
 
 
+# ----------------------------------------------------------------------------- thermoelastic coupling (heat state → thermal load → structure)
+
+class ThermoelasticSensitivity:
+    """ThermoelasticSolution.sensitivity's result: `value` (∏h·Σ b_l·u, compliance()'s scaling), `field` (the ROCMeshField d: the integrand
+    of the shape derivative of l·u in energy_density()'s convention), `adjoint` (the ElasticitySolution of A v = b_l), `heat_adjoint`
+    (the EllipticSolution w of the heat adjoint; None when T was given), `iterations` and `heat_iterations` of the two adjoint solves."""
+
+    def __init__(self, value, field, adjoint, heat_adjoint, iterations, heat_iterations):
+        self.value, self.field, self.adjoint, self.heat_adjoint = float(value), field, adjoint, heat_adjoint
+        self.iterations, self.heat_iterations = int(iterations), int(heat_iterations)
+
+
+class ThermoelasticSolution:
+    """Thermoelastic.solve's result: `temperature` (the EllipticSolution of the heat state; None when T was given), `T` (the temperature
+    ROCMeshField), `displacement` (the ElasticitySolution of A u = b_m + b_th(T)), `coupling` (the Thermoelastic).  stress() and
+    von_mises() are ElasticitySolution's with the thermal strain taken off: every normal stress loses E_C·α_C·β·θ_C (β = 1/(1−2ν), or
+    1/(1−ν) in plane stress), the out-of-plane one of plane strain included; the shears and the strain are the displacement's.  The
+    von Mises stress therefore differs from displacement.von_mises() in plane stress only.  sensitivity(l) → ThermoelasticSensitivity."""
+
+    def __init__(self, coupling, temperature, T, displacement):
+        self.coupling, self.temperature, self.T, self.displacement = coupling, temperature, T, displacement
+
+    def _stress_fields(self, what, count):
+        c, u = self.coupling, self.displacement.u
+        op = c.elastic
+        out = tuple(ROCMeshField(op.backend, u[0].mesh, u[0].bcs) for _ in range(count))
+        op.backend.elastic_thermal_stress(op._handle(), [x.buf for x in u], self.T.buf, c.T_ref, c._alpha, what, [x.buf for x in out])
+        return out
+
+    def stress(self):
+        """the stress E_C·(C₀:ε − α_C·β·θ_C·I) as N(N+1)/2 ROCMeshFields in Voigt order"""
+        N = self.coupling.elastic.ndim
+        return self._stress_fields(L.STRESS_STRESS, N * (N + 1) // 2)
+
+    def von_mises(self):
+        """the von Mises stress of stress() (with the out-of-plane normal stress in plane strain) as one ROCMeshField"""
+        return self._stress_fields(L.STRESS_VON_MISES, 1)[0]
+
+    def sensitivity(self, l, rtol=1e-8, max_iters=500):
+        """The objective l·u (l in any form ElasticityOperator.solve takes a load) and its sensitivity for the coupled problem in which one
+        ϕ gives both the conductivity and the modulus: the elastic adjoint A v = b_l (zero on the fixed components),
+        the heat adjoint w whose source is ∂(v·b_th)/∂T (zero on the Dirichlet nodes), then one fused pass:
+        d = mean over the cells around a node of E_C·(t_C·tr_C(v) − q_C(u, v)) − a∇T·∇w — energy_density()'s convention, a
+        NormalMotionTerm speed through coeff.set_values.  When T was given the temperature does not depend on the design: no heat
+        adjoint is run and nothing is subtracted.  Returns a ThermoelasticSensitivity."""
+        c = self.coupling
+        eop, hop = c.elastic, c.heat
+        rtol = float(rtol)
+        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
+            raise ValueError("thermoelastic sensitivity: rtol must be positive and finite, max_iters at least 1")
+        b, h = eop.backend, eop._handle()
+        ubufs = [x.buf for x in self.displacement.u]
+        ld = eop._load(l)
+        v = eop._fields(None, fixed="zero")
+        vbufs = [x.buf for x in v]
+        it, rel = b.elastic_solve(h, ld, vbufs, rtol, int(max_iters))
+        adjoint = ElasticitySolution(eop, v, ld, it, rel)
+        value = b.elastic_compliance(h, ld, ubufs)
+        heat_adjoint, minus, itw = None, None, 0
+        if self.temperature is not None:
+            src = b.elastic_thermal_source(h, vbufs, c._alpha)
+            w = hop._field(None, homogeneous=True)
+            itw, relw = b.elliptic_solve(hop._handle(), src, w.buf, rtol, int(max_iters))
+            heat_adjoint = EllipticSolution(hop, w, src, itw, relw)
+            minus = self.temperature.mutual_energy_density(heat_adjoint)
+        field = ROCMeshField(b, self.T.mesh, self.T.bcs)
+        b.elastic_thermal_sensitivity(h, ubufs, vbufs, self.T.buf, c.T_ref, c._alpha, None if minus is None else minus.buf, field.buf)
+        return ThermoelasticSensitivity(value, field, adjoint, heat_adjoint, it, itw)
+
+
+class Thermoelastic:
+    """The coupling of a heat problem and a structure on one grid: `heat` an EllipticOperator, `elastic` an
+    ElasticityOperator of the same backend and mesh (both built from the one ϕ), `alpha` the expansion coefficient (a scalar or a
+    cell array of shape n − 1), `T_ref` the stress-free temperature.  thermal_load(T) → the load of the eigenstress E·C₀:(α(T − T_ref)I)
+    as ElasticityOperator.solve takes it; solve(q, f) → ThermoelasticSolution.  The operators are borrowed; close() closes both."""
+
+    def __init__(self, heat_op, elastic_op, *, alpha, T_ref=0.0):
+        what = "Thermoelastic"
+        if not isinstance(heat_op, EllipticOperator) or not isinstance(elastic_op, ElasticityOperator):
+            raise TypeError(f"{what} takes an EllipticOperator and an ElasticityOperator")
+        if heat_op.backend is not elastic_op.backend:
+            raise ValueError(f"{what}: the two operators must share a backend (build both from the same ϕ)")
+        if tuple(int(m) for m in heat_op.mesh.n) != tuple(int(m) for m in elastic_op.mesh.n) or \
+                tuple(heat_op.mesh.meshsize()) != tuple(elastic_op.mesh.meshsize()):
+            raise ValueError(f"{what}: the two operators must share a mesh")
+        T_ref = float(T_ref)
+        if not math.isfinite(T_ref):
+            raise ValueError(f"{what}: T_ref must be finite")
+        b = elastic_op.backend
+        cells = tuple(int(m) - 1 for m in elastic_op.mesh.n)
+        if b.torch.is_tensor(alpha):
+            self._alpha = b.node_array(alpha, "alpha", cells)
+        else:
+            a = np.asarray(alpha, dtype=np.float64)
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"{what}: alpha must be finite")
+            if a.ndim and a.shape != cells:
+                raise ValueError(f"{what}: alpha has shape {a.shape}, the grid has {cells} cells")
+            self._alpha = b.node_array(a, "alpha", cells) if a.ndim else float(a)
+        self.heat, self.elastic, self.T_ref, self.backend = heat_op, elastic_op, T_ref, b
+
+    def _temperature(self, T):
+        """T as a ROCMeshField of the operators' backend: one is taken as it is, a scalar / host array / MeshField is uploaded"""
+        b = self.backend
+        if isinstance(T, EllipticSolution):
+            T = T.u
+        if isinstance(T, ROCMeshField):
+            if T.backend is not b or isinstance(T, ROCNarrowBandMeshField):
+                raise ValueError("Thermoelastic: T must be a dense field of the operators' backend")
+            return T
+        out = ROCMeshField(b, self.elastic.mesh, self.elastic.bcs)
+        out.copy_(np.broadcast_to(_host_values(T), tuple(int(m) for m in self.elastic.mesh.n)))
+        return out
+
+    def thermal_load(self, T):
+        """f_th as a flat float64 device tensor, component-major: elastic.solve(f_th) is the structure under the thermal load alone"""
+        return self.backend.elastic_thermal_load(self.elastic._handle(), self._temperature(T).buf, self.T_ref, self._alpha)
+
+    def solve(self, q=None, f=None, *, T=None, rtol=1e-8, max_iters=500):
+        """The heat state heat.solve(q) (or the given temperature T: a ROCMeshField, a scalar or a host array), its thermal load added
+        to the mechanical load f (none without one) on the device, then the structure: bit for bit
+        elastic.solve(f + thermal_load(T)).  Returns a ThermoelasticSolution."""
+        if (q is None) == (T is None):
+            raise ValueError("Thermoelastic.solve takes either the heat source q or the temperature T")
+        temperature = None if T is not None else self.heat.solve(q, rtol=rtol, max_iters=max_iters)
+        Tf = self._temperature(T if T is not None else temperature.u)
+        fth = self.thermal_load(Tf)
+        load = fth if f is None else self.elastic._load(f) + fth
+        return ThermoelasticSolution(self, temperature, Tf, self.elastic.solve(load, rtol=rtol, max_iters=max_iters))
+
+    def close(self):
+        self.heat.close()
+        self.elastic.close()
+
+
+def thermoelastic_solve(phi_or_eq, q, f=None, *, alpha, T_ref=0.0, heat=None, elastic=None, rtol=1e-8, max_iters=500):
+    """Thermoelastic.solve in one call: `heat` and `elastic` are the keyword arguments of EllipticOperator and ElasticityOperator
+    (dirichlet=, a_in=, E_in=, nu=, plane=, …) for the one ϕ; q the heat source, f the mechanical load (or None), alpha the expansion
+    coefficient, T_ref the stress-free temperature.  Returns a ThermoelasticSolution; its .coupling.close() releases both operators."""
+    hop = EllipticOperator(phi_or_eq, **(heat or {}))
+    eop = None
+    try:
+        eop = ElasticityOperator(phi_or_eq, **(elastic or {}))
+        return Thermoelastic(hop, eop, alpha=alpha, T_ref=T_ref).solve(q, f, rtol=rtol, max_iters=max_iters)
+    except BaseException:
+        hop.close()
+        if eop is not None:
+            eop.close()
+        raise
+
+
 # ----------------------------------------------------------------------------- homogenisation (ϕ as one cell of a periodic material)
 
 class Homogenization:

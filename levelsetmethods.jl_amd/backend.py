@@ -849,6 +849,39 @@ class HipBackend:
     def elastic_topo(self, obj, u, out):
         L.check(self.h, self.lib.lsm_elastic_topo(obj, *self._u3(u), self.ptr(out)), "lsm_elastic_topo")
 
+    # ---- thermoelastic coupling (lsm_elastic_thermal_*): T a padded field; alpha a float, or a flat float64 device tensor over the cells
+    def _alpha(self, alpha):
+        """(the scalar, the cell array's pointer)"""
+        return (0.0, self.ptr(alpha)) if self.torch.is_tensor(alpha) else (float(alpha), None)
+
+    def elastic_thermal_load(self, obj, T, t_ref, alpha):
+        out = self.torch.empty(self.ndim * int(np.prod(self.local_shape())), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_thermal_load(obj, self.ptr(T), float(t_ref), *self._alpha(alpha), self.ptr(out)), "lsm_elastic_thermal_load")
+        return out
+
+    def elastic_thermal_stress_cells(self, obj, u, T, t_ref, alpha, what):
+        """the component-major fp64 cell arrays as one flat device tensor"""
+        N = self.ndim
+        ncomp = 1 if what == L.STRESS_VON_MISES else N * (N + 1) // 2
+        out = self.torch.empty(ncomp * int(np.prod([m - 1 for m in self.local_shape()])), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_thermal_stress_cells(obj, *self._u3(u), self.ptr(T), float(t_ref), *self._alpha(alpha), int(what), self.ptr(out)),
+                "lsm_elastic_thermal_stress_cells")
+        return out
+
+    def elastic_thermal_stress(self, obj, u, T, t_ref, alpha, what, outs):
+        o = [self.ptr(t) for t in outs] + [None] * (6 - len(outs))
+        L.check(self.h, self.lib.lsm_elastic_thermal_stress(obj, *self._u3(u), self.ptr(T), float(t_ref), *self._alpha(alpha), int(what), *o),
+                "lsm_elastic_thermal_stress")
+
+    def elastic_thermal_source(self, obj, v, alpha):
+        out = self.torch.empty(int(np.prod(self.local_shape())), dtype=self.torch.float64, device=self.device)
+        L.check(self.h, self.lib.lsm_elastic_thermal_source(obj, *self._u3(v), *self._alpha(alpha), self.ptr(out)), "lsm_elastic_thermal_source")
+        return out
+
+    def elastic_thermal_sensitivity(self, obj, u, v, T, t_ref, alpha, minus, g):
+        L.check(self.h, self.lib.lsm_elastic_thermal_sensitivity(obj, *self._u3(u), *self._u3(v), self.ptr(T), float(t_ref), *self._alpha(alpha),
+                                                                 None if minus is None else self.ptr(minus), self.ptr(g)), "lsm_elastic_thermal_sensitivity")
+
     # ---- vibration modes (lsm_elastic_modes_*): the modes object borrows the elastic object
     def modes_create(self, obj, phi, level, rho_in, rho_out, rho_cells, m):
         out = C.c_void_p()

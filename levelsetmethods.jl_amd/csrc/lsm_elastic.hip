@@ -1583,3 +1583,293 @@ int lsm_elastic_topo(LsmElastic* s, const void* u0, const void* u1, const void* 
     LSM_HIP(s->h, hipGetLastError());
     return LSM_OK;
 }
+
+// ======================================================================================================================================
+// Thermoelastic coupling: a temperature field as a load on the structure, the stress with the thermal strain taken off, the elastic
+// adjoint carried back into the heat problem, and the sensitivity of l·u to the cell moduli with the thermal load in it.
+// include/lsm.h ("thermoelastic coupling") is the normative text, tests/_thermo_ref.py restates it, DESIGN.md §7.29.  The setting, SsMat,
+// the gather rule and the launch caps are the stress recovery's.
+//
+// The load, the source and the sensitivity are node-owned gathers in one launch each, as es_energy_mutual_kernel is: a thread forms θ,
+// tr and q of its ≤ 2^N cells from its 3^N neighbourhood, cell by cell in ascending m, without atomics and without a cell array.  The
+// stress pair is the stress recovery's two passes with t_C taken off the normal unit stresses.
+namespace lsm {
+
+// β = 3λ + 2μ (3-D, plane strain) or 2λ + 2μ (plane stress); alpha: the scalar expansion coefficient, used where cells == NULL
+struct ThMat { double beta, alpha, tref; const double* cells; };
+
+static ThMat th_mat(const ElasticObject& o, double t_ref, double alpha, const double* alpha_cells) {
+    ThMat H;
+    H.beta = (o.N == 2 && o.plane == LSM_PLANE_STRESS ? 2.0 : 3.0) * o.lam + 2.0 * o.mu;
+    H.alpha = alpha; H.tref = t_ref; H.cells = alpha_cells;
+    return H;
+}
+
+// the padded offset of the lowest corner of cell m around the node at `at`, and of corner b from there
+template <int N>
+__device__ __forceinline__ long long th_cell0(const MgField& F, long long at, int m) {
+    return at + ((m & 1) - 1) + (((m >> 1) & 1) - 1) * F.s1 + (N > 2 ? (((m >> 2) & 1) - 1) * F.s2 : 0);
+}
+template <int N>
+__device__ __forceinline__ long long th_corner(const MgField& F, int b) {
+    return (b & 1) + ((b >> 1) & 1) * F.s1 + (N > 2 ? ((b >> 2) & 1) * F.s2 : 0);
+}
+// t_C = ab_C·θ_C, ab_C = α_C·β, θ_C = (Σ_b T_b, b ascending from +0)·2^−N − t_ref; c0: the cell's lowest corner
+template <int N>
+__device__ __forceinline__ double th_unit(const MgField& F, const void* __restrict__ T, long long c0, int ci, const ThMat& H) {
+    double sum = 0.0;
+#pragma unroll
+    for (int b = 0; b < (1 << N); ++b) sum = sum + ld_val(T, c0 + th_corner<N>(F, b), F.f32);
+    const double theta = sum * (N == 2 ? 0.25 : 0.125) - H.tref;
+    const double ab = (H.cells ? H.cells[ci] : H.alpha) * H.beta;
+    return ab * theta;
+}
+// tr_C(v) = G_00 + G_11 (+ G_22) of the corner values vc[b·N + i], formed as ss_unit forms it
+template <int N>
+__device__ __forceinline__ double th_trace(const double vc[(1 << N) * N], const SsMat& P) {
+    double G[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double d = 0.0;
+#pragma unroll
+        for (int b = 0; b < (1 << N); ++b) d = d + (((b >> i) & 1) ? vc[b * N + i] : -vc[b * N + i]);
+        G[i] = d * P.c[i];
+    }
+    double tr = G[0] + G[1];
+    if (N > 2) tr = tr + G[N - 1];
+    return tr;
+}
+
+// ---- f_{I,i} = b_{I,i}/m_I, b_{I,i} = Σ over the existing cells, ascending, from +0, of ±(c_i·g_C), g_C = E_C·t_C: + where I is on the cell's
+// upper side along i (bit i of m clear)
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) th_load_kernel(EsLevel L, MgField F, const void* __restrict__ T, SsMat P, ThMat H, double* __restrict__ f_out) {
+    MG_LOOP(id, L.nn) {
+        int I[3], ci[1 << N];
+        bool in[1 << N];
+        mg_coords<N>(L.n, id, I);
+        ss_around<N>(L, I, ci, in);
+        const long long at = mg_padded(F, I);
+        double b[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) b[i] = 0.0;
+#pragma unroll
+        for (int m = 0; m < (1 << N); ++m) {
+            if (!in[m]) continue;
+            const double g = L.E[ci[m]] * th_unit<N>(F, T, th_cell0<N>(F, at, m), ci[m], H);
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                const double t = P.c[i] * g;
+                b[i] = b[i] + (((m >> i) & 1) ? -t : t);
+            }
+        }
+        const double mass = mg_mass<N>(L.n, I);
+#pragma unroll
+        for (int i = 0; i < N; ++i) f_out[(size_t)i * L.nn + id] = b[i] / mass;
+    }
+}
+
+// ---- the stress recovery's cell arrays with t_C off every normal unit stress (the out-of-plane one of plane strain included; plane
+// stress keeps its 0): the stress E_C·(ŝ − t, τ̂) or s_C = E_C·sqrt(v2) of those values
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) th_cells_kernel(EsLevel L, MgField F, EsU U, const void* __restrict__ T, SsMat P, ThMat H, int what, int nc,
+                                                              double* __restrict__ out) {
+    constexpr int M = N * (N + 1) / 2;
+    MG_LOOP(ci, nc) {
+        int C[3];
+        ss_cell_coords<N>(L.n, ci, C);
+        double uc[(1 << N) * N], e[M], sn[3], tau[M - N];
+        ss_corners<N>(F, U, C, uc);
+        ss_unit<N>(uc, P, e, sn, tau);
+        const double t = th_unit<N>(F, T, mg_padded(F, C), ci, H);
+#pragma unroll
+        for (int k = 0; k < N; ++k) sn[k] = sn[k] - t;
+        if (N == 2 && P.strain) sn[2] = sn[2] - t;
+        const double E = L.E[ci];
+        if (what == LSM_STRESS_STRESS) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) out[(size_t)k * nc + ci] = E * sn[k];
+#pragma unroll
+            for (int k = 0; k < M - N; ++k) out[(size_t)(N + k) * nc + ci] = E * tau[k];
+        } else {
+            out[ci] = E * sqrt(ss_v2<N>(sn, tau));
+        }
+    }
+}
+
+// ---- q_I = (Σ over the existing cells, ascending, from +0, of E_C·(ab_C·tr_C(v)))/(their number), nn fp64
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) th_source_kernel(EsLevel L, MgField F, EsU V, SsMat P, ThMat H, double* __restrict__ q_out) {
+    constexpr int NC = 1 << N, R = NC * N;
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
+        double acc = 0.0, cnt = 0.0;
+#pragma unroll 1
+        for (int m = 0; m < NC; ++m) {
+            bool in;
+            const double E = es_cell<N>(L, I, m, in);
+            if (!in) continue;
+            int C[3] = {0, 0, 0};
+#pragma unroll
+            for (int d = 0; d < N; ++d) C[d] = I[d] - 1 + ((m >> d) & 1);
+            const long long c0 = th_cell0<N>(F, at, m);
+            double vc[R];
+#pragma unroll
+            for (int b = 0; b < NC; ++b)
+#pragma unroll
+                for (int j = 0; j < N; ++j) vc[b * N + j] = ld_val(V.p[j], c0 + th_corner<N>(F, b), F.f32);
+            const double ab = (H.cells ? H.cells[mg_cell_index<N>(L.n, C)] : H.alpha) * H.beta;
+            acc = acc + E * (ab * th_trace<N>(vc, P));
+            cnt = cnt + 1.0;
+        }
+        q_out[id] = acc / cnt;
+    }
+}
+
+// ---- d_I = (Σ over the existing cells, ascending, from +0, of z_C)/(their number) − minus_I, z_C = E_C·(t_C·tr_C(v) − q_C), q_C the bilinear
+// form in es_energy_mutual_kernel's order (u outside, v inside); minus == NULL: nothing is subtracted
+template <int N>
+__global__ void __launch_bounds__(MG_THREADS) th_sens_kernel(EsLevel L, MgField F, EsU U, EsU V, const void* __restrict__ T, SsMat P, ThMat H,
+                                                             const void* __restrict__ minus, void* __restrict__ g_out) {
+    constexpr int NC = 1 << N, R = NC * N;
+    const double* __restrict__ K = L.K;
+    MG_LOOP(id, L.nn) {
+        int I[3];
+        mg_coords<N>(L.n, id, I);
+        const long long at = mg_padded(F, I);
+        double acc = 0.0, cnt = 0.0;
+#pragma unroll 1
+        for (int m = 0; m < NC; ++m) {
+            bool in;
+            const double E = es_cell<N>(L, I, m, in);
+            if (!in) continue;
+            int C[3] = {0, 0, 0};
+#pragma unroll
+            for (int d = 0; d < N; ++d) C[d] = I[d] - 1 + ((m >> d) & 1);
+            const long long c0 = th_cell0<N>(F, at, m);
+            double uc[R], vc[R];
+#pragma unroll
+            for (int b = 0; b < NC; ++b) {
+                const long long o = th_corner<N>(F, b);
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    uc[b * N + j] = ld_val(U.p[j], c0 + o, F.f32);
+                    vc[b * N + j] = ld_val(V.p[j], c0 + o, F.f32);
+                }
+            }
+            // the thermal term first: with it after the bilinear form the scheduler issues all of K0's scalar loads ahead of the block and
+            // spills them to VGPR lanes (1169 in 3-D), which more than doubles the pass
+            const double tt = th_unit<N>(F, T, c0, mg_cell_index<N>(L.n, C), H) * th_trace<N>(vc, P);
+            double q = 0.0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int s = 0; s < R; ++s) t = t + K[r * R + s] * vc[s];
+                q = q + uc[r] * t;
+            }
+            acc = acc + E * (tt - q);
+            cnt = cnt + 1.0;
+        }
+        double d = acc / cnt;
+        if (minus) d = d - ld_val(minus, at, F.f32);
+        st_val(g_out, at, F.f32, d);
+    }
+}
+
+// the refusals the five calls share: a temperature field, a finite reference temperature, a finite scalar alpha where it is used
+static bool th_args(const void* T, double t_ref, double alpha, const double* alpha_cells) {
+    return T && std::isfinite(t_ref) && (alpha_cells || std::isfinite(alpha));
+}
+
+}  // namespace lsm
+
+int lsm_elastic_thermal_load(LsmElastic* s, const void* T, double t_ref, double alpha, const double* alpha_cells, double* f_out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    if (!th_args(T, t_ref, alpha, alpha_cells)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_load: T must be given, t_ref and a scalar alpha must be finite");
+    if (!f_out || (const void*)f_out == T || (const void*)f_out == (const void*)alpha_cells)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_load: f_out must be an array of its own");
+    const EsLevel& L = o.lev[0];
+    MG_LAUNCH(o.N, th_load_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, o.F, T, ss_mat(o), th_mat(o, t_ref, alpha, alpha_cells), f_out);
+    LSM_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_thermal_stress_cells(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* T, double t_ref, double alpha,
+                                     const double* alpha_cells, int what, double* out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (what != LSM_STRESS_STRESS && what != LSM_STRESS_VON_MISES)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_stress_cells: unknown quantity (LSM_STRESS_STRESS or LSM_STRESS_VON_MISES: the total strain is lsm_elastic_stress_cells')");
+    if (!th_args(T, t_ref, alpha, alpha_cells))
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_stress_cells: T must be given, t_ref and a scalar alpha must be finite");
+    if (!es_fields(o.N, u0, u1, u2, U) || T == u0 || T == u1 || (o.N > 2 && T == u2) || !out || out == u0 || out == u1 || out == u2 || (const void*)out == T ||
+        (const void*)out == (const void*)alpha_cells)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_stress_cells: the N fields of u and T must be distinct fields, out an array of its own");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    MG_LAUNCH(o.N, th_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, s->h->stream, L, o.F, U, T, ss_mat(o), th_mat(o, t_ref, alpha, alpha_cells), what, nc, out);
+    LSM_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_thermal_stress(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* T, double t_ref, double alpha, const double* alpha_cells,
+                               int what, void* o0, void* o1, void* o2, void* o3, void* o4, void* o5) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U;
+    if (what != LSM_STRESS_STRESS && what != LSM_STRESS_VON_MISES)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_stress: unknown quantity (LSM_STRESS_STRESS or LSM_STRESS_VON_MISES: the total strain is lsm_elastic_stress')");
+    if (!th_args(T, t_ref, alpha, alpha_cells)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_stress: T must be given, t_ref and a scalar alpha must be finite");
+    const int ncomp = what == LSM_STRESS_VON_MISES ? 1 : o.N * (o.N + 1) / 2;
+    SsOut O = {{o0, o1, o2, o3, o4, o5}};
+    bool ok = es_fields(o.N, u0, u1, u2, U) && T != u0 && T != u1 && !(o.N > 2 && T == u2);
+    for (int k = 0; k < ncomp; ++k) {
+        ok = ok && O.p[k] && O.p[k] != u0 && O.p[k] != u1 && O.p[k] != u2 && O.p[k] != T && O.p[k] != (const void*)alpha_cells;
+        for (int l = 0; l < k; ++l) ok = ok && O.p[k] != O.p[l];
+    }
+    if (!ok) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_stress: the components of u, T and the output fields must be distinct fields");
+    const EsLevel& L = o.lev[0];
+    const int nc = (int)mg_ncells(o.N, L);
+    hipStream_t st = s->h->stream;
+    double* cell = o.xa[0];      // ≤ 6·(cells) of the 6·N·nn scratch doubles
+    MG_LAUNCH(o.N, th_cells_kernel, dim3(mg_blocks(nc)), MG_THREADS, st, L, o.F, U, T, ss_mat(o), th_mat(o, t_ref, alpha, alpha_cells), what, nc, cell);
+    MG_LAUNCH(o.N, ss_gather_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, st, L, o.F, (const double*)cell, nc, ncomp, 1.0, O);
+    LSM_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_thermal_source(LsmElastic* s, const void* v0, const void* v1, const void* v2, double alpha, const double* alpha_cells, double* q_out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU V;
+    if (!alpha_cells && !std::isfinite(alpha)) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_source: a scalar alpha must be finite");
+    if (!es_fields(o.N, v0, v1, v2, V) || !q_out || q_out == v0 || q_out == v1 || q_out == v2 || (const void*)q_out == (const void*)alpha_cells)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_source: the N distinct fields of v and an array of its own must be given");
+    const EsLevel& L = o.lev[0];
+    MG_LAUNCH(o.N, th_source_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, o.F, V, ss_mat(o), th_mat(o, 0.0, alpha, alpha_cells), q_out);
+    LSM_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
+
+int lsm_elastic_thermal_sensitivity(LsmElastic* s, const void* u0, const void* u1, const void* u2, const void* v0, const void* v1, const void* v2, const void* T,
+                                    double t_ref, double alpha, const double* alpha_cells, const void* minus, void* g_out) {
+    if (!s) return LSM_ERR_INVALID;
+    ElasticObject& o = *s->o;
+    EsU U, V;
+    if (!th_args(T, t_ref, alpha, alpha_cells))
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_sensitivity: T must be given, t_ref and a scalar alpha must be finite");
+    if (!es_fields(o.N, u0, u1, u2, U) || !es_fields(o.N, v0, v1, v2, V) || !g_out)
+        return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_sensitivity: the components of u, those of v and g_out must be given, distinct within u and within v");
+    bool ok = g_out != T && g_out != minus && g_out != (const void*)alpha_cells;
+    for (int i = 0; i < o.N; ++i) ok = ok && g_out != U.p[i] && g_out != V.p[i] && T != U.p[i] && T != V.p[i];
+    if (!ok) return lsm_fail(s->h, LSM_ERR_INVALID, "lsm_elastic_thermal_sensitivity: T must be none of u's or v's fields, g_out none of the inputs");
+    const EsLevel& L = o.lev[0];
+    MG_LAUNCH(o.N, th_sens_kernel, dim3(mg_blocks(L.nn)), MG_THREADS, s->h->stream, L, o.F, U, V, T, ss_mat(o), th_mat(o, t_ref, alpha, alpha_cells), minus, g_out);
+    LSM_HIP(s->h, hipGetLastError());
+    return LSM_OK;
+}
