@@ -236,6 +236,27 @@ int lsm_advance_rk3(LsmHandle* h, const LsmTerm* terms, int nterms, void* phi, v
 int lsm_advance_i2oe(LsmHandle* h, const LsmTerm* term, void* phi, double tc, double dt, double rtol, int max_iters, int* iters_out,
                      double* rel_residual_out);
 
+/* ---- SemiLagrangian (not in the reference): ONE out-of-place step of a single AdvectionTerm by backward
+ *      characteristics.  Every node I is traced back for dt in index space — trace 1: ξ = W(i − (dt·u(node, tc))/h); trace 2, the
+ *      midpoint rule: ξᵐ = W(i − (½dt·u(node, tc + ½dt))/h), ξ = W(i − (dt·u(ξᵐ, tc + ½dt))/h) — and out[I] is the tensor-product
+ *      Lagrange interpolant of phi at ξ on the centred stencil of 2, 4 or 6 nodes per dimension (order 1, 3, 5), clamped to the
+ *      extrema of the departure cell's 2^N corners when limiter != 0 (Bermejo–Staniforth).  W wraps on an axis that is periodic
+ *      (period n − 1) and clamps to [0, n − 1] on every other axis: a departure point outside the box reads the boundary.  The
+ *      velocity is term->coeff (CONST, ROTATION, SEPARABLE, FIELD — interpolated linearly off the nodes, FIELD as it stands at the
+ *      call); term->scheme is ignored.  A NaN velocity gives a NaN node and never an index outside the cell range.
+ *      phi's ghost layers are filled on entry (all dimensions); the interior of out is written, its ghosts are STALE afterwards.
+ *      Float32 storage: fp64 arithmetic, rounded once on store; both arithmetic modes run the same code and give the same bits.
+ *      stats (may be NULL: the kernels then count nothing; a non-NULL pointer adds one record per workgroup, a small reduction
+ *      behind the launch and a host wait): [0] workgroups that interpolated from the staged tile, [1] workgroups that read global
+ *      memory, [2] the largest |dt·u_d/h_d| of the final trace over the grid — the displacement before W, since |ξ − i| means
+ *      nothing across a wrap — in cells, rounded up (INT64_MAX for an infinite velocity).
+ *      LSM_ERR_INVALID (nothing runs, nothing is written): out == phi or a null pointer; a term other than LSM_TERM_ADVECTION;
+ *      order not 1, 3 or 5; trace not 1 or 2; dt negative or not finite; fewer than 2 nodes in a dimension; a slab handle or one
+ *      with a communicator; an axis periodic on one face only.  With LSM_SEMILAG_STAGE = 2 also when a workgroup's departure box
+ *      does not fit the staged tile (phi's ghosts are filled, out is untouched). */
+int lsm_advance_semilag(LsmHandle* h, const LsmTerm* term, void* phi, void* out, double tc, double dt, int order, int trace, int limiter,
+                        int64_t* stats);
+
 /* ---- multi-GPU: the grid is cut into slabs of the LAST dimension, one handle per slab (lsm_create with an
  *      LsmSlab and LSM_BC_NONE on the faces towards neighbouring ranks — on BOTH faces of every rank when that dimension
  *      is periodic: the ring closes across the wrap, whose period is n-1, src/boundaryconditions.jl:107-119).  After every
@@ -1290,7 +1311,10 @@ int lsm_reinitialize(LsmHandle* h, void* phi, const void* mask, void* work, int 
  *   LSM_SLAB_OVERLAP             1   slab steps update the interface planes first (read when a communicator is attached)
  *   LSM_COMM_TIMEOUT_MS      60000   how long a rank waits for its peers before LSM_ERR_COMM
  *   LSM_LAYOUT_ALIGN             1   rows of the padded layout start on 64-byte lines (environment only: fixed by lsm_create)
- *   LSM_RENDER_SKIP              1   lsm_render_draw: rays step over uniform bricks (0: every lattice sample is loaded; identical pictures) */
+ *   LSM_RENDER_SKIP              1   lsm_render_draw: rays step over uniform bricks (0: every lattice sample is loaded; identical pictures)
+ *   LSM_SEMILAG_STAGE            0   lsm_advance_semilag: the direct gather everywhere (1: workgroups whose departure box fits read the stencils
+ *                                    from LDS, the others from global memory — faster for order 5, not for orders 1 and 3; 2: the same, and
+ *                                    LSM_ERR_INVALID when a box does not fit; 0 .. 2, identical bits) */
 int lsm_set_tuning(LsmHandle* h, const char* name, int value);
 int lsm_get_tuning(const LsmHandle* h, const char* name, int* value);
 

@@ -319,6 +319,30 @@ function LSM._integrate!(ls, ϕ::ROCMeshField, integrator::LSM.SemiImplicitI2OE,
     return nothing
 end
 
+# SemiLagrangian (DESIGN.md §7.30; not in the reference): large advection steps by backward characteristics, one gather pass per
+# step on the device (lsm_advance_semilag).  It runs through the reference's generic step loop: one buffer, one out-of-place step,
+# and the buffers of ϕ and dst change places (nothing on the handle keeps ϕ's pointer between calls).
+Base.@kwdef struct SemiLagrangian <: LSM.TimeIntegrator
+    cfl::Float64 = 4.0
+    order::Int = 3        # degree of the Lagrange interpolant: 1, 3 or 5
+    trace::Int = 2        # 1: Euler, 2: midpoint
+    limiter::Bool = true  # clamp to the departure cell's extrema (Bermejo–Staniforth)
+end
+LSM._describe(::SemiLagrangian) = "SemiLagrangian (backward characteristics, Lagrange interpolation)"
+LSM._alloc_buffers(::SemiLagrangian, ϕ::ROCMeshField) = (copy(ϕ),)
+function LSM._advance!(s::SemiLagrangian, ϕ::ROCMeshField, (dst,), terms, tc, Δt)
+    length(terms) == 1 && only(terms) isa LSM.AdvectionTerm || throw(ArgumentError("SemiLagrangian requires exactly one AdvectionTerm"))
+    ϕ.h.world > 1 && throw(ArgumentError("SemiLagrangian runs on a single device: a slab decomposition is not supported"))
+    s.order in (1, 3, 5) || throw(ArgumentError("SemiLagrangian: order must be 1, 3 or 5, got $(s.order)"))
+    s.trace in (1, 2) || throw(ArgumentError("SemiLagrangian: trace must be 1 or 2, got $(s.trace)"))
+    ts = [_term(only(terms), ϕ, tc)]
+    _check(ϕ.h.ptr, ccall((:lsm_advance_semilag, libhiplsm), Cint,
+        (Ptr{Cvoid}, Ptr{LsmTerm}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Cint, Cint, Cint, Ptr{Int64}),
+        ϕ.h.ptr, ts, pointer(ϕ.buf), pointer(dst.buf), tc, Δt, s.order, s.trace, s.limiter ? 1 : 0, C_NULL), "lsm_advance_semilag")
+    ϕ.buf, dst.buf = dst.buf, ϕ.buf
+    return ϕ
+end
+
 LSM._alloc_buffers(::LSM.ForwardEuler, ϕ::ROCMeshField) = (copy(ϕ),)
 LSM._alloc_buffers(::Union{LSM.RK2, LSM.RK3}, ϕ::ROCMeshField) = (copy(ϕ), copy(ϕ))
 

@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import LsmError, LsmNotConvergedError, build
 from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm, EikonalReinitializationTerm,
                   ExtrapolationBC, ForwardEuler, LazyMeshField, LevelSetEquation, LevelSetTerm, LinearExtrapolationBC, MeshField,
-                  NarrowBandMeshField, NeumannBC, NormalMotionTerm, PeriodicBC, RK2, RK3, RigidRotation, SemiImplicitI2OE, ROCMeshField,
+                  NarrowBandMeshField, NeumannBC, NormalMotionTerm, PeriodicBC, RK2, RK3, RigidRotation, SemiImplicitI2OE, SemiLagrangian, ROCMeshField,
                   ROCNarrowBandMeshField, SeparableCoefficient,
                   SymmetryBC, TimeIntegrator, Upwind, WENO5, current_state, current_time, extend_along_normals_, integrate_, reinitialize_,
                   perimeter, volume, InterpolatedField, NewtonSDF, hausdorff_distance, SideField, curvature, curvature_field, gradient, gradient_field, normal, normal_field,
@@ -25,7 +25,7 @@ from .api import (AdvectionTerm, BoundaryCondition, CartesianGrid, CurvatureTerm
 __all__ = [
     "AdvectionTerm", "BoundaryCondition", "CartesianGrid", "CurvatureTerm", "EikonalReinitializationTerm",
     "ExtrapolationBC", "ForwardEuler", "LazyMeshField", "LevelSetEquation", "LevelSetTerm", "LinearExtrapolationBC", "MeshField",
-    "NarrowBandMeshField", "ROCNarrowBandMeshField", "NeumannBC", "NormalMotionTerm", "PeriodicBC", "RK2", "RK3", "SemiImplicitI2OE",
+    "NarrowBandMeshField", "ROCNarrowBandMeshField", "NeumannBC", "NormalMotionTerm", "PeriodicBC", "RK2", "RK3", "SemiImplicitI2OE", "SemiLagrangian",
     "RigidRotation", "ROCMeshField",
     "SeparableCoefficient", "SymmetryBC", "TimeIntegrator", "Upwind", "WENO5", "current_state", "current_time",
     "integrate_", "vortex_deformation", "volume", "perimeter", "extend_along_normals_", "reinitialize_", "LsmError", "LsmNotConvergedError", "build",

@@ -98,6 +98,8 @@ _SIGS = [
                                   C.c_double, StageHook, C.c_void_p]),
     ("lsm_advance_i2oe", C.c_int, [_H, C.POINTER(LsmTerm), C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
                                    C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("lsm_advance_semilag", C.c_int, [_H, C.POINTER(LsmTerm), C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(C.c_int64)]),
     ("lsm_comm_unique_id", C.c_int, [C.c_void_p]),
     ("lsm_comm_attach_rccl", C.c_int, [_H, C.c_void_p, C.c_int, C.c_int]),
     ("lsm_comm_attach_local", C.c_int, [C.POINTER(_H), C.c_int]),

@@ -988,6 +988,21 @@ class SemiImplicitI2OE(TimeIntegrator):
             raise ValueError("SemiImplicitI2OE: rtol must be positive and max_iters at least 1")
 
 
+class SemiLagrangian(TimeIntegrator):
+    """SemiLagrangian(cfl = 4.0; order = 3, trace = 2, limiter = true) — large advection steps by backward characteristics for one
+    AdvectionTerm on a dense field of a single device (not part of the reference).  Every node is traced back
+    along the velocity for Δt (trace 1: one Euler step; 2: the midpoint rule) and ϕⁿ is read there by the tensor-product Lagrange
+    interpolant of degree `order` (1, 3 or 5), clamped to the departure cell's extrema with `limiter`.  One gather pass per step
+    (lsm_advance_semilag), stable at any cfl; the term's scheme is ignored.  `stats` (an extra of this implementation): read the
+    step's counters into `ls.semilag_last` after every step — a record per workgroup, a reduction and a host wait; False leaves
+    them out and `ls.semilag_last` None."""
+    name, _describe = "semilag", "SemiLagrangian (backward characteristics, Lagrange interpolation)"
+
+    def __init__(self, cfl=4.0, *, order=3, trace=2, limiter=True, stats=True):
+        super().__init__(cfl)
+        self.order, self.trace, self.limiter, self.stats = order, trace, bool(limiter), bool(stats)
+
+
 def _jl_min(*xs):
     m = xs[0]
     for x in xs[1:]:
@@ -1529,6 +1544,8 @@ def integrate_(ls, tf, dt=float("inf"), prehook=None, posthook=None):
         raise ValueError(f"final time {tf} must be ≥ initial time {tc}: the level-set equation cannot be solved back in time")
     if isinstance(ls.integrator, SemiImplicitI2OE):
         return _integrate_i2oe(ls, tc, tf, dt, prehook, posthook)
+    if isinstance(ls.integrator, SemiLagrangian):
+        return _integrate_semilag(ls, tc, tf, dt, prehook, posthook)
     alpha = ls.integrator.cfl
     while tc <= tf - _eps(tc):
         if prehook is not None:
@@ -1586,6 +1603,53 @@ def _integrate_i2oe(ls, tc, tf, dt, prehook, posthook):
         step = _jl_min(dt, integ.cfl * ls.compute_cfl(tc), tf - tc)
         ls.i2oe_last = ls.backend.advance_i2oe(_terms_c(ls.terms), ls.state.buf, tc, step, integ.rtol, integ.max_iters)
         ls.i2oe_iters += ls.i2oe_last[0]
+        ls.state.ghosts_dirty = True
+        tc += step
+        ls.t = tc
+        ls._range_checked_at += 1
+        if ls._range_checked_at % 64 == 0:
+            ls._check_range()
+        if posthook is not None:
+            posthook(ls)
+    ls.t = tf
+    return ls
+
+
+def _validate_semilag(ls):
+    """What SemiLagrangian can run, checked on the host before any step."""
+    integ = ls.integrator
+    if ls.band:
+        raise ValueError("SemiLagrangian requires a full-grid MeshField, got ROCNarrowBandMeshField")
+    if not (len(ls.terms) == 1 and isinstance(ls.terms[0], AdvectionTerm)):
+        raise ValueError("SemiLagrangian requires exactly one AdvectionTerm")
+    if ls.comm is not None and ls.world > 1:
+        raise ValueError("SemiLagrangian runs on a single device: a slab decomposition (comm) is not supported")
+    if isinstance(integ.order, bool) or integ.order not in (1, 3, 5):
+        raise ValueError(f"SemiLagrangian: order must be 1, 3 or 5, got {integ.order!r}")
+    if isinstance(integ.trace, bool) or integ.trace not in (1, 2):
+        raise ValueError(f"SemiLagrangian: trace must be 1 or 2, got {integ.trace!r}")
+
+
+def _integrate_semilag(ls, tc, tf, dt, prehook, posthook):
+    """The step loop of _integrate_i2oe with one gather pass per step (lsm_advance_semilag); no update_band!.  The step is out of
+    place: the new state is written to a stage buffer, which then changes places with the state's buffer (nothing on the handle
+    keeps ϕ's pointer between calls: the Δt caches are keyed by the term alone, and a Renderer re-attaches to a changed buffer).
+    The counters of the last step — (staged workgroups, fallback workgroups, largest displacement in cells) — are kept in
+    ls.semilag_last: every step therefore ends in one small reduction and a host wait, unless the integrator was built with
+    stats=False."""
+    _validate_semilag(ls)
+    integ = ls.integrator
+    while tc <= tf - _eps(tc):
+        if prehook is not None:
+            prehook(ls)
+        ls._update_terms(ls.state, tc)
+        step = _jl_min(dt, integ.cfl * ls.compute_cfl(tc), tf - tc)
+        if getattr(ls, "_semilag_buf", None) is None:
+            ls._semilag_buf = ls.backend.alloc()   # the one stage buffer of this integrator, kept across integrate! calls
+        out = ls._semilag_buf
+        ls.semilag_last = ls.backend.advance_semilag(_terms_c(ls.terms), ls.state.buf, out, tc, step, integ.order, integ.trace, integ.limiter,
+                                                     want_stats=integ.stats)
+        ls.state.buf, ls._semilag_buf = out, ls.state.buf
         ls.state.ghosts_dirty = True
         tc += step
         ls.t = tc

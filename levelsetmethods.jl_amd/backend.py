@@ -151,6 +151,14 @@ class HipBackend:
                 "lsm_advance_i2oe")
         return it.value, rel.value
 
+    def advance_semilag(self, term_c, phi, out, tc, dt, order=3, trace=2, limiter=True, want_stats=True):
+        """One SemiLagrangian step (lsm_advance_semilag), out of place: the interior of `out` is the new state.  Returns
+        (staged workgroups, fallback workgroups, largest displacement in cells), or None without want_stats (no host wait)."""
+        st = (C.c_int64 * 3)() if want_stats else None
+        L.check(self.h, self.lib.lsm_advance_semilag(self.h, term_c, self.ptr(phi), self.ptr(out), tc, dt, order, trace, 1 if limiter else 0, st),
+                "lsm_advance_semilag")
+        return (int(st[0]), int(st[1]), int(st[2])) if want_stats else None
+
     def check_range(self, t):
         """(ok, max|ϕ|): is the field inside the domain of the handle's arithmetic mode (include/lsm.h, LSM_FAST_MAX_ABS)?"""
         ok, m = C.c_int(), C.c_double()

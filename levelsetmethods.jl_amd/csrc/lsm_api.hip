@@ -102,6 +102,7 @@ const LsmTuning& lsm_tuning_env() {
         if (u.comm_timeout_ms <= 0) u.comm_timeout_ms = 60000;
         u.layout_align = env_int("LSM_LAYOUT_ALIGN", 1);
         u.render_skip = env_int("LSM_RENDER_SKIP", 1);
+        u.semilag_stage = ranged("LSM_SEMILAG_STAGE", 0, 2);
         return u;
     }();
     return t;
@@ -115,16 +116,19 @@ int* lsm_tuning_field(LsmTuning& t, const char* name) {
         {"LSM_BAND_CFL_PREFETCH", &t.band_cfl_prefetch}, {"LSM_BAND_BYTES", &t.band_bytes}, {"LSM_BAND_NO_LISTS", &t.band_no_lists},
         {"LSM_STATUS_SPIN", &t.status_spin}, {"LSM_SLAB_OVERLAP", &t.slab_overlap}, {"LSM_COMM_TIMEOUT_MS", &t.comm_timeout_ms},
         {"LSM_LAYOUT_ALIGN", &t.layout_align}, {"LSM_RENDER_SKIP", &t.render_skip},
+        {"LSM_SEMILAG_STAGE", &t.semilag_stage},
     };
     for (const auto& e : tab)
         if (strcmp(e.n, name) == 0) return e.p;
     return nullptr;
 }
 // the launch-geometry switches take what the launch arithmetic is written for (include/lsm.h): chunk lengths 0 .. 65536,
-// the dynamic tail's spare workgroups 0 .. 1000 %.  Every other switch is a flag or has its own rule.
+// the dynamic tail's spare workgroups 0 .. 1000 %; LSM_SEMILAG_STAGE names one of three paths.  Every other switch is a flag or
+// has its own rule.
 static int tuning_max(const LsmTuning& t, const int* p) {
     if (p == &t.stage_mc || p == &t.stage_mc2 || p == &t.stage_tail) return 65536;
     if (p == &t.stage_tail_dyn) return 1000;
+    if (p == &t.semilag_stage) return 2;
     return 0;
 }
 }  // namespace lsm
@@ -137,6 +141,7 @@ LsmHandle::~LsmHandle() {
     if (own_stream && stream) (void)hipStreamDestroy(stream);
     reinit_workspace_free(reinit_ws);
     i2oe_workspace_free(i2oe_ws);
+    semilag_workspace_free(semilag_ws);
     mdist_workspace_free(mdist_ws);
     eikonal_workspace_free(eikonal_ws);
     cc_workspace_free(cc_ws);

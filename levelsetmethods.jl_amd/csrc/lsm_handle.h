@@ -54,6 +54,7 @@ struct PinnedBuf {
 };
 
 struct I2oeWorkspace;   // lsm_i2oe.hip: SemiImplicitI2OE's device buffers
+struct SemilagWorkspace;   // lsm_semilag.hip: SemiLagrangian's counters
 struct MdistWorkspace;  // lsm_mdist.hip: mesh_distance's scratch arrays
 struct EikonalWorkspace;   // lsm_eikonal.hip: eikonal's arrival times, frozen mask and tile lists
 struct CcWorkspace;     // lsm_cc.hip: components' parent array, chunk counts and counters
@@ -142,6 +143,7 @@ struct LsmHandle {
     size_t ev_used = 0;
     lsm::ReinitWorkspace* reinit_ws = nullptr;   // reinitialize!'s device buffers, kept between calls (grow-only)
     lsm::I2oeWorkspace* i2oe_ws = nullptr;       // lsm_advance_i2oe's solver vectors and face arrays, kept between calls (grow-only)
+    lsm::SemilagWorkspace* semilag_ws = nullptr; // lsm_advance_semilag's workgroup counters and their pinned copy
     lsm::MdistWorkspace* mdist_ws = nullptr;     // lsm_mesh_distance's squared distances and flip counters, kept between calls (grow-only)
     lsm::EikonalWorkspace* eikonal_ws = nullptr; // lsm_eikonal's arrival times, frozen mask, tile flags and lists, kept between calls (grow-only)
     lsm::CcWorkspace* cc_ws = nullptr;           // lsm_cc_*'s parent array (4 bytes per node), chunk counts and counters, kept between calls (grow-only)
@@ -183,6 +185,7 @@ bool lsm_comm_overlap(const LsmHandle* h);
 int lsm_host_sync(LsmHandle* h, const char* what);   // host wait for h->stream that an RCCL peer's silence cannot hang (lsm_comm.hip)
 int lsm_comm_band_overlap(const LsmHandle* h);   // overlap depth declared by lsm_band_overlap_config (0 = none)
 namespace lsm { void i2oe_workspace_free(I2oeWorkspace* w); }   // lsm_i2oe.hip: delete, where the type is complete
+namespace lsm { void semilag_workspace_free(SemilagWorkspace* w); }   // lsm_semilag.hip: delete, where the type is complete
 namespace lsm {   // lsm_quad.hip (compiled through lsm_reinit.hip): quadrature results
 struct QuadObject;
 int quad_build(int ndim, const int n[3], const int goff[3], long long s1, long long s2, long long origin, const double lc[3], const double h[3],

@@ -38,6 +38,7 @@ struct LsmTuning {
     int comm_timeout_ms;    // LSM_COMM_TIMEOUT_MS   a rank's wait for its peers                                              60000
     int layout_align;       // LSM_LAYOUT_ALIGN      rows of the padded layout on 64-byte lines (read by lsm_create)             1
     int render_skip;        // LSM_RENDER_SKIP       render: rays step over uniform bricks (0: every lattice sample is loaded)     1
+    int semilag_stage;      // LSM_SEMILAG_STAGE     SemiLagrangian: 0 direct gather, 1 staged tiles where the box fits, 2 staged or refuse  0
 };
 const LsmTuning& lsm_tuning_env();
 int* lsm_tuning_field(LsmTuning& t, const char* name);      // NULL: no such switch
