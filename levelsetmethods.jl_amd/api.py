@@ -3753,34 +3753,28 @@ def thermoelastic_solve(phi_or_eq, q, f=None, *, alpha, T_ref=0.0, heat=None, el
 
 # ----------------------------------------------------------------------------- homogenisation (ϕ as one cell of a periodic material)
 
-class Homogenization:
-    """homogenize's result and its operator, kept on the device (DESIGN.md §7.23).  The torus has m = n − 1 nodes (and cells) per axis;
-    M = N(N+1)/2 unit strains in Voigt order: 2-D (00, 11, 01), 3-D (00, 11, 22, 12, 02, 01), engineering shears.
-    `tensor` ((M, M) numpy, exactly symmetric), `iterations` and `relres` (one entry per corrector), `levels`, `free_dofs`;
-    corrector(k) → N ROCMeshFields (image nodes n − 1 from node 0); correctors() → host (M, N) + m; sensitivity(W) → the ROCMeshField
-    of the integrand of d(W:C^H)/dΩ, a normal speed (coeff.set_values takes it device to device); cells(), apply(x), load(k),
-    energy_cells(p, q), stiffness(level) show the operator; solve(chi0=None, rtol, max_iters) solves again (a warm start);
-    with_correctors(chi) sets the correctors without a solve; close() releases the device memory.  ϕ is read once, at construction:
-    after ϕ has moved, build a new object and pass the old correctors() as chi0."""
+class _CellProblem:
+    """What Homogenization and ConductivityHomogenization share: an operator on the torus of the grid's m = n − 1 cells per axis, its
+    K cell problems and their correctors kept on the device (csrc/cell_problem.h).  A subclass gives
+      _what, _prefix   its name in messages and the backend's method prefix
+      _cells, _unit    what messages call the cell array and a cell problem's index
+      _host_finite     solve_rhs and apply refuse non-finite host input here (or pass it to the device)
+      _material, _lead its own construction checks (what they return goes to the backend's create) and the lead shape of all correctors"""
 
-    def __init__(self, phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", level=0.0, precond="mg"):
-        what = "homogenize"
+    def __init__(self, phi_or_eq, v_in, v_out, v, names, level, precond, **material):
+        what, (n_in, n_out, n_v) = self._what, names
         self._h = None
         if precond not in _PRECONDS:
             raise ValueError(f'{what}: precond must be "mg" or "jacobi", not {precond!r}')
-        if plane not in _PLANES:
-            raise ValueError(f'{what}: plane must be "stress" or "strain", not {plane!r}')
-        nu = float(nu)
-        if not (math.isfinite(nu) and -1.0 < nu < 0.5):
-            raise ValueError(f"{what}: nu must be finite with -1 < nu < 0.5")
-        E_host = None if E is None or hasattr(E, "is_cuda") else np.asarray(E, dtype=np.float64)
-        if E is None:
-            if not (_finite_positive(float(E_in)) and _finite_positive(float(E_out))):
-                raise ValueError(f"{what}: E_in and E_out must be finite and positive")
+        material = self._material(**material)
+        v_host = None if v is None or hasattr(v, "is_cuda") else np.asarray(v, dtype=np.float64)
+        if v is None:
+            if not (_finite_positive(float(v_in)) and _finite_positive(float(v_out))):
+                raise ValueError(f"{what}: {n_in} and {n_out} must be finite and positive")
             if not math.isfinite(float(level)):
                 raise ValueError(f"{what}: level must be finite")
-        elif E_host is not None and not _finite_positive(E_host):
-            raise ValueError(f"{what}: the cell moduli `E` must be finite and positive")
+        elif v_host is not None and not _finite_positive(v_host):
+            raise ValueError(f"{what}: the {self._cells} `{n_v}` must be finite and positive")
         phi = phi_or_eq.current_state() if isinstance(phi_or_eq, LevelSetEquation) else phi_or_eq
         if not isinstance(phi, ROCMeshField):
             raise TypeError(f"{what} takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
@@ -3793,143 +3787,171 @@ class Homogenization:
         n = tuple(int(m) for m in phi.mesh.n)
         if any(m < 3 for m in n):
             raise ValueError(f"{what} needs at least 2 cells (3 nodes) in every dimension")
-        N = len(n)
         self.cells_shape = cells = tuple(m - 1 for m in n)
-        if E_host is not None and E_host.ndim and E_host.shape != cells:
-            raise ValueError(f"{what}: `E` has shape {E_host.shape}, the grid has {cells} cells")
+        if v_host is not None and v_host.ndim and v_host.shape != cells:
+            raise ValueError(f"{what}: `{n_v}` has shape {v_host.shape}, the grid has {cells} cells")
         b = self.backend = phi.backend
-        self.mesh, self.bcs, self.precond, self.ndim, self.nstrains = phi.mesh, phi.bcs, precond, N, N * (N + 1) // 2
-        E_dev = None if E is None else b.node_array(E if E_host is None else E_host, "E", cells)
+        self.mesh, self.bcs, self.precond, self.ndim = phi.mesh, phi.bcs, precond, len(n)
+        v_dev = None if v is None else b.node_array(v if v_host is None else v_host, n_v, cells)
         try:
-            self._h, stats = b.homog_create(None if E is not None else phi.buf, level, E_in, E_out, E_dev, nu, _PLANES[plane], _PRECONDS[precond])
+            self._h, stats = getattr(b, f"{self._prefix}_create")(None if v is not None else phi.buf, level, v_in, v_out, v_dev, *material, _PRECONDS[precond])
         except L.LsmError as e:
-            why = {1: "phi must be finite", 2: "the cell moduli must be finite and positive"}.get(getattr(e, "reason", 0))
+            why = {1: "phi must be finite", 2: f"the {self._cells} must be finite and positive"}.get(getattr(e, "reason", 0))
             if why is None:
                 raise
             raise ValueError(f"{what}: {why} ({getattr(e, 'detail', 0)} entries are not)") from None
         self.levels, self.free_dofs = stats[0], stats[1]
-        self.iterations, self.relres, self._tensor = [0] * self.nstrains, [0.0] * self.nstrains, None
+        K = self._lead()[0]
+        self.iterations, self.relres, self._tensor = [0] * K, [0.0] * K, None
+
+    def _material(self):
+        return ()
 
     def _handle(self):
         if self._h is None:
-            raise ValueError("the Homogenization is closed")
+            raise ValueError(f"the {type(self).__name__} is closed")
         return self._h
 
-    def _chi_dev(self, chi, what):
-        """(M, N) + m host values (or a device tensor of as many) as one flat float64 device array"""
+    def _call(self, name, *args):
+        return getattr(self.backend, f"{self._prefix}_{name}")(self._handle(), *args)
+
+    def _dev(self, v, lead, what, finite=True):
+        """lead + m host values (or a device tensor of as many) as one flat float64 device array"""
         b = self.backend
-        shape = (self.nstrains, self.ndim) + self.cells_shape
-        if b.torch.is_tensor(chi):
-            return b.node_array(chi, what, shape)
-        a = np.asarray(chi, dtype=np.float64)
+        shape = tuple(lead) + self.cells_shape
+        if b.torch.is_tensor(v):
+            return b.node_array(v, what, shape)
+        a = np.asarray(v, dtype=np.float64)
         if a.shape != shape:
             raise ValueError(f"{what} has shape {a.shape}, expected {shape}")
-        if not np.all(np.isfinite(a)):
+        if finite and not np.all(np.isfinite(a)):
             raise ValueError(f"{what} must be finite")
-        flat = np.concatenate([a[k, i].reshape(-1, order="F") for k in range(shape[0]) for i in range(shape[1])])
+        flat = np.concatenate([r.reshape(-1, order="F") for r in a.reshape((-1,) + self.cells_shape)])
         return b.torch.from_numpy(flat).to(b.device)
 
     def _unflat(self, t, lead):
         """a flat device tensor as a host array of shape lead + m"""
         m = self.cells_shape
-        nn = int(np.prod(m))
-        v = t.cpu().numpy().reshape((-1, nn))
+        v = t.cpu().numpy().reshape((-1, int(np.prod(m))))
         return np.stack([r.reshape(m, order="F") for r in v]).reshape(tuple(lead) + m)
 
+    def _index(self, k, what=None):
+        what = what or self._unit
+        K = self._lead()[0]
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"{self._what}: {what} must be an integer, not {type(k).__name__}")
+        if not 0 <= int(k) < K:
+            raise ValueError(f"{self._what}: {what} {k} of {K}")
+        return int(k)
+
     def solve(self, chi0=None, rtol=1e-8, max_iters=500):
-        """all M correctors by PCG from chi0 ((M, N) + m; zero without one).  A failure raises and leaves the stored correctors as they were."""
-        h = self._handle()
+        """all correctors by PCG from chi0 (the shape of correctors(); zero without one).  A failure raises and leaves the stored
+        correctors as they were."""
+        self._handle()
         rtol = float(rtol)
         if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
-            raise ValueError("homogenize: rtol must be positive and finite, max_iters at least 1")
-        guess = None if chi0 is None else self._chi_dev(chi0, "homogenize: chi0")
-        self.iterations, self.relres = self.backend.homog_solve(h, guess, rtol, int(max_iters))
+            raise ValueError(f"{self._what}: rtol must be positive and finite, max_iters at least 1")
+        guess = None if chi0 is None else self._dev(chi0, self._lead(), f"{self._what}: chi0")
+        self.iterations, self.relres = self._call("solve", guess, rtol, int(max_iters))
         self._tensor = None
         return self
 
     def solve_rhs(self, f, x0=None, rtol=1e-8, max_iters=500):
-        """the same PCG for a right-hand side of the caller's, A x = f away from the pinned node 0: f and x0 host arrays of shape
-        (N,) + m.  Returns (x, iterations, relres); the correctors are not touched (for diagnostics and tests of the V-cycle)."""
-        b, N = self.backend, self.ndim
-        shape = (N,) + self.cells_shape
-
-        def dev(a, what):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape != shape:
-                raise ValueError(f"homogenize: {what} has shape {a.shape}, expected {shape}")
-            return b.torch.from_numpy(np.concatenate([a[i].reshape(-1, order="F") for i in range(N)])).to(b.device)
-        fd = dev(f, "f")
-        xd = dev(np.zeros(shape) if x0 is None else x0, "x0")
-        it, rel = b.homog_solve_rhs(self._handle(), fd, xd, float(rtol), int(max_iters))
-        return self._unflat(xd, (N,)), it, rel
+        """the same PCG for a right-hand side of the caller's, A x = f away from the pinned node 0: f and x0 host arrays of the shape
+        of one corrector.  Returns (x, iterations, relres); the correctors are not touched (for diagnostics and tests of the V-cycle)."""
+        lead = self._lead()[1:]
+        fd = self._dev(f, lead, f"{self._what}: f", self._host_finite)
+        xd = self._dev(np.zeros(lead + self.cells_shape) if x0 is None else x0, lead, f"{self._what}: x0", self._host_finite)
+        it, rel = self._call("solve_rhs", fd, xd, float(rtol), int(max_iters))
+        return self._unflat(xd, lead), it, rel
 
     def with_correctors(self, chi):
-        """take correctors from elsewhere ((M, N) + m), without a solve"""
-        self.backend.homog_set_correctors(self._handle(), self._chi_dev(chi, "with_correctors: chi"))
+        """take correctors from elsewhere (the shape of correctors()), without a solve"""
+        self._handle()
+        self._call("set_correctors", self._dev(chi, self._lead(), "with_correctors: chi"))
         self._tensor = None
         return self
 
     @property
     def tensor(self):
         if self._tensor is None:
-            self._tensor = self.backend.homog_tensor(self._handle())
+            self._tensor = self._call("tensor")
         return self._tensor
 
     def correctors(self):
-        return self._unflat(self.backend.homog_correctors(self._handle()), (self.nstrains, self.ndim))
-
-    def _strain(self, k, what="the unit strain"):
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-            raise TypeError(f"homogenize: {what} must be an integer, not {type(k).__name__}")
-        if not 0 <= int(k) < self.nstrains:
-            raise ValueError(f"homogenize: {what} {k} of {self.nstrains}")
-        return int(k)
-
-    def corrector(self, k):
-        h = self._handle()
-        u = [ROCMeshField(self.backend, self.mesh, self.bcs) for _ in range(self.ndim)]
-        self.backend.homog_corrector(h, self._strain(k), [c.buf for c in u])
-        return tuple(u)
+        return self._unflat(self._call("correctors"), self._lead())
 
     def sensitivity(self, W):
         W = np.asarray(W, dtype=np.float64)
-        M = self.nstrains
-        if W.shape != (M, M) or not np.all(np.isfinite(W)) or not np.array_equal(W, W.T):
-            raise ValueError(f"homogenize: W must be a finite symmetric {M}×{M} matrix")
+        K = self._lead()[0]
+        if W.shape != (K, K) or not np.all(np.isfinite(W)) or not np.array_equal(W, W.T):
+            raise ValueError(f"{self._what}: W must be a finite symmetric {K}×{K} matrix")
         g = ROCMeshField(self.backend, self.mesh, self.bcs)
-        self.backend.homog_sensitivity(self._handle(), W, g.buf)
+        self._call("sensitivity", W, g.buf)
         return g
 
     def cells(self):
-        return self._unflat(self.backend.homog_cells(self._handle()), ())
+        return self._unflat(self._call("cells"), ())
 
     def apply(self, x):
-        """A x on all components, no pin: x a host array of shape (N,) + m; returns one"""
-        b, N = self.backend, self.ndim
-        a = np.asarray(x, dtype=np.float64)
-        if a.shape != (N,) + self.cells_shape:
-            raise ValueError(f"homogenize: x has shape {a.shape}, expected {(N,) + self.cells_shape}")
-        xd = b.torch.from_numpy(np.concatenate([a[i].reshape(-1, order="F") for i in range(N)])).to(b.device)
-        return self._unflat(b.homog_apply(self._handle(), xd), (N,))
+        """A x on all components, no pin: x a host array of the shape of one corrector; returns one"""
+        lead = self._lead()[1:]
+        return self._unflat(self._call("apply", self._dev(x, lead, f"{self._what}: x", self._host_finite)), lead)
 
     def load(self, k):
-        return self._unflat(self.backend.homog_load(self._handle(), self._strain(k)), (self.ndim,))
+        return self._unflat(self._call("load", self._index(k)), self._lead()[1:])
 
     def energy_cells(self, p, q):
-        return self._unflat(self.backend.homog_energy_cells(self._handle(), self._strain(p), self._strain(q)), ())
-
-    def stiffness(self, level=0):
-        return self.backend.homog_stiffness(self._handle(), level)
+        return self._unflat(self._call("energy_cells", self._index(p), self._index(q)), ())
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h is not None:
             try:
-                self.backend.homog_destroy(h)
+                getattr(self.backend, f"{self._prefix}_destroy")(h)
             except Exception:
                 pass
 
     __del__ = close
+
+
+class Homogenization(_CellProblem):
+    """homogenize's result and its operator, kept on the device (DESIGN.md §7.23).  The torus has m = n − 1 nodes (and cells) per axis;
+    M = N(N+1)/2 unit strains in Voigt order: 2-D (00, 11, 01), 3-D (00, 11, 22, 12, 02, 01), engineering shears.
+    `tensor` ((M, M) numpy, exactly symmetric), `iterations` and `relres` (one entry per corrector), `levels`, `free_dofs`;
+    corrector(k) → N ROCMeshFields (image nodes n − 1 from node 0); correctors() → host (M, N) + m; sensitivity(W) → the ROCMeshField
+    of the integrand of d(W:C^H)/dΩ, a normal speed (coeff.set_values takes it device to device); cells(), apply(x), load(k),
+    energy_cells(p, q), stiffness(level) show the operator; solve(chi0=None, rtol, max_iters) solves again (a warm start);
+    with_correctors(chi) sets the correctors without a solve; close() releases the device memory.  ϕ is read once, at construction:
+    after ϕ has moved, build a new object and pass the old correctors() as chi0."""
+    _what, _prefix, _cells, _unit, _host_finite = "homogenize", "homog", "cell moduli", "the unit strain", False
+
+    def __init__(self, phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", level=0.0, precond="mg"):
+        super().__init__(phi_or_eq, E_in, E_out, E, ("E_in", "E_out", "E"), level, precond, nu=nu, plane=plane)
+
+    def _material(self, nu, plane):
+        if plane not in _PLANES:
+            raise ValueError(f'{self._what}: plane must be "stress" or "strain", not {plane!r}')
+        nu = float(nu)
+        if not (math.isfinite(nu) and -1.0 < nu < 0.5):
+            raise ValueError(f"{self._what}: nu must be finite with -1 < nu < 0.5")
+        return nu, _PLANES[plane]
+
+    @property
+    def nstrains(self):
+        return self.ndim * (self.ndim + 1) // 2
+
+    def _lead(self):
+        return (self.nstrains, self.ndim)
+
+    def corrector(self, k):
+        u = [ROCMeshField(self.backend, self.mesh, self.bcs) for _ in range(self.ndim)]
+        self._call("corrector", self._index(k), [c.buf for c in u])
+        return tuple(u)
+
+    def stiffness(self, level=0):
+        return self._call("stiffness", level)
+
 
 
 def homogenize(phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress", level=0.0, rtol=1e-8, max_iters=500, precond="mg", chi0=None):
@@ -3949,7 +3971,7 @@ def homogenize(phi_or_eq, *, E_in=1.0, E_out=1e-3, E=None, nu=0.3, plane="stress
         raise
 
 
-class ConductivityHomogenization:
+class ConductivityHomogenization(_CellProblem):
     """homogenize_conductivity's result and its operator, kept on the device.  The torus has m = n − 1 nodes (and
     cells) per axis; there are N unit gradients e_0 … e_{N−1}.  `tensor` ((N, N) numpy, exactly symmetric), `iterations` and `relres`
     (one entry per corrector), `levels`, `free_dofs`, `cells_shape`; corrector(k) → a ROCMeshField (image nodes n − 1 from node 0);
@@ -3958,151 +3980,19 @@ class ConductivityHomogenization:
     solves again (a warm start); solve_rhs(f, x0) runs the same PCG on a right-hand side of the caller's; with_correctors(chi) sets
     the correctors without a solve; close() releases the device memory.  ϕ is read once, at construction: after ϕ has moved, build
     a new object and pass the old correctors() as chi0."""
+    _what, _prefix, _cells, _unit, _host_finite = "homogenize_conductivity", "hcond", "cell coefficients", "the unit gradient", True
 
     def __init__(self, phi_or_eq, *, a_in=1.0, a_out=1e-3, a=None, level=0.0, precond="mg"):
-        what = "homogenize_conductivity"
-        self._h = None
-        if precond not in _PRECONDS:
-            raise ValueError(f'{what}: precond must be "mg" or "jacobi", not {precond!r}')
-        a_host = None if a is None or hasattr(a, "is_cuda") else np.asarray(a, dtype=np.float64)
-        if a is None:
-            if not (_finite_positive(float(a_in)) and _finite_positive(float(a_out))):
-                raise ValueError(f"{what}: a_in and a_out must be finite and positive")
-            if not math.isfinite(float(level)):
-                raise ValueError(f"{what}: level must be finite")
-        elif a_host is not None and not _finite_positive(a_host):
-            raise ValueError(f"{what}: the cell coefficients `a` must be finite and positive")
-        phi = phi_or_eq.current_state() if isinstance(phi_or_eq, LevelSetEquation) else phi_or_eq
-        if not isinstance(phi, ROCMeshField):
-            raise TypeError(f"{what} takes a device field (ROCMeshField) or a LevelSetEquation, not {type(phi).__name__}")
-        if isinstance(phi, ROCNarrowBandMeshField):
-            raise ValueError(f"{what} is not supported on NarrowBandMeshField: the cell problems are solved over the whole box. Use a full MeshField.")
-        if phi.mesh.ndim == 1:
-            raise ValueError(f"{what} of a 1 dimensional level-set is not supported: 2-D and 3-D fields only")
-        if getattr(phi.backend, "slab", None) is not None:
-            raise ValueError(f"{what} of a slab-decomposed field (a field with a comm) is not supported")
-        n = tuple(int(m) for m in phi.mesh.n)
-        if any(m < 3 for m in n):
-            raise ValueError(f"{what} needs at least 2 cells (3 nodes) in every dimension")
-        self.cells_shape = cells = tuple(m - 1 for m in n)
-        if a_host is not None and a_host.ndim and a_host.shape != cells:
-            raise ValueError(f"{what}: `a` has shape {a_host.shape}, the grid has {cells} cells")
-        b = self.backend = phi.backend
-        self.mesh, self.bcs, self.precond, self.ndim = phi.mesh, phi.bcs, precond, len(n)
-        a_dev = None if a is None else b.node_array(a if a_host is None else a_host, "a", cells)
-        try:
-            self._h, stats = b.hcond_create(None if a is not None else phi.buf, level, a_in, a_out, a_dev, _PRECONDS[precond])
-        except L.LsmError as e:
-            why = {1: "phi must be finite", 2: "the cell coefficients must be finite and positive"}.get(getattr(e, "reason", 0))
-            if why is None:
-                raise
-            raise ValueError(f"{what}: {why} ({getattr(e, 'detail', 0)} entries are not)") from None
-        self.levels, self.free_dofs = stats[0], stats[1]
-        self.iterations, self.relres, self._tensor = [0] * self.ndim, [0.0] * self.ndim, None
+        super().__init__(phi_or_eq, a_in, a_out, a, ("a_in", "a_out", "a"), level, precond)
 
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the ConductivityHomogenization is closed")
-        return self._h
-
-    def _dev(self, v, lead, what):
-        """lead + m host values (or a device tensor of as many) as one flat float64 device array"""
-        b = self.backend
-        shape = tuple(lead) + self.cells_shape
-        if b.torch.is_tensor(v):
-            return b.node_array(v, what, shape)
-        a = np.asarray(v, dtype=np.float64)
-        if a.shape != shape:
-            raise ValueError(f"{what} has shape {a.shape}, expected {shape}")
-        if not np.all(np.isfinite(a)):
-            raise ValueError(f"{what} must be finite")
-        flat = np.concatenate([r.reshape(-1, order="F") for r in a.reshape((-1,) + self.cells_shape)])
-        return b.torch.from_numpy(flat).to(b.device)
-
-    def _unflat(self, t, lead):
-        """a flat device tensor as a host array of shape lead + m"""
-        m = self.cells_shape
-        v = t.cpu().numpy().reshape((-1, int(np.prod(m))))
-        return np.stack([r.reshape(m, order="F") for r in v]).reshape(tuple(lead) + m)
-
-    def solve(self, chi0=None, rtol=1e-8, max_iters=500):
-        """all N correctors by PCG from chi0 ((N,) + m; zero without one).  A failure raises and leaves the stored correctors as they were."""
-        h = self._handle()
-        rtol = float(rtol)
-        if not (rtol > 0 and math.isfinite(rtol)) or int(max_iters) < 1:
-            raise ValueError("homogenize_conductivity: rtol must be positive and finite, max_iters at least 1")
-        guess = None if chi0 is None else self._dev(chi0, (self.ndim,), "homogenize_conductivity: chi0")
-        self.iterations, self.relres = self.backend.hcond_solve(h, guess, rtol, int(max_iters))
-        self._tensor = None
-        return self
-
-    def solve_rhs(self, f, x0=None, rtol=1e-8, max_iters=500):
-        """the same PCG for a right-hand side of the caller's, A x = f away from the pinned node 0: f and x0 host arrays of shape m.
-        Returns (x, iterations, relres); the correctors are not touched (for diagnostics and tests of the V-cycle)."""
-        fd = self._dev(f, (), "homogenize_conductivity: f")
-        xd = self._dev(np.zeros(self.cells_shape) if x0 is None else x0, (), "homogenize_conductivity: x0")
-        it, rel = self.backend.hcond_solve_rhs(self._handle(), fd, xd, float(rtol), int(max_iters))
-        return self._unflat(xd, ()), it, rel
-
-    def with_correctors(self, chi):
-        """take correctors from elsewhere ((N,) + m), without a solve"""
-        self.backend.hcond_set_correctors(self._handle(), self._dev(chi, (self.ndim,), "with_correctors: chi"))
-        self._tensor = None
-        return self
-
-    @property
-    def tensor(self):
-        if self._tensor is None:
-            self._tensor = self.backend.hcond_tensor(self._handle())
-        return self._tensor
-
-    def correctors(self):
-        return self._unflat(self.backend.hcond_correctors(self._handle()), (self.ndim,))
-
-    def _axis(self, k, what="the unit gradient"):
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-            raise TypeError(f"homogenize_conductivity: {what} must be an integer, not {type(k).__name__}")
-        if not 0 <= int(k) < self.ndim:
-            raise ValueError(f"homogenize_conductivity: {what} {k} of {self.ndim}")
-        return int(k)
+    def _lead(self):
+        return (self.ndim,)
 
     def corrector(self, k):
-        h = self._handle()
         u = ROCMeshField(self.backend, self.mesh, self.bcs)
-        self.backend.hcond_corrector(h, self._axis(k), u.buf)
+        self._call("corrector", self._index(k), u.buf)
         return u
 
-    def sensitivity(self, W):
-        W = np.asarray(W, dtype=np.float64)
-        N = self.ndim
-        if W.shape != (N, N) or not np.all(np.isfinite(W)) or not np.array_equal(W, W.T):
-            raise ValueError(f"homogenize_conductivity: W must be a finite symmetric {N}×{N} matrix")
-        g = ROCMeshField(self.backend, self.mesh, self.bcs)
-        self.backend.hcond_sensitivity(self._handle(), W, g.buf)
-        return g
-
-    def cells(self):
-        return self._unflat(self.backend.hcond_cells(self._handle()), ())
-
-    def apply(self, x):
-        """A x on all nodes, no pin: x a host array of shape m; returns one"""
-        return self._unflat(self.backend.hcond_apply(self._handle(), self._dev(x, (), "homogenize_conductivity: x")), ())
-
-    def load(self, k):
-        return self._unflat(self.backend.hcond_load(self._handle(), self._axis(k)), ())
-
-    def energy_cells(self, p, q):
-        return self._unflat(self.backend.hcond_energy_cells(self._handle(), self._axis(p), self._axis(q)), ())
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h is not None:
-            try:
-                self.backend.hcond_destroy(h)
-            except Exception:
-                pass
-
-    __del__ = close
 
 
 def homogenize_conductivity(phi_or_eq, *, a_in=1.0, a_out=1e-3, a=None, level=0.0, rtol=1e-8, max_iters=500, precond="mg", chi0=None):

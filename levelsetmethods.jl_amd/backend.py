@@ -9,6 +9,7 @@ The only implementation in this package is the HIP one; it raises if the library
 missing — there is no CPU path.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -658,166 +659,98 @@ class HipBackend:
     def elastic_destroy(self, obj):
         self.lib.lsm_elastic_destroy(obj)
 
-    # ---- homogenisation (lsm_homog_*): vectors are flat float64 device tensors over the torus of n − 1 nodes per axis
-    def _homog_sizes(self):
-        N = self.ndim
-        return N, N * (N + 1) // 2, int(np.prod([m - 1 for m in self.local_shape()]))
+    # ---- the periodic cell problems: homogenisation (lsm_homog_*) and conductivity homogenisation (lsm_hcond_*), csrc/cell_problem.h.
+    # Vectors are flat float64 device tensors over the torus of n − 1 nodes per axis.  The methods homog_NAME and hcond_NAME are the
+    # _cp_NAME below with the prefix bound (after the class).
+    def _cp_sizes(self, pre):
+        """(components per node, cell problems, nodes of the torus)"""
+        N, nn = self.ndim, int(np.prod([m - 1 for m in self.local_shape()]))
+        return (N, N * (N + 1) // 2, nn) if pre == "homog" else (1, N, nn)
 
-    def homog_create(self, phi, level, e_in, e_out, e_cells, nu, plane, precond):
-        """returns (object, (levels, free components, nodes of the torus, 0)); an LsmError raised for the data carries `reason` and `detail`"""
+    def _cp_check(self, pre, name, *args):
+        fn = f"lsm_{pre}_{name}"
+        L.check(self.h, getattr(self.lib, fn)(*args), fn)
+
+    def _cp_device(self, pre, name, size, obj, *args):
+        """the entry point's output, `size` doubles on the device"""
+        out = self.torch.empty(size, dtype=self.torch.float64, device=self.device)
+        self._cp_check(pre, name, obj, *args, self.ptr(out))
+        return out
+
+    def _cp_create(self, pre, phi, level, v_in, v_out, cells, *own):
+        """own: the operator's own arguments, then the preconditioner.  Returns (object, (levels, free components, nodes of the torus,
+        0)); an LsmError raised for the data carries `reason` and `detail`"""
         if self.slab is not None:
-            raise L.LsmError("homog_create: this backend holds a slab of a decomposed grid; lsm_homog_create works on the whole grid of one device")
+            raise L.LsmError(f"{pre}_create: this backend holds a slab of a decomposed grid; lsm_{pre}_create works on the whole grid of one device")
         out, stats = C.c_void_p(), (C.c_int64 * 4)()
-        code = self.lib.lsm_homog_create(self.h, self.ptr(phi), float(level), float(e_in), float(e_out), self.ptr(e_cells), float(nu), int(plane), int(precond),
-                                         C.byref(out), stats)
+        code = getattr(self.lib, f"lsm_{pre}_create")(self.h, self.ptr(phi), float(level), float(v_in), float(v_out), self.ptr(cells), *own, C.byref(out), stats)
         try:
-            L.check(self.h, code, "lsm_homog_create")
+            L.check(self.h, code, f"lsm_{pre}_create")
         except L.LsmError as e:
             e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0
             e.detail = int(stats[1])
             raise
         return out, tuple(int(v) for v in stats)
+
+    def _cp_cells(self, pre, obj):
+        return self._cp_device(pre, "cells", self._cp_sizes(pre)[2], obj)
+
+    def _cp_apply(self, pre, obj, x):
+        y = self.torch.empty_like(x)
+        self._cp_check(pre, "apply", obj, self.ptr(x), self.ptr(y))
+        return y
+
+    def _cp_load(self, pre, obj, k):
+        nc, _, nn = self._cp_sizes(pre)
+        return self._cp_device(pre, "load", nc * nn, obj, int(k))
+
+    def _cp_solve(self, pre, obj, guess, rtol, max_iters):
+        """guess: a flat float64 device tensor of all correctors or None; returns (iterations, relres), one entry per corrector"""
+        K = self._cp_sizes(pre)[1]
+        it, rel = (C.c_int * K)(), (C.c_double * K)()
+        self._cp_check(pre, "solve", obj, self.ptr(guess), float(rtol), int(max_iters), it, rel)
+        return [int(v) for v in it], [float(v) for v in rel]
+
+    def _cp_solve_rhs(self, pre, obj, f, x, rtol, max_iters):
+        """x (in: the guess, out: the solution) and f are flat float64 device tensors of one corrector's size; returns (iterations, relres)"""
+        it, rel = C.c_int(0), C.c_double(0.0)
+        self._cp_check(pre, "solve_rhs", obj, self.ptr(f), self.ptr(x), float(rtol), int(max_iters), C.byref(it), C.byref(rel))
+        return it.value, rel.value
+
+    def _cp_set_correctors(self, pre, obj, chi):
+        self._cp_check(pre, "set_correctors", obj, self.ptr(chi))
+
+    def _cp_correctors(self, pre, obj):
+        nc, K, nn = self._cp_sizes(pre)
+        return self._cp_device(pre, "correctors", K * nc * nn, obj)
+
+    def _cp_energy_cells(self, pre, obj, p, q):
+        return self._cp_device(pre, "energy_cells", self._cp_sizes(pre)[2], obj, int(p), int(q))
+
+    def _cp_tensor(self, pre, obj):
+        K = self._cp_sizes(pre)[1]
+        out = np.zeros((K, K), dtype=np.float64)
+        self._cp_check(pre, "tensor", obj, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def _cp_sensitivity(self, pre, obj, W, g):
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        self._cp_check(pre, "sensitivity", obj, W.ctypes.data_as(C.POINTER(C.c_double)), self.ptr(g))
+
+    def _cp_destroy(self, pre, obj):
+        getattr(self.lib, f"lsm_{pre}_destroy")(obj)
 
     def homog_stiffness(self, obj, level):
         R = (1 << self.ndim) * self.ndim
         out = np.zeros((R, R), dtype=np.float64)
-        L.check(self.h, self.lib.lsm_homog_stiffness(obj, int(level), out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_homog_stiffness")
-        return out
-
-    def homog_cells(self, obj):
-        out = self.torch.empty(self._homog_sizes()[2], dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_homog_cells(obj, self.ptr(out)), "lsm_homog_cells")
-        return out
-
-    def homog_apply(self, obj, x):
-        y = self.torch.empty_like(x)
-        L.check(self.h, self.lib.lsm_homog_apply(obj, self.ptr(x), self.ptr(y)), "lsm_homog_apply")
-        return y
-
-    def homog_load(self, obj, k):
-        N, _, nn = self._homog_sizes()
-        out = self.torch.empty(N * nn, dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_homog_load(obj, int(k), self.ptr(out)), "lsm_homog_load")
-        return out
-
-    def homog_solve(self, obj, guess, rtol, max_iters):
-        """guess: a flat float64 device tensor of M·N·nn values or None; returns (iterations, relres), one entry per corrector"""
-        M = self._homog_sizes()[1]
-        it, rel = (C.c_int * M)(), (C.c_double * M)()
-        L.check(self.h, self.lib.lsm_homog_solve(obj, self.ptr(guess), float(rtol), int(max_iters), it, rel), "lsm_homog_solve")
-        return [int(v) for v in it], [float(v) for v in rel]
-
-    def homog_solve_rhs(self, obj, f, x, rtol, max_iters):
-        """x (in: the guess, out: the solution) and f are flat float64 device tensors of N·nn values; returns (iterations, relres)"""
-        it, rel = C.c_int(0), C.c_double(0.0)
-        L.check(self.h, self.lib.lsm_homog_solve_rhs(obj, self.ptr(f), self.ptr(x), float(rtol), int(max_iters), C.byref(it), C.byref(rel)), "lsm_homog_solve_rhs")
-        return it.value, rel.value
-
-    def homog_set_correctors(self, obj, chi):
-        L.check(self.h, self.lib.lsm_homog_set_correctors(obj, self.ptr(chi)), "lsm_homog_set_correctors")
-
-    def homog_correctors(self, obj):
-        N, M, nn = self._homog_sizes()
-        out = self.torch.empty(M * N * nn, dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_homog_correctors(obj, self.ptr(out)), "lsm_homog_correctors")
-        return out
-
-    def homog_energy_cells(self, obj, p, q):
-        out = self.torch.empty(self._homog_sizes()[2], dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_homog_energy_cells(obj, int(p), int(q), self.ptr(out)), "lsm_homog_energy_cells")
-        return out
-
-    def homog_tensor(self, obj):
-        M = self._homog_sizes()[1]
-        out = np.zeros((M, M), dtype=np.float64)
-        L.check(self.h, self.lib.lsm_homog_tensor(obj, out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_homog_tensor")
+        self._cp_check("homog", "stiffness", obj, int(level), out.ctypes.data_as(C.POINTER(C.c_double)))
         return out
 
     def homog_corrector(self, obj, k, u):
-        L.check(self.h, self.lib.lsm_homog_corrector(obj, int(k), *self._u3(u)), "lsm_homog_corrector")
-
-    def homog_sensitivity(self, obj, W, g):
-        W = np.ascontiguousarray(W, dtype=np.float64)
-        L.check(self.h, self.lib.lsm_homog_sensitivity(obj, W.ctypes.data_as(C.POINTER(C.c_double)), self.ptr(g)), "lsm_homog_sensitivity")
-
-    def homog_destroy(self, obj):
-        self.lib.lsm_homog_destroy(obj)
-
-    # ---- conductivity homogenisation (lsm_hcond_*): vectors are flat float64 device tensors over the torus of n − 1 nodes per axis
-    def _hcond_sizes(self):
-        return self.ndim, int(np.prod([m - 1 for m in self.local_shape()]))
-
-    def hcond_create(self, phi, level, a_in, a_out, a_cells, precond):
-        """returns (object, (levels, free nodes, nodes of the torus, 0)); an LsmError raised for the data carries `reason` and `detail`"""
-        if self.slab is not None:
-            raise L.LsmError("hcond_create: this backend holds a slab of a decomposed grid; lsm_hcond_create works on the whole grid of one device")
-        out, stats = C.c_void_p(), (C.c_int64 * 4)()
-        code = self.lib.lsm_hcond_create(self.h, self.ptr(phi), float(level), float(a_in), float(a_out), self.ptr(a_cells), int(precond), C.byref(out), stats)
-        try:
-            L.check(self.h, code, "lsm_hcond_create")
-        except L.LsmError as e:
-            e.reason = -int(stats[0]) if code == L.ERR_INVALID and stats[0] < 0 else 0
-            e.detail = int(stats[1])
-            raise
-        return out, tuple(int(v) for v in stats)
-
-    def hcond_cells(self, obj):
-        out = self.torch.empty(self._hcond_sizes()[1], dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_hcond_cells(obj, self.ptr(out)), "lsm_hcond_cells")
-        return out
-
-    def hcond_apply(self, obj, x):
-        y = self.torch.empty_like(x)
-        L.check(self.h, self.lib.lsm_hcond_apply(obj, self.ptr(x), self.ptr(y)), "lsm_hcond_apply")
-        return y
-
-    def hcond_load(self, obj, k):
-        out = self.torch.empty(self._hcond_sizes()[1], dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_hcond_load(obj, int(k), self.ptr(out)), "lsm_hcond_load")
-        return out
-
-    def hcond_solve(self, obj, guess, rtol, max_iters):
-        """guess: a flat float64 device tensor of N·nn values or None; returns (iterations, relres), one entry per corrector"""
-        N = self.ndim
-        it, rel = (C.c_int * N)(), (C.c_double * N)()
-        L.check(self.h, self.lib.lsm_hcond_solve(obj, self.ptr(guess), float(rtol), int(max_iters), it, rel), "lsm_hcond_solve")
-        return [int(v) for v in it], [float(v) for v in rel]
-
-    def hcond_solve_rhs(self, obj, f, x, rtol, max_iters):
-        """x (in: the guess, out: the solution) and f are flat float64 device tensors of nn values; returns (iterations, relres)"""
-        it, rel = C.c_int(0), C.c_double(0.0)
-        L.check(self.h, self.lib.lsm_hcond_solve_rhs(obj, self.ptr(f), self.ptr(x), float(rtol), int(max_iters), C.byref(it), C.byref(rel)), "lsm_hcond_solve_rhs")
-        return it.value, rel.value
-
-    def hcond_set_correctors(self, obj, chi):
-        L.check(self.h, self.lib.lsm_hcond_set_correctors(obj, self.ptr(chi)), "lsm_hcond_set_correctors")
-
-    def hcond_correctors(self, obj):
-        N, nn = self._hcond_sizes()
-        out = self.torch.empty(N * nn, dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_hcond_correctors(obj, self.ptr(out)), "lsm_hcond_correctors")
-        return out
-
-    def hcond_energy_cells(self, obj, p, q):
-        out = self.torch.empty(self._hcond_sizes()[1], dtype=self.torch.float64, device=self.device)
-        L.check(self.h, self.lib.lsm_hcond_energy_cells(obj, int(p), int(q), self.ptr(out)), "lsm_hcond_energy_cells")
-        return out
-
-    def hcond_tensor(self, obj):
-        N = self.ndim
-        out = np.zeros((N, N), dtype=np.float64)
-        L.check(self.h, self.lib.lsm_hcond_tensor(obj, out.ctypes.data_as(C.POINTER(C.c_double))), "lsm_hcond_tensor")
-        return out
+        self._cp_check("homog", "corrector", obj, int(k), *self._u3(u))
 
     def hcond_corrector(self, obj, k, u):
-        L.check(self.h, self.lib.lsm_hcond_corrector(obj, int(k), self.ptr(u)), "lsm_hcond_corrector")
-
-    def hcond_sensitivity(self, obj, W, g):
-        W = np.ascontiguousarray(W, dtype=np.float64)
-        L.check(self.h, self.lib.lsm_hcond_sensitivity(obj, W.ctypes.data_as(C.POINTER(C.c_double)), self.ptr(g)), "lsm_hcond_sensitivity")
-
-    def hcond_destroy(self, obj):
-        self.lib.lsm_hcond_destroy(obj)
+        self._cp_check("hcond", "corrector", obj, int(k), self.ptr(u))
 
     # ---- stress recovery (lsm_elastic_stress_*): `what` is L.STRESS_STRAIN, L.STRESS_STRESS or L.STRESS_VON_MISES
     def elastic_stress_cells(self, obj, u, what):
@@ -1170,3 +1103,8 @@ class HipBackend:
         n, ms = C.c_int64(), C.c_double()
         L.check(self.h, self.lib.lsm_profile_read(self.h, C.byref(n), C.byref(ms)), "lsm_profile_read")
         return n.value, ms.value
+
+
+for _pre in ("homog", "hcond"):
+    for _name in ("create", "cells", "apply", "load", "solve", "solve_rhs", "set_correctors", "correctors", "energy_cells", "tensor", "sensitivity", "destroy"):
+        setattr(HipBackend, f"{_pre}_{_name}", functools.partialmethod(getattr(HipBackend, f"_cp_{_name}"), _pre))

@@ -32,7 +32,8 @@
 //   static launch_resid(N, nb, stream, L, r, x, res, st)   launches the level's residual kernel: mg_resid_kernel, or its own
 //   apply<N, MASK>(id, I, x, stride, out)  the comps(N) rows of the eliminated operator at node id from x[j·stride + q].  MASK: x may
 //                                          hold anything on fixed components (they are not read); without it x holds zero there.
-//   optional: static constexpr bool wraps = true, with launch_gather and launch_prolong (see mg_wraps below): a grid that wraps
+//   optional: static constexpr bool wraps = true, with launch_gather and launch_prolong (see mg_wraps below): a grid that wraps;
+//             its index arithmetic, its transfers and the Levels' common base are cell_problem.h's
 #pragma once
 
 #include <algorithm>
@@ -359,109 +360,6 @@ __global__ void __launch_bounds__(MG_THREADS) mg_prolong_kernel(Level Lf, Level 
         x[id] = x[id] + acc;
     }
 }
-// ---- the index arithmetic of a grid that wraps: n nodes (= cells) per axis, node n is node 0
-// c[d][o + 1] = ((I_d + o) mod n_d)·(the axis' stride), o ∈ {−1, 0, 1}: nodes and cells share it
-template <int N>
-__device__ __forceinline__ void mg_wrapped(const int n[3], const int I[3], int c[3][3]) {
-    const int st[3] = {1, n[0], n[0] * n[1]};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        if (d < N) {
-            c[d][0] = (I[d] == 0 ? n[d] - 1 : I[d] - 1) * st[d];
-            c[d][1] = I[d] * st[d];
-            c[d][2] = (I[d] == n[d] - 1 ? 0 : I[d] + 1) * st[d];
-        } else c[d][0] = c[d][1] = c[d][2] = 0;
-    }
-}
-// the 2^N corner nodes of cell C, wrapped
-template <int N>
-__device__ __forceinline__ void mg_wrapped_corners(const int n[3], const int C[3], int node[1 << N]) {
-    int up[3] = {0, 0, 0};
-#pragma unroll
-    for (int d = 0; d < N; ++d) up[d] = C[d] == n[d] - 1 ? 0 : C[d] + 1;
-#pragma unroll
-    for (int b = 0; b < (1 << N); ++b)
-        node[b] = ((b & 1) ? up[0] : C[0]) + n[0] * (((b >> 1) & 1 ? up[1] : C[1]) + (N > 2 ? n[1] * ((b >> 2) & 1 ? up[2] : C[2]) : 0));
-}
-
-// ---- the transfers of a grid that wraps (lsm_homog.hip, lsm_hcond.hip: m nodes per axis, node m is node 0, m even on a coarsened
-// axis), per component (blockIdx.y).  r_c[J] = 2^−k·Σ_o w_o·res[(2J + o) mod m], w = 1 at o = 0 and ½ at o = ±1 per coarsened axis
-// (o0 fastest, from +0); zero on the fixed components (the pin)
-template <int N, class Level>
-__global__ void __launch_bounds__(MG_THREADS) mg_wrap_gather_kernel(Level Lf, Level Lc, int co0, int co1, int co2, const double* __restrict__ res,
-                                                                    double* __restrict__ rc, const MgState* st) {
-    if (st->status != MG_RUN) return;
-    const int co[3] = {co0, co1, co2};
-    const double scale = mg_coarsen_scale(co0 + co1 + co2);
-    const int comp = blockIdx.y;
-    res += (size_t)comp * Lf.nn;
-    rc += (size_t)comp * Lc.nn;
-    MG_LOOP(id, Lc.nn) {
-        double acc = 0.0;
-        if (!Lc.fixed(id, comp)) {
-            int J[3];
-            mg_coords<N>(Lc.n, id, J);
-            for (int m = 0; m < (N == 2 ? 9 : 27); ++m) {
-                const int o[3] = {m % 3 - 1, (m / 3) % 3 - 1, N > 2 ? m / 9 - 1 : 0};
-                int I[3] = {0, 0, 0};
-                double w = 1.0;
-                bool use = true;
-#pragma unroll
-                for (int d = 0; d < N; ++d) {
-                    if (!co[d]) {
-                        if (o[d] != 0) use = false;
-                        I[d] = J[d];
-                        continue;
-                    }
-                    I[d] = 2 * J[d] + o[d];
-                    if (I[d] < 0) I[d] += Lf.n[d];
-                    if (I[d] >= Lf.n[d]) I[d] -= Lf.n[d];
-                    if (o[d] != 0) w = w * 0.5;
-                }
-                if (use) acc += w * res[I[0] + Lf.n[0] * (I[1] + (N > 2 ? Lf.n[1] * I[2] : 0))];     // zero on fixed fine components
-            }
-        }
-        rc[id] = acc * scale;
-    }
-}
-// x += P x_c on the free fine components: the transpose of the wrapping gather without its 2^−k
-template <int N, class Level>
-__global__ void __launch_bounds__(MG_THREADS) mg_wrap_prolong_kernel(Level Lf, Level Lc, int co0, int co1, int co2, const double* __restrict__ xc,
-                                                                     double* __restrict__ x, const MgState* st) {
-    if (st->status != MG_RUN) return;
-    const int co[3] = {co0, co1, co2};
-    const int comp = blockIdx.y;
-    xc += (size_t)comp * Lc.nn;
-    x += (size_t)comp * Lf.nn;
-    MG_LOOP(id, Lf.nn) {
-        if (Lf.fixed(id, comp)) continue;
-        int I[3];
-        mg_coords<N>(Lf.n, id, I);
-        int J0[3] = {0, 0, 0}, J1[3] = {0, 0, 0}, two[3] = {0, 0, 0};
-#pragma unroll
-        for (int d = 0; d < N; ++d) {
-            J0[d] = co[d] ? I[d] >> 1 : I[d];
-            two[d] = co[d] && (I[d] & 1);
-            J1[d] = J0[d] + 1 == Lc.n[d] ? 0 : J0[d] + 1;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int m = 0; m < (1 << N); ++m) {
-            double w = 1.0;
-            bool use = true;
-            int J[3] = {0, 0, 0};
-#pragma unroll
-            for (int d = 0; d < N; ++d) {
-                const int b = (m >> d) & 1;
-                if (b && !two[d]) use = false;
-                if (two[d]) w = w * 0.5;
-                J[d] = b ? J1[d] : J0[d];
-            }
-            if (use) acc += w * xc[J[0] + Lc.n[0] * (J[1] + (N > 2 ? Lc.n[1] * J[2] : 0))];
-        }
-        x[id] = x[id] + acc;
-    }
-}
 // the coarsest level (≤ 128 nodes): MG_NCOARSE sweeps from zero in one workgroup, x in LDS (component stride 128), double-buffered
 template <int N, int DOT, class Level, int MANY = 0>
 __global__ void __launch_bounds__(128) mg_coarsest_kernel(Level L, const double* __restrict__ r, double* __restrict__ x, MgState* st) {
@@ -607,8 +505,8 @@ static int mg_alloc_scalars(LsmHandle* h, MgSolver<Level>& o, int nstat, hipStre
     return LSM_OK;
 }
 
-// A Level whose grid wraps (lsm_homog.hip, lsm_hcond.hip) declares `static constexpr bool wraps = true` and launches the wrapping
-// transfers (mg_wrap_gather_kernel, mg_wrap_prolong_kernel) from
+// A Level whose grid wraps (cell_problem.h's CpLevel) declares `static constexpr bool wraps = true` and launches the wrapping
+// transfers (cell_problem.h's mg_wrap_gather_kernel, mg_wrap_prolong_kernel) from
 //   static launch_gather(N, stream, Lf, Lc, co, res, rc, st),  static launch_prolong(N, stream, Lf, Lc, co, xc, x, st);
 // every other Level takes mg_gather_kernel and mg_prolong_kernel, as before.
 template <class Level, class = void>

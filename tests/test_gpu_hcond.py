@@ -199,6 +199,26 @@ def test_the_first_iterate_is_the_restatements_to_rounding(name):
     dev.close()
 
 
+@pytest.mark.parametrize("name,precond", [(k, pc) for k in ("13x9", "9x5x7") for pc in ("mg", "jacobi")])
+def test_a_guess_at_the_pinned_node_is_ignored(name, precond):
+    """solve_rhs from a guess that is not zero at node 0: the bits, iterations and residual of the same guess with zero there, and
+    zero at the pin.  These two of R.FIRST_ITERATE have odd axes, which leave a coarsest level that one workgroup cannot hold in 2-D."""
+    lsm = _lsm()
+    cs = R.cases()[name]
+    dev = lsm.ConductivityHomogenization(_field(lsm, cs), precond=precond, **_kwargs(cs))
+    pin = (0,) * len(cs["n"])
+    f = dev.load(0)
+    x0 = np.random.default_rng(5).standard_normal(f.shape) * min(cs["h"])
+    x0[pin] = 0.0
+    xz, itz, relz = dev.solve_rhs(f, x0, rtol=RTOL, max_iters=3000)
+    x0[pin] = 1.0
+    xp, itp, relp = dev.solve_rhs(f, x0, rtol=RTOL, max_iters=3000)
+    print(f"{name} {precond}: {itz} iterations, relres {relz:.3e}, levels {dev.levels}")
+    assert itz > 1 and itp == itz and relp == relz
+    assert np.array_equal(_bits(xp), _bits(xz)) and xp[pin] == 0.0
+    dev.close()
+
+
 @pytest.mark.parametrize("n", [(801, 701), (90, 90, 70)])
 def test_grid_stride_shapes(n):
     """more nodes than 2048 × 256 threads, without a solve: the second trip of the grid-stride loops and the index arithmetic"""

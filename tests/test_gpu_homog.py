@@ -201,6 +201,41 @@ def test_the_first_iterate_is_the_restatements_to_rounding(name):
     dev.close()
 
 
+@pytest.mark.parametrize("name,precond", [(k, pc) for k in ("13x9", "9x5x7") for pc in ("mg", "jacobi")])
+def test_a_guess_at_the_pinned_node_is_ignored(name, precond):
+    """solve_rhs from a guess that is not zero at node 0, in every component: the bits, iterations and residual of the same guess with
+    zeros there, and zero at the pin.  These two of R.FIRST_ITERATE have odd axes, which leave a coarsest level that one workgroup cannot hold in 2-D."""
+    lsm = _lsm()
+    cs = R.cases()[name]
+    N = len(cs["n"])
+    dev = lsm.Homogenization(_field(lsm, cs), precond=precond, **_kwargs(cs))
+    pin = (slice(None),) + (0,) * N
+    f = dev.load(0)
+    x0 = np.random.default_rng(5).standard_normal(f.shape) * min(cs["h"])
+    x0[pin] = 0.0
+    xz, itz, relz = dev.solve_rhs(f, x0, rtol=RTOL, max_iters=3000)
+    x0[pin] = 1.0 + np.arange(N)
+    xp, itp, relp = dev.solve_rhs(f, x0, rtol=RTOL, max_iters=3000)
+    print(f"{name} {precond}: {itz} iterations, relres {relz:.3e}, levels {dev.levels}")
+    assert itz > 1 and itp == itz and relp == relz
+    assert np.array_equal(_bits(xp), _bits(xz)) and not xp[pin].any()
+    dev.close()
+
+
+def test_a_non_finite_right_hand_side_is_refused_and_changes_nothing():
+    lsm = _lsm()
+    cs = R.cases()["13x9"]
+    dev = lsm.homogenize(_field(lsm, cs), rtol=RTOL, **_kwargs(cs))
+    chi, C = dev.correctors(), dev.backend.homog_tensor(dev._handle())
+    f = dev.load(0)
+    f[1, 3, 4] = np.nan
+    with pytest.raises(lsm.LsmError, match=r"\(1 entries are not\)"):
+        dev.solve_rhs(f, rtol=RTOL)
+    assert np.array_equal(_bits(dev.correctors()), _bits(chi))
+    assert np.array_equal(_bits(dev.backend.homog_tensor(dev._handle())), _bits(C)) and np.array_equal(_bits(dev.tensor), _bits(C))
+    dev.close()
+
+
 @pytest.mark.parametrize("n", [(801, 701), (90, 90, 70)])
 def test_grid_stride_shapes(n):
     """more nodes than 2048 × 256 threads, without a solve: the second trip of the grid-stride loops and the index arithmetic"""

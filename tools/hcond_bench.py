@@ -15,7 +15,9 @@ correctors from zero; at 256², 1024², 64³ and 128³ cells.
   copy yardstick    --copy-tbs, or measured here: a device-to-device copy of 2^27 doubles, 8 bytes read and 8 written per element
   demo              a square cell with a round inclusion at 64² cells: the tensor, its harmonic/arithmetic bounds, the range of the
                     sensitivity of tr K^H, and three steps of an ascent on it
-These are first measurements: no test asserts them."""
+These are first measurements: no test asserts them.
+
+--refactor PARENT_LIB: the parent commit's library against this one, bits and speed (tools/cell_problem_ab.py); runs nothing else."""
 import argparse
 import json
 import os
@@ -143,8 +145,16 @@ def main():
     ap.add_argument("--copy-tbs", type=float, help="the copy yardstick in TB/s (default: measured here)")
     ap.add_argument("--out", default=OUT, help="output directory (default: profiles/hcond)")
     ap.add_argument("--no-write", action="store_true")
+    ap.add_argument("--refactor", metavar="PARENT_LIB", help="compare bits and speed between the parent commit's library and this one; run nothing else")
+    ap.add_argument("--refactor-out", help="with --refactor: the output directory (default: profiles/cell_problem)")
+    ap.add_argument("--refactor-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-demo", action="store_true")
     a = ap.parse_args()
+    if a.refactor or a.refactor_child:
+        import cell_problem_ab as ab
+        if a.refactor:
+            return ab.refactor(__file__, "hcond", a.refactor, a.reps, a.refactor_out)
+        return ab.child(sys.modules[__name__], lambda lsm, phi, pc: lsm.ConductivityHomogenization(phi, precond=pc), lambda hom: hom.backend.hcond_tensor(hom._handle()), a.reps)
     import lsm_amd as lsm
     elliptic = None
     ep = os.path.join(ROOT, "profiles", "elliptic", "elliptic_bench.json")

@@ -12,7 +12,9 @@ in 2-D), rtol 1e-8, all M correctors from zero; at 256², 1024², 64³ and 128³
   sensitivity       ms of sensitivity(W) (the cell pass and the node gather)
   demo              a square cell with a round hole at 64² cells: the tensor, its Reuss/Voigt bounds, the range of the
                     sensitivity of the bulk-like sum C00 + C11 + 2·C01, and three steps of an ascent on it
-These are first measurements: no test asserts them."""
+These are first measurements: no test asserts them.
+
+--refactor PARENT_LIB: the parent commit's library against this one, bits and speed (tools/cell_problem_ab.py); runs nothing else."""
 import argparse
 import json
 import os
@@ -125,8 +127,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--cases", nargs="*", default=list(SIZES))
     ap.add_argument("--no-write", action="store_true")
+    ap.add_argument("--refactor", metavar="PARENT_LIB", help="compare bits and speed between the parent commit's library and this one; run nothing else")
+    ap.add_argument("--refactor-out", help="with --refactor: the output directory (default: profiles/cell_problem)")
+    ap.add_argument("--refactor-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-demo", action="store_true")
     a = ap.parse_args()
+    if a.refactor or a.refactor_child:
+        import cell_problem_ab as ab
+        if a.refactor:
+            return ab.refactor(__file__, "homog", a.refactor, a.reps, a.refactor_out)
+        return ab.child(sys.modules[__name__], lambda lsm, phi, pc: lsm.Homogenization(phi, precond=pc), lambda hom: hom.backend.homog_tensor(hom._handle()), a.reps)
     import lsm_amd as lsm
     elastic = None
     ep = os.path.join(ROOT, "profiles", "elastic", "elastic_bench.json")
