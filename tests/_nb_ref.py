@@ -15,11 +15,15 @@ def ring_offsets(N):
 
 
 class NBRef:
-    def __init__(self, vals, nlayers):
+    def __init__(self, vals, nlayers, seed=None):
+        """`seed`: optional boolean mask of the nodes to seed instead of all of them.  The result is the same whenever
+        every cut cell of `vals` has all its corners in the seed (the caller's to check); a dict over a large grid whose
+        surface sits in a small box is wasted time."""
         self.n = vals.shape
         self.N = vals.ndim
         self.nlayers = nlayers
-        self.d = {I: float(vals[I]) for I in np.ndindex(*vals.shape)}   # seed every node ...
+        nodes = np.ndindex(*vals.shape) if seed is None else (tuple(int(i) for i in I) for I in np.argwhere(seed))
+        self.d = {I: float(vals[I]) for I in nodes}                      # seed every node ...
         self.ring = ring_offsets(self.N)
         self.update_band()                                               # ... then restrict to the band
 

@@ -527,11 +527,13 @@ def test_library_band_step_equals_the_stage_by_stage_sequence_bitwise(lsm, monke
 
 @pytest.mark.parametrize("dtype,nlayers", [("float64", 3), ("float32", 3), ("float64", 2)])
 def test_bit_row_update_equals_the_byte_mask_update_bitwise(lsm, monkeypatch, dtype, nlayers):
-    """update_band! through the bit-row kernels (band_bits / band_grow_bits / band_halo_bits: every node read once, mask
-    updated in place, new nodes extrapolated by the grow kernel, slope neighbours resolved in the halo list) against the
-    byte-mask kernels (LSM_BAND_BITS=0), on a band that stays a tile away from every face — the case that also takes the
-    bit-row halo search: band sets, band values, halo masks and the values every stage input gets on the halo, bit for bit,
-    over several RK3 steps of config 5's equation."""
+    """update_band! through the bit-row kernels (band_bits / band_grow_bits: every node read once, mask updated in place, new
+    nodes extrapolated by the grow kernel) against the byte-mask kernels (LSM_BAND_BITS=0): band sets, band values, halo masks
+    and the values every stage input gets on the halo, bit for bit, over several RK3 steps of config 5's equation.
+    The band keeps clear of the faces, but its work tiles do not: it occupies tiles 1 and 2 of the 4 along the last axis, so
+    their neighbours 0 and 3 lie on faces and the halo is searched by band_search3_kernel on both sides — none of the 6628
+    (6324 for nlayers = 2) list entries carries the 0x40 that band_halo_bits_kernel sets (printed below).  That kernel is
+    compared with the restatement in tests/test_gpu_band_update.py."""
     dt = np.dtype(dtype)
     n = (192, 64, 64)
     grid = lsm.CartesianGrid((-3, -1, -1), (3, 1, 1), n)
@@ -555,7 +557,10 @@ def test_bit_row_update_equals_the_byte_mask_update_bitwise(lsm, monkeypatch, dt
         vals = st.values()
         st.prepare(st.buf)                      # what a stage input looks like: band halo by extrapolation
         prepared = st.backend.download(st.buf)
-        return masks, vals, halo, prepared, int(st._hcount.item())
+        n = int(st._hcount.item())
+        flags = (st._hlist[:2 * n].cpu().numpy()[1::2] >> 56) & 0xff      # BandEntry::d[3] of the list's entries
+        print(f"bits={bits}: {int(((flags & 0x40) != 0).sum())} of {n} halo list entries carry 0x40 (written by band_halo_bits_kernel)")
+        return masks, vals, halo, prepared, n
 
     m0, v0, h0, p0, c0 = run(False)
     m1, v1, h1, p1, c1 = run(True)
